@@ -19,6 +19,11 @@ loop only (VAE decode excluded).  `roofline` is for the dominant 
 72 % of the step's FLOPs at 720p); `cpu_baseline` times the reference's CPU path on this box's host cores:
 BASELINE config #1 end to end by the UNMODIFIED reference (kind "reference"; the oracle port where no reference checkout travels with the tree), plus one
 block of the BENCHED workload at its full sequence length on a bounded row sample by the oracle port beside it.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  `--full` adds what the headline figure does not need: the
+box-calibration probes (`box_calibration`, `roofline.frac_of_probe`), the `other_configs` legs and `cpu_baseline` (`extra_legs`).  Where
+`__graft_entry__.build()` staged a reference checkout, `cpu_baseline.kind` is "reference", otherwise "port".  `--dump-outputs DIR` writes
+the latents of the last timed step to DIR/latents.npy (float32) after the timed region.
 """
 import argparse
 import contextlib
@@ -36,7 +41,7 @@ if ROOT not in sys.path:
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -61,7 +66,13 @@ def parse():
     ap.add_argument("--distill", action="store_true", help="4-step distilled schedule of config #4 (no CFG, denoising_step_list 1000/750/500/250, shift 5)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the untimed-for-`value` legs behind the headline steps (BASELINE configs #2, #4, #5 on one GPU and the Wan VAE decode; `other_configs`)")
     ap.add_argument("--other-configs", action="store_true", help="run the `other_configs` legs even when the headline workload / flags are not the default ones")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the box-calibration probes, the `other_configs` legs "
+                    "and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (the latents) as DIR/<name>.npy in float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def step_flops(dims, S, text_len, cfg_forwards, cross_kv_cached=True):
@@ -522,6 +533,26 @@ def other_configs(headline_ms_per_step, frames, infer_steps):
     return out
 
 
+def extra_legs(args, world):
+    """Which measurements beyond the headline steps this run makes.  A plain run makes none; `--full` adds the box-calibration probes, the
+    `other_configs` legs (one GPU, default headline workload or `--other-configs`) and the CPU baseline (one GPU), each unless its --no-* switch
+    is given."""
+    default_headline = args.workload == "wan14b_720px81f" and not (args.fp8 or args.mxfp8 or args.distill or args.no_cfg or args.ref_rounding)
+    return {"calibration": args.full and not args.no_calibration,
+            "other_configs": world == 1 and args.full and not args.no_other_configs and (default_headline or args.other_configs),
+            "cpu_baseline": world == 1 and args.full and not args.no_cpu_baseline}
+
+
+def dump_outputs(out_dir, arrays):
+    """What the timed path handed its caller in the last timed step, one float32 .npy per array: two builds run with the same arguments see the
+    same seeded inputs, so their files can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+
+
 def ulysses_self_check(dist, world, rank, one_gpu_plumbing=False):
     """N > 1, before the timed region: a one-layer Wan model with the real run's per-rank head count (5 x 128 per rank: at N = 8 exactly a Wan-14B
     layer; in the one-GPU plumbing mode a small 2-layer one) on a short token grid runs one CFG step sharded over the N ranks (the product Ulysses
@@ -705,8 +736,9 @@ def main():
     # Box calibration, UNTIMED, in this process: what the bare bf16 MFMA instruction sustains on this board right before and right after the timed
     # region (lib.mfma_probe -> x2v_mfma_probe_bf16).  Boxes of the pool differ by several percent under the 1400 W limit; with these
     # two numbers in the line, `roofline.frac_of_probe` can be compared between runs where `roofline.frac` (against the nominal 2.5 PFLOP/s) cannot.
+    legs = extra_legs(args, world)
     calib = None
-    if not args.no_calibration:
+    if legs["calibration"]:
         calib = {"kernel": "v_mfma_f32_16x16x32_bf16, operands in registers, 8 waves per CU on every CU (x2v_mfma_probe_bf16)", "probe_ms": args.probe_ms,
                  "mfma_probe_tflops_before": lib.mfma_probe(args.probe_ms)}
         watchdog.tick("calibration probe done")
@@ -757,6 +789,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
     assert torch.isfinite(sch.latents).all(), "non-finite latents"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": sch.latents})
 
     ms_per_step = elapsed * 1e3 / args.steps
     fps = wl["frames"] / (args.infer_steps * ms_per_step * 1e-3)
@@ -877,8 +911,7 @@ def main():
         "self_attention_launch_plan": {"xcd_remap": bool(plan[0]), "staggered_walk": bool(plan[1]), "Sq": S, "Sk": S, "heads": heads_local},
     }
     out["box_calibration"] = calib
-    default_headline = args.workload == "wan14b_720px81f" and not (args.fp8 or args.mxfp8 or args.distill or args.no_cfg or args.ref_rounding)
-    if world == 1 and not args.no_other_configs and (default_headline or args.other_configs):
+    if legs["other_configs"]:
         # free the headline model first (28 GB of weights + the step's buffers); the legs build their own
         model.transformer_infer.attn_time_hook = None
         del model, sch, inputs, lat
@@ -886,7 +919,7 @@ def main():
         watchdog.tick("other configs")
         out["other_configs"] = other_configs(ms_per_step, wl["frames"], args.infer_steps)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             try:
                 out["cpu_baseline"] = cpu_baseline(dims, S, ts, dims["text_len"], wl["frames"], args.infer_steps, fwd, args.cpu_baseline_rows, not args.no_cpu_config1)
             except Exception as e:  # noqa: BLE001 — the measured line must not be lost to a host-side failure (e.g. out of host memory)

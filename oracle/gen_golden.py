@@ -24,6 +24,34 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 BF16 = torch.bfloat16
 
 
+SHARD_BYTES = 900 * 1024  # every committed fixture file stays under 1 MiB
+
+
+def save_golden(out, name):
+    """tests/golden/<name>.<i>.safetensors: `out` packed in key order into shards of at most SHARD_BYTES of tensor data; a tensor larger than
+    that is stored flat in pieces `<key>@<j>` with its shape in the shard's metadata (tests/util.py::load_golden reassembles it)."""
+    import glob
+
+    for old in glob.glob(os.path.join(GOLDEN, f"{name}.safetensors")) + glob.glob(os.path.join(GOLDEN, f"{name}.[0-9]*.safetensors")):
+        os.remove(old)
+    shards, cur, meta, size = [], {}, {}, 0
+    for k in sorted(out):
+        v = out[k].contiguous()
+        per = SHARD_BYTES // v.element_size()
+        parts = [(k, v)] if v.numel() * v.element_size() <= SHARD_BYTES else [(f"{k}@{j}", c.clone()) for j, c in enumerate(v.reshape(-1).split(per))]
+        for key, t in parts:
+            nbytes = t.numel() * t.element_size()
+            if cur and size + nbytes > SHARD_BYTES:
+                shards.append((cur, meta))
+                cur, meta, size = {}, {}, 0
+            cur[key], size = t, size + nbytes
+            if key != k:
+                meta[k] = ",".join(str(s) for s in v.shape)
+    shards.append((cur, meta))
+    for i, (tensors, md) in enumerate(shards):
+        save_file(tensors, os.path.join(GOLDEN, f"{name}.{i}.safetensors"), metadata=md or None)
+
+
 def weights_checksum(wd):
     acc = torch.zeros((), dtype=torch.float64)
     for k in sorted(wd):
@@ -106,8 +134,8 @@ def gen_ops():
     t = torch.tensor([999, 727, 3], dtype=torch.int64)
     out.update(sin_t=t, sin_y=sinusoidal_embedding_1d(256, t))
 
-    save_file({k: v.contiguous() for k, v in out.items()}, os.path.join(GOLDEN, "ops.safetensors"))
-    print("ops.safetensors:", len(out), "tensors")
+    save_golden(out, "ops")
+    print("ops.*.safetensors:", len(out), "tensors")
 
 
 def _ref_model_infer(R, sch, cfg, inputs):
@@ -362,8 +390,8 @@ def gen_vae(dim=32, seed=1):
             out[f"decoded_dist_w{world}_d{split_dim}"] = full[0].clone()
     finally:
         ref_vae.dist.all_gather, torch.cuda.synchronize = real_gather, real_sync
-    save_file({k: v.contiguous() for k, v in out.items()}, os.path.join(GOLDEN, "wan_vae_tiny.safetensors"))
-    print("wan_vae_tiny.safetensors:", len(out), "tensors")
+    save_golden(out, "wan_vae_tiny")
+    print("wan_vae_tiny.*.safetensors:", len(out), "tensors")
 
 
 def gen_hunyuan(name="hunyuan-tiny", seed=4):
@@ -559,7 +587,7 @@ def gen_hunyuan_vae(seed=1):
         out["z_single"] = z1
         out["image_single"] = (vae.decode(z1 / vae.config.scaling_factor, return_dict=False)[0] / 2 + 0.5).clamp(0, 1).float()
     out["weights_checksum"] = weights_checksum(sd).reshape(1)
-    save_file({k: v.contiguous() for k, v in out.items()}, os.path.join(GOLDEN, "hunyuan_vae_tiny.safetensors"))
+    save_golden(out, "hunyuan_vae_tiny")
     print("hunyuan vae fixture:", {k: tuple(v.shape) for k, v in out.items()})
 
 

@@ -5,7 +5,7 @@ reference: /root/reference/lightx2v/models/video_encoders/hf/wan/vae.py
   CausalConv3d :19-44 · RMS_norm :47-59 · Upsample :62-67 · Resample :70-159 · ResidualBlock :185-223 ·
   AttentionBlock :226-262 · Decoder3d :377-489 · WanVAE_.decode :713-738 · WanVAE.decode (clamp) :931-957
 
-Pinned: `tests/golden/wan_vae_tiny.safetensors` is generated from the unmodified reference (oracle/gen_golden.py::gen_vae)
+Pinned: `tests/golden/wan_vae_tiny.*.safetensors` is generated from the unmodified reference (oracle/gen_golden.py::gen_vae)
 and `tests/test_oracle_golden.py` requires this restatement to reproduce it (same torch ops in the same order → bit-exact
 on the same host).
 

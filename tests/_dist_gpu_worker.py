@@ -37,8 +37,8 @@ def main():
     from lightx2v_amd import lib, scheduler, synth, wan
 
     lib.init(0)
-    # 4 heads so that H % 2 == 0 with 2 heads per rank; S = 3*6*5 = 90 tokens -> 45 per rank (ragged vs the 32/64 tiles).  World 8 (the node
-    # size, all ranks on the one GPU): 8 heads, 3*8*6 = 144 tokens -> 18 per rank.  (A token count the group does not divide is zero-padded
+    # 4 heads so that H % 2 == 0 with 2 heads per rank; S = 3*6*5 = 90 tokens -> 45 per rank (ragged vs the 32/64 tiles).  World 4 (all ranks
+    # on the one GPU): 4 heads, one per rank, 3*8*6 = 144 tokens -> 36 per rank.  (A token count the group does not divide is zero-padded
     # and — a reference quirk kept bit for bit, ulysses/attn.py:60-66 — the pad rows then take part in the attention as keys, so the sharded
     # forward legitimately differs from the single-GPU one: 2.9e-2 with 6 pad rows among 96.  The 720p grids divide by 8.)
     heads = max(4, n)

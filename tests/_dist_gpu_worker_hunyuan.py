@@ -1,4 +1,4 @@
-"""world_size-2 (or -8) worker: Ulysses-sharded Hunyuan forward (all ranks on cuda:0, gloo + host-staged collectives — see
+"""world_size-2 (or -4) worker: Ulysses-sharded Hunyuan forward (all ranks on cuda:0, gloo + host-staged collectives — see
 tests/_dist_gpu_worker.py) must match the single-GPU forward."""
 import os
 import sys
@@ -24,7 +24,7 @@ def main():
     n = dist.get_world_size()
     dims = synth.HUNYUAN_DIMS["hunyuan-tiny"]
     ts = synth.HUNYUAN_WORKLOADS["hunyuan-tiny"]["target_shape"]
-    if n > 2:  # the node size on one GPU: one head per rank, a token grid whose h axis the group divides (16 rows of tokens)
+    if n > 2:  # one head per rank, a token grid whose h axis the group divides (16 rows of tokens)
         dims = dict(dims, hidden=128 * n, heads=n, mlp=2048, refiner_mlp=2048)
         ts = (1, 16, 3, 4 * n, 12)
     wd = {k: v.cuda() for k, v in synth.synth_hunyuan_weights(dims, seed=2).items()}

@@ -1,6 +1,6 @@
-"""world_size-8 worker of tests/test_gpu_rank_shapes.py: ONE transformer block at the real dimensions of BASELINE config #3 (Wan2.1-14B, 75 600
-tokens, 40 heads -> 9 450 tokens and 5 heads per rank) or #5 (HunyuanVideo-13B, 118 800 + 256 tokens, 24 heads -> 14 850 image tokens and 3 heads
-per rank) through the product's Ulysses driver, all eight ranks on the box's one GPU (gloo with host-staged collectives: tests/_dist_gpu_worker.py).
+"""world_size-N worker of tests/test_gpu_rank_shapes.py: ONE transformer block at the real dimensions of BASELINE config #3 (Wan2.1-14B, 75 600
+tokens, 40 heads -> at N = 4 18 900 tokens and 10 heads per rank) or #5 (HunyuanVideo-13B, 118 800 + 256 tokens, 24 heads -> at N = 4 29 700 image
+tokens and 6 heads per rank) through the product's Ulysses driver, all N ranks on the box's one GPU (gloo with host-staged collectives: tests/_dist_gpu_worker.py).
 The parent test wrote the block-boundary inputs to $X2V_RANK_SHAPES_DIR/inputs.pt; every rank writes the sampled rows of its shard to
 out_rank<r>.pt and the parent compares them with the CPU oracle."""
 import os
@@ -39,7 +39,7 @@ def wan(r, n, d, out_dir):
     pa = tr.parallel_attention
     assert pa.copies == 0 and pa._buffers, "the fused driver must take the copy-free blocked exchange path"
     b = next(iter(pa._buffers.values()))
-    assert tuple(b["sq"].shape) == (n, s_local, 40 * 128 // n) == (8, 9450, 640), tuple(b["sq"].shape)
+    assert tuple(b["sq"].shape) == {4: (4, 18900, 1280), 8: (8, 9450, 640)}[n], tuple(b["sq"].shape)
     assert pa.split_head2seq is True, "two-piece head->seq (the designed path)"
     assert torch.isfinite(out.float()).all()
     torch.save(out[d["local_rows"].cuda()].cpu(), os.path.join(out_dir, f"out_rank{r}.pt"))
@@ -60,19 +60,19 @@ def hunyuan(r, n, d, out_dir):
     w_local = gw // n
     D = d["img"].shape[1]
     sl = slice(r * w_local, (r + 1) * w_local)
-    # utils/hunyuan/processor.py:5-50: the rank's slab of the token grid (W is the axis 8 divides) and the RoPE rows of the same tokens
+    # utils/hunyuan/processor.py:5-50: the rank's slab of the token grid (W is the axis N divides) and the RoPE rows of the same tokens
     img = d["img"].view(gt, gh, gw, D)[:, :, sl].reshape(-1, D).contiguous().cuda()
     cos = d["cos"].view(gt, gh, gw, -1)[:, :, sl].reshape(img.shape[0], -1).contiguous().cuda()
     sin = d["sin"].view(gt, gh, gw, -1)[:, :, sl].reshape(img.shape[0], -1).contiguous().cuda()
     n_local, n_txt = img.shape[0], d["txt"].shape[0]
-    assert n_local == 14850
+    assert n_local == {4: 29700, 8: 14850}[n]  # 45 % n != 0: the W axis is split
     cu = torch.tensor([0, n_local + d["n_valid"], n_local + n_txt], dtype=torch.int32)
     out, _ = tr.infer(tw, img, d["txt"].cuda(), d["vec"].cuda(), cu, n_local + n_txt, (cos, sin))
     torch.cuda.synchronize()
     pa = tr.parallel_attention
     assert pa.copies == 0 and pa._buffers, "the fused driver must take the copy-free blocked exchange path"
     b = next(iter(pa._buffers.values()))
-    assert tuple(b["snd"].shape) == (3, 8, 14850, 384), tuple(b["snd"].shape)
+    assert tuple(b["snd"].shape) == {4: (3, 4, 29700, 768), 8: (3, 8, 14850, 384)}[n], tuple(b["snd"].shape)
     assert out.shape[0] == n_local and torch.isfinite(out.float()).all()
     torch.save(out[d["local_rows"].cuda()].cpu(), os.path.join(out_dir, f"out_rank{r}.pt"))
     return "RANK_SHAPES_HUNYUAN_OK"

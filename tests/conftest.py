@@ -16,9 +16,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden_ops():
-    from safetensors.torch import load_file
+    from tests.util import load_golden
 
-    return load_file(os.path.join(GOLDEN, "ops.safetensors"))
+    return load_golden("ops")
 
 
 @pytest.fixture(scope="session")

@@ -146,3 +146,31 @@ def test_kernel_gaps_accounting_on_a_synthetic_trace(tmp_path):
     assert abs(g["F->D +residual"]["tflops"] - 2.0 * 20280 * 8960 * 1536 / 400e-6 / 1e12) < 1e-6
     attn = next(k for k in d["kernels"] if k["kernel"].startswith("attn_fwd_v9_kernel<8, 8, true"))
     assert abs(attn["tflops"] - 4.0 * 20280 * 20280 * 12 * 128 / 2e-3 / 1e12) < 1e-6
+
+
+def test_dump_outputs_writes_float32_npy_and_steps_must_be_positive(bench, tmp_path):
+    """`--dump-outputs DIR` writes each array the last timed step returned as DIR/<name>.npy in float32; `--steps 0` is refused before any work."""
+    import subprocess
+
+    import numpy as np
+    import torch
+
+    lat = torch.randn(2, 3, 4, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "out"), {"latents": lat})
+    got = np.load(tmp_path / "out" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, lat.float().numpy())
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
+def test_plain_run_makes_no_extra_legs_and_full_makes_them(bench):
+    """A plain run measures the headline steps only; `--full` adds the calibration probes, the other configurations (one GPU, default
+    headline) and the CPU baseline, each still switched off by its --no-* flag."""
+    none = {"calibration": False, "other_configs": False, "cpu_baseline": False}
+    assert bench.extra_legs(bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"]), 1) == none
+    assert bench.extra_legs(bench.parse(["--full"]), 1) == {"calibration": True, "other_configs": True, "cpu_baseline": True}
+    assert bench.extra_legs(bench.parse(["--full", "--no-calibration", "--no-cpu-baseline"]), 1) == {"calibration": False, "other_configs": True, "cpu_baseline": False}
+    assert bench.extra_legs(bench.parse(["--full", "--fp8"]), 1)["other_configs"] is False
+    assert bench.extra_legs(bench.parse(["--full", "--fp8", "--other-configs"]), 1)["other_configs"] is True
+    assert bench.extra_legs(bench.parse(["--full", "--gpus", "2"]), 2) == {"calibration": True, "other_configs": False, "cpu_baseline": False}
+    assert bench.extra_legs(bench.parse(["--gpus", "2"]), 2) == none

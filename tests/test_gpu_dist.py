@@ -8,12 +8,15 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
+# The GPU machines this suite is checked on allow at most 6 processes with the GPU open at once.  A run of the suite with 8-rank cases was
+# stopped there with 10 open: pytest, the torch.distributed.run launcher and 8 ranks (the launcher imports torch and was counted).  So no test
+# here starts more than 4 ranks under the launcher, and a script that re-launches itself (its bare parent is one more process) more than 3.
 
 
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_ulysses_world2_on_one_gpu(world):
-    """world 8 = the node size, all eight ranks driving the one GPU of the box: the HIP Ulysses path (blocked exchange buffers, K-blocked output
-    projection, sharded RoPE offsets with padding rows, the CFG branches on two streams) at the partitioning the scaling bench uses."""
+    """world 4: all four ranks driving the one GPU of the box: the HIP Ulysses path (blocked exchange buffers, K-blocked output projection,
+    sharded RoPE offsets, the CFG branches on two streams) with one head per rank."""
     env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29541 + 10 * (world > 2)),
            os.path.join(ROOT, "tests", "_dist_gpu_worker.py")]
@@ -35,7 +38,7 @@ def test_ulysses_w8a8_world2_on_one_gpu():
     assert "DIST_GPU_OK" in p.stdout and "w8a8" in p.stdout
 
 
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_ulysses_hunyuan_world2_on_one_gpu(world):
     env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29543 + 10 * (world > 2)),
@@ -73,9 +76,9 @@ def test_ulysses_over_rccl_world1():
     assert "DIST_GPU_RCCL1_OK" in p.stdout
 
 
-@pytest.mark.parametrize("gpus", [2, 4, 8])
+@pytest.mark.parametrize("gpus", [2, 4])
 def test_bench_n8_code_path_on_one_gpu(gpus):
-    """`python bench.py --gpus N` (N = 2, 4, 8: what the driver's scaling run launches) END TO END on a one-GPU box (X2V_ONE_GPU_TEST=1: all ranks drive cuda:0 over gloo with host-staged collectives,
+    """`python bench.py --full --gpus N` (N = 2 bare, N = 4 under the launcher: what the driver's scaling run launches) END TO END on a one-GPU box (X2V_ONE_GPU_TEST=1: all ranks drive cuda:0 over gloo with host-staged collectives,
     lightx2v_amd/launch.py): the self-launch under torch.distributed.run, the Ulysses self-check walking the designed path (CFG branches on two
     streams, blocked buffers, two-piece head->seq), the per-instance settings handed to the timed model, the timed loop with barriers and the
     max-over-ranks reduction, the per-launch attention timers and the JSON line.  Everything the 8-GPU scaling run executes except RCCL itself;
@@ -84,8 +87,9 @@ def test_bench_n8_code_path_on_one_gpu(gpus):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0", X2V_ONE_GPU_TEST="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "wan-tiny-h8", "--steps", "2", "--warmup", "1", "--infer-steps", "4", "--probe-ms", "100"],
-                       capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    launcher = [] if gpus <= 3 else ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1", "--master-port", "29551"]
+    p = subprocess.run([sys.executable, *launcher, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--workload", "wan-tiny-h8", "--steps", "2", "--warmup", "1",
+                        "--infer-steps", "4", "--probe-ms", "100"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -109,15 +113,56 @@ def test_bench_n8_code_path_on_one_gpu(gpus):
     assert r["launches_timed"] == 2 * 2 * 2 * 2 and r["forwards_per_launch"] == 0.5, r  # 2 steps x 2 layers x 2 CFG branches x 2 head->seq pieces
 
 
-def test_e2e_n8_code_path_on_one_gpu():
-    """`python tools/e2e.py --gpus 8` end to end in the one-GPU plumbing mode: the Ulysses denoise loop (CFG branches on two streams) followed by
-    the 8-way halo-split parallel VAE decode (`decode_dist`, vae.py:883-929) on a 2-layer, 8-head model — the N-rank code of the end-to-end driver."""
+def test_e2e_bare_self_launch_on_one_gpu():
+    """`python tools/e2e.py --gpus 2` without a launcher environment re-runs itself as 2 ranks under torch.distributed.run (launch.ranks) and
+    completes the Ulysses loop and the 2-way parallel decode in the one-GPU plumbing mode."""
     import json
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0", X2V_ONE_GPU_TEST="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "e2e.py"), "--gpus", "8", "--workload", "wan-tiny-h8", "--steps", "3"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "e2e.py"), "--gpus", "2", "--workload", "wan-tiny-h8", "--steps", "2"],
+                       capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "no launcher environment, starting -m torch.distributed.run" in p.stderr
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["n_gpus"] == 2 and d["parallelism"] == "ulysses-sp2 + decode_dist" and d["steps"] == 2 and d["video_shape"] == [1, 3, 9, 128, 96], d
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline line without the --full legs, and `--dump-outputs` holds the latents after the
+    last timed step: warm-up 1 + 1 timed step and warm-up 0 + 2 timed steps end on the same latents, one step fewer does not."""
+    import json
+
+    import numpy as np
+
+    def run(steps, warmup, name):
+        out = tmp_path / name
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "wan-tiny-h8", "--steps", str(steps), "--warmup", str(warmup),
+                            "--infer-steps", "4", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["box_calibration"] is None and "other_configs" not in d and "cpu_baseline" not in d, sorted(d)
+        lat = np.load(out / "latents.npy")
+        assert lat.dtype == np.float32 and list(lat.shape) == d["config"]["latent_shape"] and np.isfinite(lat).all()
+        return lat
+
+    a, b, c = run(1, 1, "a"), run(2, 0, "b"), run(1, 0, "c")
+    assert np.array_equal(a, b), float(np.abs(a - b).max())
+    assert not np.array_equal(a, c)
+
+
+def test_e2e_n8_code_path_on_one_gpu():
+    """`tools/e2e.py --gpus 4` under the launcher, end to end in the one-GPU plumbing mode: the Ulysses denoise loop (CFG branches on two streams)
+    followed by the 4-way halo-split parallel VAE decode (`decode_dist`, vae.py:883-929) on a 2-layer, 8-head model — the N-rank code of the
+    end-to-end driver."""
+    import json
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0", X2V_ONE_GPU_TEST="1")
+    launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1", "--master-port", "29553"]
+    p = subprocess.run([sys.executable, *launcher, os.path.join(ROOT, "tools", "e2e.py"), "--gpus", "4", "--workload", "wan-tiny-h8", "--steps", "3"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
-    assert d["n_gpus"] == 8 and d["parallelism"] == "ulysses-sp8 + decode_dist" and d["steps"] == 3 and d["video_shape"] == [1, 3, 9, 128, 96], d
+    assert d["n_gpus"] == 4 and d["parallelism"] == "ulysses-sp4 + decode_dist" and d["steps"] == 3 and d["video_shape"] == [1, 3, 9, 128, 96], d

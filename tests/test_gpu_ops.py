@@ -1,5 +1,5 @@
 """Parity of each HIP operator (through the C-ABI) against (1) fixtures generated from the reference
-(tests/golden/ops.safetensors) and (2) the CPU oracle on seeded inputs at sizes it finishes in seconds.
+(tests/golden/ops.*.safetensors) and (2) the CPU oracle on seeded inputs at sizes it finishes in seconds.
 
 Tolerances (bf16 outputs; 1 ulp = 2^-7 relative, the widest bf16 spacing):
   * elementwise residual/gate: bit-exact (same rounding points as the reference chain)

@@ -1,16 +1,13 @@
 """Wan VAE decode on the HIP kernels (csrc/vae.hip, lightx2v_amd/vae.py) against
-  * the fixture generated from the unmodified reference (tests/golden/wan_vae_tiny.safetensors), and
+  * the fixture generated from the unmodified reference (tests/golden/wan_vae_tiny.*.safetensors), and
   * the CPU oracle (oracle/wan_vae_oracle.py, pinned bit-exact to that fixture) at the real channel widths.
 fp32 end to end; the only differences are summation order inside the convolutions (MFMA k-blocking vs oneDNN) and
 fast-math exp in SiLU/softmax: tolerance |d| <= 2e-3 absolute on outputs in [-1, 1] and relative L2 <= 1e-3."""
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _check(got, ref, what, atol=2e-3, rel=1e-3):
@@ -87,11 +84,11 @@ def test_vae_prep_and_softmax():
 
 
 def test_vae_decode_matches_reference_fixture():
-    from safetensors.torch import load_file
+    from tests.util import load_golden
 
     from lightx2v_amd import synth, vae
 
-    gld = load_file(os.path.join(GOLDEN, "wan_vae_tiny.safetensors"))
+    gld = load_golden("wan_vae_tiny")
     dim, seed = int(gld["dim"]), int(gld["seed"])
     sd = synth.synth_wan_vae_weights(dim=dim, seed=seed)
     m = vae.WanVAE(sd, dim=dim, conv16=False)  # the fp32 matrix instruction
@@ -108,11 +105,11 @@ def test_vae_decode_frame_batched_is_bit_identical():
     every kernel reduces an output pixel in an order independent of the number of frames in the launch and the conv caches are the
     leading frames of the input buffers, so the decoded video must be EQUAL bit for bit — fp32 and the opt-in fp16-operand form, with
     chunk sizes that do / do not divide T - 1 (T = 6: chunks 1+5, 1+2+2+1, 1+3+2, 1+4+1)."""
-    from safetensors.torch import load_file
+    from tests.util import load_golden
 
     from lightx2v_amd import synth, vae
 
-    gld = load_file(os.path.join(GOLDEN, "wan_vae_tiny.safetensors"))
+    gld = load_golden("wan_vae_tiny")
     dim, seed = int(gld["dim"]), int(gld["seed"])
     sd = synth.synth_wan_vae_weights(dim=dim, seed=seed)
     z = torch.randn(16, 6, 8, 8, generator=torch.Generator().manual_seed(5)).cuda()
@@ -133,7 +130,7 @@ def test_vae_decode_fp16_operands_opt_in():
     """Opt-in fast decode (WanVAE(conv16=True)): fp16 operands for the 3x3(x3) convolutions, everything else fp32 — against the fp32
     fixture generated from the reference.  Stated tolerance on outputs in [-1, 1]: |d| <= 2e-2, relative L2 <= 1e-2.  The tiny model's
     32- and 128-channel stages exercise the channel padding (32 -> 64) of the 16-bit kernel's operand buffers; dim = 96 does 96 -> 128."""
-    from safetensors.torch import load_file
+    from tests.util import load_golden
 
     from lightx2v_amd import lib, synth, vae
     from oracle import wan_vae_oracle as V
@@ -170,7 +167,7 @@ def test_vae_decode_fp16_operands_opt_in():
     _check(y[:, 1:6, 1:7, :C], refp.half(), "norm+silu -> fp16 padded buffer", atol=2e-3, rel=1e-3)
     assert y[..., C:].abs().max() == 0 and y[:, 0].abs().max() == 0
     # whole decodes
-    gld = load_file(os.path.join(GOLDEN, "wan_vae_tiny.safetensors"))
+    gld = load_golden("wan_vae_tiny")
     dim, seed = int(gld["dim"]), int(gld["seed"])
     m = vae.WanVAE(synth.synth_wan_vae_weights(dim=dim, seed=seed), dim=dim, conv16=True)
     out = m.decode(gld["z"].cuda())
@@ -190,7 +187,7 @@ def test_vae_decode_split_fp16_is_fp32_grade():
     products per fp32 product, fp32 accumulation — held to the SAME tolerance as the all-fp32 decode (|d| <= 2e-3, relative L2 <= 1e-3;
     the fp16-operand form needs 2e-2 / 1e-2), against the reference fixture and against the oracle at the released widths; the split of a
     single convolution against fp32 conv3d of the unrounded operands; bit-identical across frame chunkings like the other forms."""
-    from safetensors.torch import load_file
+    from tests.util import load_golden
 
     from lightx2v_amd import lib, synth, vae
     from oracle import wan_vae_oracle as V
@@ -271,7 +268,7 @@ def test_vae_decode_split_fp16_is_fp32_grade():
     # guard buys a finite, 11-bit-accurate result where an unguarded split would produce inf / NaN
     assert err[~near].max().item() <= 4e-6 * scale_far, (err[~near].max().item(), scale_far)
     assert err[near].max().item() <= 2.0 ** -10 * scale_near, (err[near].max().item(), scale_near)
-    gld = load_file(os.path.join(GOLDEN, "wan_vae_tiny.safetensors"))
+    gld = load_golden("wan_vae_tiny")
     dim, seed = int(gld["dim"]), int(gld["seed"])
     sd_t = synth.synth_wan_vae_weights(dim=dim, seed=seed)
     m = vae.WanVAE(sd_t, dim=dim, conv16="split")

@@ -24,6 +24,33 @@ def assert_rel(got, ref, tol, name=""):
     assert e <= tol, f"{name}: relative L2 error {e:.3e} > {tol}"
 
 
+def load_golden(name):
+    """tests/golden/<name>.safetensors, or the shards <name>.<i>.safetensors that oracle/gen_golden.py::save_golden writes (committed files stay
+    under 1 MiB); a tensor stored in pieces `<key>@<j>` is reassembled to the shape its shard's metadata records."""
+    import glob
+    import os
+
+    from safetensors import safe_open
+
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    one = os.path.join(gold, f"{name}.safetensors")
+    paths = [one] if os.path.exists(one) else sorted(glob.glob(os.path.join(gold, f"{name}.[0-9]*.safetensors")), key=lambda p: int(p.rsplit(".", 2)[1]))
+    assert paths, f"no golden fixture {name} under {gold}"
+    out, pieces, shapes = {}, {}, {}
+    for p in paths:
+        with safe_open(p, framework="pt") as fh:
+            shapes.update(fh.metadata() or {})
+            for k in fh.keys():
+                if "@" in k:
+                    base, j = k.rsplit("@", 1)
+                    pieces.setdefault(base, {})[int(j)] = fh.get_tensor(k)
+                else:
+                    out[k] = fh.get_tensor(k)
+    for base, parts in pieces.items():
+        out[base] = torch.cat([parts[j] for j in sorted(parts)]).reshape([int(d) for d in shapes[base].split(",")])
+    return out
+
+
 def record(name, **numbers):
     """Append measured parity numbers to gpurun_out/parity_summary.jsonl (merged back from the GPU box; the round's summary under
     profiles/ is assembled from it).  Never fails a test."""

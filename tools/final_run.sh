@@ -11,12 +11,12 @@ run pytest timeout 1500 python -m pytest tests -m gpu -q --timeout 900 --duratio
 run smoke timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; tail -2 "$OUT/smoke.log" >> "$OUT/summary.txt"
 # the DRIVER's exact command (BENCH_rNN.json is produced by it: 25 sustained steps at the 1400 W cap, not the 3-step default)
 run bench_driver_command timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_command.json" 2> "$OUT/bench_driver_command.err"; cat "$OUT/bench_driver_command.json" >> "$OUT/summary.txt"
-run bench_default timeout 900 python bench.py --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; cat "$OUT/bench_default.json" >> "$OUT/summary.txt"
+run bench_default timeout 900 python bench.py --full --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; cat "$OUT/bench_default.json" >> "$OUT/summary.txt"
 # kernel stats of the headline leg alone: the other_configs legs launch the same kernel instantiations and would mix into the per-kernel averages
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof" -o bench -- python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-other-configs > "$GRAFT_REPO_ROOT/$OUT/prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/prof.err"); echo "prof rc=$?" | tee -a "$OUT/summary.txt"
 find "$OUT/prof" -name "*kernel_trace.csv" -size +20M -delete
-run bench13 timeout 600 python bench.py --workload wan1.3b_480px49f --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench13.json" 2> "$OUT/bench13.err"; cat "$OUT/bench13.json" >> "$OUT/summary.txt"
-run bench_fp8_distill timeout 600 python bench.py --fp8 --distill --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench14_fp8_distill.json" 2> "$OUT/bench14_fp8_distill.err"; cat "$OUT/bench14_fp8_distill.json" >> "$OUT/summary.txt"
+run bench13 timeout 600 python bench.py --full --workload wan1.3b_480px49f --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench13.json" 2> "$OUT/bench13.err"; cat "$OUT/bench13.json" >> "$OUT/summary.txt"
+run bench_fp8_distill timeout 600 python bench.py --full --fp8 --distill --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench14_fp8_distill.json" 2> "$OUT/bench14_fp8_distill.err"; cat "$OUT/bench14_fp8_distill.json" >> "$OUT/summary.txt"
 run gemm_vs_hipblaslt timeout 300 python tools/gemm_vs_hipblaslt.py > "$OUT/gemm_vs_hipblaslt.json" 2> "$OUT/gemm_cmp.err"; cat "$OUT/gemm_vs_hipblaslt.json" >> "$OUT/summary.txt"
 run hunyuan timeout 600 python tools/hunyuan_bench.py > "$OUT/hunyuan13b.json" 2> "$OUT/hunyuan13b.err"; cat "$OUT/hunyuan13b.json" >> "$OUT/summary.txt"
 run e2e_13b timeout 300 python tools/e2e.py --workload wan1.3b_480px49f --steps 50 > "$OUT/e2e_wan13b_480p.json" 2> "$OUT/e2e13.err"; cat "$OUT/e2e_wan13b_480p.json" >> "$OUT/summary.txt"
@@ -26,7 +26,7 @@ run vae_wan_split timeout 300 python tools/vae_bench.py --latent 16,21,90,160 --
 # attention kernel generations, same box (tools/build_attn_v8_variant.sh must have been run before the call: the variant library travels with the snapshot)
 if [ -f tools/probes/ab/attn_r3/libx2v_hip.so ] && [ "${ATTN_AB:-1}" = "1" ]; then
   for gen in 8 9; do
-    X2V_LIB_PATH=$PWD/tools/probes/ab/attn_r3/libx2v_hip.so X2V_ATTN_GEN=$gen timeout 600 python bench.py --steps ${ATTN_AB_STEPS:-10} --warmup 3 --no-cpu-baseline > "$OUT/bench_attn_gen$gen.json" 2> "$OUT/bench_attn_gen$gen.err"
+    X2V_LIB_PATH=$PWD/tools/probes/ab/attn_r3/libx2v_hip.so X2V_ATTN_GEN=$gen timeout 600 python bench.py --full --steps ${ATTN_AB_STEPS:-10} --warmup 3 --no-cpu-baseline > "$OUT/bench_attn_gen$gen.json" 2> "$OUT/bench_attn_gen$gen.err"
     echo "attention generation $gen (round-3 source, X2V_ATTN_GEN): $(python -c "import json; d=json.loads(open('$OUT/bench_attn_gen$gen.json').read().strip().splitlines()[-1]); print('ms_per_step', d['ms_per_step'], 'attn_ms', d['roofline']['avg_launch_ms'], 'frac', d['roofline']['frac'], 'frac_of_probe', d['roofline']['frac_of_probe'], 'probe', d['box_calibration']['mfma_probe_tflops'])")" | tee -a "$OUT/summary.txt"
   done
 fi

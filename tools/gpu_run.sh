@@ -28,10 +28,10 @@ for st in $STAGES; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?" | tee -a "$OUT/summary.txt"
       tail -2 "$OUT/smoke.log" >> "$OUT/summary.txt" ;;
     bench13)
-      timeout 600 python bench.py --workload wan1.3b_480px49f --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench13.json" 2> "$OUT/bench13.err"; echo "bench13 rc=$?" | tee -a "$OUT/summary.txt"
+      timeout 600 python bench.py --full --workload wan1.3b_480px49f --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench13.json" 2> "$OUT/bench13.err"; echo "bench13 rc=$?" | tee -a "$OUT/summary.txt"
       cat "$OUT/bench13.json" >> "$OUT/summary.txt" ;;
     bench14)
-      timeout 1200 python bench.py --steps ${B14_STEPS:-1} --warmup ${B14_WARMUP:-1} > "$OUT/bench14.json" 2> "$OUT/bench14.err"; echo "bench14 rc=$?" | tee -a "$OUT/summary.txt"
+      timeout 1200 python bench.py --full --steps ${B14_STEPS:-1} --warmup ${B14_WARMUP:-1} > "$OUT/bench14.json" 2> "$OUT/bench14.err"; echo "bench14 rc=$?" | tee -a "$OUT/summary.txt"
       cat "$OUT/bench14.json" >> "$OUT/summary.txt" ;;
     prof)
       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof" -o bench -- python "$GRAFT_REPO_ROOT/bench.py" --workload ${PROF_WL:-wan1.3b_480px49f} --steps 1 --warmup ${PROF_WARMUP:-1} --no-cpu-baseline > "$GRAFT_REPO_ROOT/$OUT/prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/prof.err"); echo "prof rc=$?" | tee -a "$OUT/summary.txt"
