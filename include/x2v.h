@@ -357,6 +357,24 @@ int x2v_vae_prep_f32(const float* x, float* y, int T, int Hh, int Ww, int C, con
  * AttentionBlock (vae.py:249-253).  N % 4 == 0. */
 int x2v_softmax_rows_f32(float* s, int64_t ld, int64_t M, int N, float scale, void* stream);
 
+/* ---- Wan VAE encoder (models/video_encoders/hf/wan/vae.py Encoder3d :265-374, WanVAE_.encode :684-711) ------------------------
+ * The encoder's other convolutions run on the decoder's entries above; see lightx2v_amd/csrc/vae_enc.hip. */
+
+/* 3x3 stride-2 convolution of Resample downsample2d / downsample3d (vae.py:96-100: nn.ZeroPad2d((0, 1, 0, 1)) + nn.Conv2d(dim, dim, 3, stride=(2, 2))):
+ *   y[t,h,w,co] = bias[co] + sum_{dh,dw,c} xp[t*fs + (2h+dh)*rs + (2w+dw)*ps + c] * w[co*wrs + (dh*3+dw)*Cin + c],  h < Hin/2, w < Win/2,
+ * where input rows >= Hin and columns >= Win read as zero (the bottom / right pad; xp needs no border).  fp16 operands (strides in halves), fp32
+ * accumulate on v_mfma_f32_16x16x32_f16, fp32 bias / output y [T][Hin/2][Win/2][Cout].  With the hi/lo split operands of x2v_vae_prep_split_f16
+ * (activations [hi | hi * 2^-12 | lo], weights [hi | lo * 2^12 | hi], Cin = 3 * C rounded up to 32) the result is fp32-grade.
+ * Cin % 32 == 0, Cout % 4 == 0, Hin, Win >= 2, strides % 8 == 0, flags = 0. */
+int x2v_vae_conv_s2_f16(const void* xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride, const void* w, int64_t w_row_stride, const float* bias,
+                        float* y, int T, int Hin, int Win, int Cin, int Cout, int flags, void* stream);
+
+/* Producer of Encoder3d.conv1's operand buffer (vae.py:286) from the caller's video, read in place: video[c*c_stride + t*t_stride + h*row_stride + w]
+ * (c < 3, w contiguous) -> y + t*y_frame_stride + h*y_row_stride + w*y_px_stride, channels-last: mode 0 = 3 fp32, 1 = 3 fp16, 2 = the hi/lo split
+ * [hi(3) | hi * 2^-12 (3) | lo(3)] of x2v_vae_prep_split_f16 (9 halves).  Channels behind those are not written (pad channels stay zero). */
+int x2v_vae_video_prep(const float* video, int64_t c_stride, int64_t t_stride, int64_t row_stride, int T, int H, int W, void* y, int64_t y_frame_stride,
+                       int64_t y_row_stride, int64_t y_px_stride, int mode, void* stream);
+
 /* ---- HunyuanVideo VAE decode (video_encoders/hf/autoencoder_kl_causal_3d/), fp32, channels-last ------------------- */
 
 /* Pixel-wise producer: v = x*mul[c] + add[c] (mul/add optional; GroupNorm applied as a per-channel affine), optional SiLU

@@ -78,6 +78,8 @@ PROTOTYPES = {
     "x2v_vae_prep_split_f16": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i64, _i64, _i64, _c_void_p],
     "x2v_vae_prep_ex_f16": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i64, _i64, _c_void_p],
     "x2v_vae_prep_ex_f32": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i64, _i64, _c_void_p],
+    "x2v_vae_conv_s2_f16": [_c_void_p, _i64, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
+    "x2v_vae_video_prep": [_c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_vae_replicate_border_f32": [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
@@ -845,6 +847,45 @@ def vae_prep_ex(x, y_view, y_strides, mul=None, add=None, silu=False, clamp01=Fa
         return
     _check(_lib.x2v_vae_prep_ex_f32(_p(x), _p(y_view), T, H, W, C, _p(mul), _p(add), int(silu), int(clamp01), int(up_hw), int(up_t), y_strides[0], y_strides[1], _stream()),
            "vae_prep_ex")
+
+
+def vae_conv_s2(x, weight, out, bias=None):
+    """x2v_vae_conv_s2_f16: 3x3 stride-2 convolution with the bottom / right zero pad of Resample downsample2d / 3d.  x: fp16 view [T, Hin, Win, >= Cin]
+    (pixel stride from the view, the pixel axis may be padded); weight: contiguous fp16 [Cout, 3, 3, Cin] (or [Cout, 1, 3, 3, Cin]); out: fp32 [T, Hin // 2, Win // 2, Cout]."""
+    if x.dtype != torch.float16 or weight.dtype != torch.float16 or not x.is_cuda or not weight.is_cuda or not weight.is_contiguous():
+        raise X2VError("vae_conv_s2: operand and weight must be CUDA float16 (weight contiguous)")
+    if x.dim() != 4 or x.stride(3) != 1:
+        raise X2VError("vae_conv_s2: x must be a [T, H, W, C] view with unit channel stride")
+    _f32dense(out, "vae_conv_s2 out", 4), _f32dense(bias, "vae_conv_s2 bias")
+    cout, cin = weight.shape[0], weight.shape[-1]
+    T, H, W, _ = x.shape
+    if tuple(out.shape) != (T, H // 2, W // 2, cout) or weight.numel() != cout * 9 * cin:
+        raise X2VError(f"vae_conv_s2: out {tuple(out.shape)} / weight {tuple(weight.shape)} do not match x {tuple(x.shape)}")
+    init()
+    _check(_lib.x2v_vae_conv_s2_f16(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(weight), weight.stride(0), _p(bias), _p(out), T, H, W, cin, cout, 0, _stream()),
+           "vae_conv_s2")
+    return out
+
+
+VIDEO_PREP_MODES = {torch.float32: 0, torch.float16: 1, "split": 2}
+
+
+def vae_video_prep(video, y_view, split=False):
+    """x2v_vae_video_prep: video [3, T, H, W] fp32 (a view with unit W stride: read in place) -> y_view [T, H, W, >= 3 (9 split)] channels-last fp32 /
+    fp16 / hi-lo split fp16 (strides from the view)."""
+    _f32c(video, "vae_video_prep video")
+    if video.dim() != 4 or video.shape[0] != 3 or video.stride(3) != 1:
+        raise X2VError(f"vae_video_prep: expected a [3, T, H, W] video with unit W stride, got {tuple(video.shape)} strides {video.stride()}")
+    _dev_view(y_view, "vae_video_prep y", (torch.float32, torch.float16))
+    if split and y_view.dtype != torch.float16:
+        raise X2VError("vae_video_prep: split needs an fp16 destination")
+    if y_view.dim() != 4 or tuple(y_view.shape[:3]) != tuple(video.shape[1:]) or y_view.stride(3) != 1:
+        raise X2VError(f"vae_video_prep: destination {tuple(y_view.shape)} does not match video {tuple(video.shape)}")
+    _, T, H, W = video.shape
+    init()
+    mode = 2 if split else VIDEO_PREP_MODES[y_view.dtype]
+    _check(_lib.x2v_vae_video_prep(_p(video), video.stride(0), video.stride(1), video.stride(2), T, H, W, _p(y_view), y_view.stride(0), y_view.stride(1),
+                                   y_view.stride(2), mode, _stream()), "vae_video_prep")
 
 
 def vae_replicate_border_(buf, lead, pad):

@@ -220,6 +220,67 @@ def synth_wan_vae_weights(dim=96, z_dim=16, seed=0, device="cpu"):
     return sd
 
 
+def wan_vae_encoder_plan(dim=96, dim_mult=(1, 2, 4, 4), num_res_blocks=2, temperal_downsample=(False, True, True)):
+    """Encoder3d.__init__ (vae.py:265-320): channel plan and the `downsamples` Sequential as (index, kind, in_dim, out_dim)."""
+    dims = [dim * u for u in [1] + list(dim_mult)]
+    plan, idx = [], 0
+    for i, (in_dim, out_dim) in enumerate(zip(dims[:-1], dims[1:])):
+        for _ in range(num_res_blocks):
+            plan.append((idx, "res", in_dim, out_dim))
+            idx += 1
+            in_dim = out_dim
+        if i != len(dim_mult) - 1:
+            plan.append((idx, "downsample3d" if temperal_downsample[i] else "downsample2d", out_dim, out_dim))
+            idx += 1
+    return dims, plan
+
+
+def synth_wan_vae_encoder_weights(dim=96, z_dim=16, seed=0, device="cpu"):
+    """Seeded fp32 weights of the Wan VAE *encoder* under the reference's state-dict names (`encoder.*`, `conv1.*`; WanVAE_ / Encoder3d module tree,
+    vae.py:265-374,640-676, with z_dim * 2 = 32 head channels: mu and log_var).  A separate stream from synth_wan_vae_weights (whose outputs fixtures
+    pin): merge the two dicts for a full VAE.  Convs are scaled ~1/sqrt(fan_in) so activations stay O(1)."""
+    gen = torch.Generator().manual_seed(seed + 1000)
+    sd = {}
+
+    def conv(name, cout, cin, *k, gain=1.0):
+        fan = cin
+        for kk in k:
+            fan *= kk
+        sd[f"{name}.weight"] = (torch.randn((cout, cin, *k), generator=gen) * (gain / math.sqrt(fan))).to(device)
+        sd[f"{name}.bias"] = (torch.randn((cout,), generator=gen) * 0.05).to(device)
+
+    def gamma(name, c, *ones):
+        sd[name] = (1.0 + 0.1 * torch.randn((c, *ones), generator=gen)).to(device)
+
+    def res(p, cin, cout):
+        gamma(p + "residual.0.gamma", cin, 1, 1, 1)
+        conv(p + "residual.2", cout, cin, 3, 3, 3, gain=1.4)
+        gamma(p + "residual.3.gamma", cout, 1, 1, 1)
+        conv(p + "residual.6", cout, cout, 3, 3, 3, gain=1.4)
+        if cin != cout:
+            conv(p + "shortcut", cout, cin, 1, 1, 1)
+
+    dims, plan = wan_vae_encoder_plan(dim)
+    conv("encoder.conv1", dims[0], 3, 3, 3, 3)
+    for idx, kind, cin, cout in plan:
+        p = f"encoder.downsamples.{idx}."
+        if kind == "res":
+            res(p, cin, cout)
+        else:
+            conv(p + "resample.1", cout, cin, 3, 3, gain=1.4)
+            if kind == "downsample3d":
+                conv(p + "time_conv", cout, cin, 3, 1, 1)
+    res("encoder.middle.0.", dims[-1], dims[-1])
+    gamma("encoder.middle.1.norm.gamma", dims[-1], 1, 1)
+    conv("encoder.middle.1.to_qkv", dims[-1] * 3, dims[-1], 1, 1)
+    conv("encoder.middle.1.proj", dims[-1], dims[-1], 1, 1)
+    res("encoder.middle.2.", dims[-1], dims[-1])
+    gamma("encoder.head.0.gamma", dims[-1], 1, 1, 1)
+    conv("encoder.head.2", 2 * z_dim, dims[-1], 3, 3, 3)
+    conv("conv1", 2 * z_dim, 2 * z_dim, 1, 1, 1)
+    return sd
+
+
 # HunyuanVideo DiT (reference: hunyuan/infer/transformer_infer.py:13-17 hard-codes the 13B numbers)
 HUNYUAN_DIMS = {
     "hunyuan-13b": dict(hidden=3072, heads=24, mlp=12288, double_blocks=20, single_blocks=40, text_dim=4096, text_dim_2=768, text_len=256, refiner_mlp=12288),

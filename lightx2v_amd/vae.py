@@ -85,20 +85,37 @@ def _cl(weight):
     return weight.permute(0, 2, 3, 4, 1).contiguous()
 
 
+def _split16(v, cp, split):
+    """fp32 weight [..., C] → fp16 [..., cp]: hi, or [hi | lo * 2^12 | hi] (split: against activations [hi | hi * 2^-12 | lo] the scaled lo halves are
+    normal fp16 numbers), zero channels behind."""
+    c = v.shape[-1]
+    w16 = torch.zeros((*v.shape[:-1], cp), dtype=torch.float16, device=v.device)
+    hi = v.to(torch.float16)
+    w16[..., :c] = hi
+    if split:
+        w16[..., c : 2 * c] = ((v - hi.float()) * 4096.0).to(torch.float16)
+        w16[..., 2 * c : 3 * c] = hi
+    return w16
+
+
 class Decoder3d:
     """reference: vae.py:377-489."""
 
     def __init__(self, sd, dim, latent_hw, device, conv16=False):
+        self._setup(sd, "decoder.", latent_hw, device, conv16)
+        self.dims, self.plan = synth.wan_vae_decoder_plan(dim)
+
+    def _setup(self, sd, prefix, hw, device, conv16):
+        """Weights under `prefix` in the kernels' layouts, buffer pools and cache state — shared with the encoder (vae_enc.Encoder3d)."""
         self.device = device
         # conv16: False = fp32 convolutions on the fp32 matrix instruction (the reference's precision); True = fp16 operands (opt-in fast
         # decode, 11 mantissa bits); "split" = hi/lo fp16 split of activations and weights, three 16-bit products per fp32 product
         # accumulated in fp32 (~22 mantissa bits per operand: fp32-grade results at 16-bit matrix speed)
         self.conv16 = conv16
         self.split = conv16 == "split"
-        self.dims, self.plan = synth.wan_vae_decoder_plan(dim)
         self.w = {}
         for k, v in sd.items():
-            if not k.startswith("decoder."):
+            if not k.startswith(prefix):
                 continue
             v = v.to(device=device, dtype=torch.float32)
             self.w[k] = _cl(v) if (k.endswith(".weight") and v.dim() >= 4) else v.reshape(-1).contiguous()
@@ -109,15 +126,9 @@ class Decoder3d:
                 if k.endswith(".weight") and v.dim() == 5 and v.shape[1] * v.shape[2] * v.shape[3] > 1 and v.shape[4] >= 32:
                     cin = v.shape[4]
                     cp = ((3 * cin if self.split else cin) + 63) // 64 * 64
-                    w16 = torch.zeros((*v.shape[:4], cp), dtype=torch.float16, device=device)
-                    hi = v.to(torch.float16)
-                    w16[..., :cin] = hi
-                    if self.split:  # [hi | lo * 2^12 | hi] against activations [hi | hi * 2^-12 | lo]: the scaled lo halves are normal fp16 numbers
-                        w16[..., cin : 2 * cin] = ((v - hi.float()) * 4096.0).to(torch.float16)
-                        w16[..., 2 * cin : 3 * cin] = hi
-                    self.w16[k] = w16
+                    self.w16[k] = _split16(v, cp, self.split)
                     self.w16_tail[k] = cp - (3 * cin if self.split else cin)  # zero channels behind the planes (weights and activations alike)
-        self.h0, self.w0 = latent_hw
+        self.h0, self.w0 = hw
         self._bufs = {}
         self._pool = {}  # shared frame buffers by geometry (see _ConvInput)
         self._rep = {}  # upsample3d time-conv state: False until the first chunk has passed (the reference's "Rep", vae.py:113-115)
@@ -232,25 +243,38 @@ def chunk_bounds(t, chunk_frames):
 
 
 class WanVAE_:
-    """reference: vae.py:640-760 (decode side)."""
+    """reference: vae.py:640-760 (decode; encode in vae_enc.py)."""
 
-    def __init__(self, sd, dim=96, z_dim=16, device="cuda", conv16="split", chunk_frames=4):
+    def __init__(self, sd, dim=96, z_dim=16, device="cuda", conv16="split", chunk_frames=4, encode_chunk_frames=4):
         """chunk_frames: latent frames per pass through the decoder after the first one (default 4: 88 GB of buffers at 720p, 2.8 % faster than 2 at 56 GB —
         fewer cache moves and tile tails; profiles/r06_call10_*).  The reference pushes ONE latent frame at a time
         through its cache-carrying decoder (vae.py:722-736) to bound memory; every kernel here reduces each output pixel in an order that
         does not depend on how many frames share the launch, and the 2-frame caches are the leading frames of the conv input buffers, so
         any chunking gives bit-identical output — larger chunks only fill the GPU better in the low-resolution stages
-        (90x160 latents: 57 workgroups per frame and 32 output channels) and launch 4x fewer kernels."""
+        (90x160 latents: 57 workgroups per frame and 32 output channels) and launch 4x fewer kernels.
+        encode_chunk_frames: video frames per encoder pass after the first one (a multiple of 4; the reference's 4, vae.py:687-705) — likewise
+        bit-identical for every value.  The encoder is built on the first encode() from the `encoder.*` / `conv1.*` tensors."""
         self.dim, self.z_dim, self.device, self.conv16 = dim, z_dim, device, conv16
         self.chunk_frames = max(1, int(chunk_frames))
         self.sd = sd
-        self.conv2_w = sd["conv2.weight"].to(device=device, dtype=torch.float32).reshape(z_dim, z_dim).contiguous()
-        self.conv2_b = sd["conv2.bias"].to(device=device, dtype=torch.float32).contiguous()
+        self.encode_chunk_frames = int(encode_chunk_frames)
+        has_dec = "conv2.weight" in sd  # an encoder-only state dict (encoder.* / conv1.*) can encode, not decode
+        self.conv2_w = sd["conv2.weight"].to(device=device, dtype=torch.float32).reshape(z_dim, z_dim).contiguous() if has_dec else None
+        self.conv2_b = sd["conv2.bias"].to(device=device, dtype=torch.float32).contiguous() if has_dec else None
         self.decoder = None
+        self.encoder = None
+
+    def encode(self, x, scale, chunk_frames=None):
+        """x [1, 3, T, H, W] (T = 1 + 4k); scale = [mean, inv_std] → mu [1, z_dim, 1 + k, H / 8, W / 8] fp32, (mu - mean) * inv_std (vae.py:684-711)."""
+        from . import vae_enc
+
+        return vae_enc.encode(self, x, scale, chunk_frames)
 
     def decode(self, z, scale):
         """z [1, 16, T, h, w] fp32; scale = [mean, inv_std] → [1, 3, 1 + 4 (T-1), 8h, 8w], clamped to [-1, 1]."""
         zc, t, h, w = z.shape[1:]
+        if self.conv2_w is None:
+            raise lib.X2VError("decode: the state dict holds no decoder (conv2.* / decoder.* tensors)")
         if self.decoder is None or (self.decoder.h0, self.decoder.w0) != (h, w):
             self.decoder = Decoder3d(self.sd, self.dim, (h, w), self.device, conv16=self.conv16)
         self.decoder.clear_cache()
@@ -266,9 +290,9 @@ class WanVAE_:
 
 
 class WanVAE:
-    """reference: vae.py:789-957 (decode side; `use_tiling` is not built)."""
+    """reference: vae.py:789-957 (`use_tiling` is not built)."""
 
-    def __init__(self, sd, z_dim=16, dim=96, device="cuda", parallel=False, conv16="split", chunk_frames=4):
+    def __init__(self, sd, z_dim=16, dim=96, device="cuda", parallel=False, conv16="split", chunk_frames=4, encode_chunk_frames=4, use_tiling=False):
         """conv16 selects how the 3x3(x3) convolutions multiply (accumulation, residual stream, norms and attention are fp32 in every mode):
           "split" (default)  activations and weights as hi + lo fp16 pairs (~22 mantissa bits), three 16-bit products per fp32 product:
                              fp32-grade — it meets the all-fp32 decode's tolerance against the reference's fp32 decode (vae.py:794) — at
@@ -279,7 +303,15 @@ class WanVAE:
         self.mean = torch.tensor(synth.WAN_VAE_MEAN, dtype=torch.float32, device=device)
         self.inv_std = 1.0 / torch.tensor(synth.WAN_VAE_STD, dtype=torch.float32, device=device)
         self.scale = [self.mean, self.inv_std]
-        self.model = WanVAE_(sd, dim=dim, z_dim=z_dim, device=device, conv16=conv16, chunk_frames=chunk_frames)
+        self.use_tiling = use_tiling
+        self.model = WanVAE_(sd, dim=dim, z_dim=z_dim, device=device, conv16=conv16, chunk_frames=chunk_frames, encode_chunk_frames=encode_chunk_frames)
+
+    def encode(self, videos, args=None):
+        """videos: list of [3, T, H, W] in [-1, 1] → list of latents [z_dim, 1 + (T - 1) / 4, H / 8, W / 8] fp32 (vae.py:867-881; `args` is accepted for the
+        reference's signature — its cpu_offload has no counterpart here)."""
+        if self.use_tiling:
+            raise lib.X2VError("WanVAE.encode: use_tiling (tiled_encode, vae.py:568) is not built")
+        return [self.model.encode(u.unsqueeze(0).to(self.device), self.scale).float().squeeze(0) for u in videos]
 
     def decode_dist(self, zs, world_size, cur_rank, split_dim):
         """reference: vae.py:883-929 — each rank decodes its slab of the latent (split along H = dim 2 or W = dim 3) plus a
@@ -312,6 +344,8 @@ class WanVAE:
     def decode(self, zs, generator=None, config=None):
         """zs [16, T, h, w] → images [1, 3, T_out, 8h, 8w] fp32 in [-1, 1] (vae.py:931-957; `parallel` = the decode_dist
         branch when H or W divides by the world size, else the plain decode like the reference's fallback)."""
+        if self.use_tiling:
+            raise lib.X2VError("WanVAE.decode: use_tiling (tiled_decode, vae.py:631) is not built")
         if self.parallel:
             import torch.distributed as dist
 
