@@ -387,16 +387,17 @@ int x2v_vae_prep_ex_f32(const float* x, float* y, int T, int Hh, int Ww, int C, 
 /* 16-bit-operand form of x2v_vae_conv_f32 for the HunyuanVideo VAE, which the reference runs in fp16 (hunyuan_runner.py:40): xp and w
  * are fp16 (strides in halves, Cin % 64 == 0), accumulation fp32 on v_mfma_f32_32x32x16_f16, bias / residual / output fp32 — the residual
  * stream and the normalisation statistics keep fp32, only the convolution operands are rounded.  Same flags and layouts as the fp32 entry, plus
- * 4 = the per-tap kernel and 8 = the 64-pixel halo kernel (kernel choice for A/B runs and tests: by default 3x3 kernels with Cout % 96 == 0 take the
- * 128-pixel x 96-cout kernel on v_mfma_f32_16x16x32_f16, whose reduction order differs in rounding) and 16 = the last 32 channels of Cin are zero
- * padding in both operands (skipped where the kernel steps in 32 channels; a no-op for the results). */
+ * 4 = the per-tap kernel and 8 = the 64-pixel halo kernel (kernel choice for A/B runs and tests: by default 3x3 kernels on images at least 16 pixels wide
+ * with Cin % 32 == 0 and Cout % 96 == 0, Cout % 128 == 0 or Cout <= 16 take the 128-pixel kernel on v_mfma_f32_16x16x32_f16, whose reduction order differs in
+ * rounding; other 3x3 kernels at least 16 pixels wide the 64-pixel halo kernel; everything else the per-tap kernel) and 16 = the last 32 channels of Cin
+ * are zero padding in both operands (skipped where the kernel steps in 32 channels; a no-op for the results). */
 int x2v_vae_conv_f16(const void* xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride, const void* w, int64_t w_row_stride, const float* bias,
                      const float* resid, float* y, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags, void* stream);
 
 /* x2v_vae_conv_f16 with the causal convolution's feature cache (the reference's feat_cache entry, vae.py:16,199-214: the last kt - 1 input frames of the
  * previous chunk) in a buffer of its own: input frames 0 .. kt-2 are read from `cache` ([kt-1][H+2][W+2][Cin], xp's strides), the rest from xp, whose own
  * leading kt - 1 frames are not read — a frame buffer shared by several convolutions then needs no copy of the cache in front of it.  Only where
- * x2v_vae_conv_f16_cached_ok(...) == 1 (3x3 kernels with Cout % 96 == 0, Cout % 128 == 0 or Cout <= 16: the 128-pixel kernel); bit-identical to x2v_vae_conv_f16 on a buffer
+ * x2v_vae_conv_f16_cached_ok(...) == 1 (the shapes that take the 128-pixel kernel, see x2v_vae_conv_f16, without the time-split and kernel-choice flags); bit-identical to x2v_vae_conv_f16 on a buffer
  * that carries the same frames. */
 int x2v_vae_conv_f16_cached(const void* xp, const void* cache, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride, const void* w, int64_t w_row_stride,
                             const float* bias, const float* resid, float* y, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags, void* stream);

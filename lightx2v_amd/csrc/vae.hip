@@ -23,30 +23,75 @@
 // K step carries 32*NF fp32 MFMAs of 64 cycles per wave, which hides the next slab's DMA behind one barrier.
 // Bound: MFMA fp32 (157 TFLOP/s); algorithmic work 2 * T*H*W * Cout * Cin * taps FLOP per launch.
 #include <algorithm>
+#include <type_traits>
 
 #include "x2v_common.h"
 
 namespace x2v {
 
 typedef __attribute__((address_space(3))) void* v_lds_ptr_t;
+typedef _Float16 vc_half8_t __attribute__((ext_vector_type(8)));
 
 constexpr int VC_PIX = 256;
 constexpr unsigned VC_OOB = 0x80000000u;  // voffset of a masked row: beyond any descriptor range we build (< 2 GiB)
 
-// flags of x2v_vae_conv_f32
+// flags of x2v_vae_conv_f32 / x2v_vae_conv_f16
 constexpr int VCF_CLAMP = 1;   // clamp the result to [-1, 1] (WanVAE.decode, vae.py:951-955)
 constexpr int VCF_TSPLIT = 2;  // Cout = 2C: channel block j of frame t -> frame 2t + j (Resample upsample3d, vae.py:136-138)
 
-template <int NF, int KC>
-__global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restrict__ xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride,
-                                                       const float* __restrict__ w, int64_t w_row_stride, const float* __restrict__ bias,
+// Epilogue of every convolution kernel in this file, for one group of 4 consecutive couts of one pixel: a[4g .. 4g+3] are couts co .. co+3, y[oidx] is
+// cout co's output element; y = clamp(acc + bias + resid).  16-byte accesses where Cout % 4 == 0 (vec_ok), else element-wise and bounded by Cout.
+__device__ __forceinline__ void vconv_epilogue4(const f32x16_t& a, int g, int co, int64_t oidx, const float* __restrict__ bias, const float* __restrict__ resid,
+                                                float* __restrict__ y, int Cout, int flags, bool vec_ok) {
+  float vv[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) vv[e] = a[4 * g + e];
+  if (vec_ok) {
+    if (bias != nullptr) {
+      const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
+      vv[0] += b4.x; vv[1] += b4.y; vv[2] += b4.z; vv[3] += b4.w;
+    }
+    if (resid != nullptr) {
+      const float4 r4 = *reinterpret_cast<const float4*>(resid + oidx);
+      vv[0] += r4.x; vv[1] += r4.y; vv[2] += r4.z; vv[3] += r4.w;
+    }
+    if (flags & VCF_CLAMP) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) vv[e] = fminf(fmaxf(vv[e], -1.f), 1.f);
+    }
+    *reinterpret_cast<float4*>(y + oidx) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (co + e < Cout) {
+        float o = vv[e] + (bias != nullptr ? bias[co + e] : 0.f) + (resid != nullptr ? resid[oidx + e] : 0.f);
+        if (flags & VCF_CLAMP) o = fminf(fmaxf(o, -1.f), 1.f);
+        y[oidx + e] = o;
+      }
+  }
+}
+
+// The per-tap kernel described above, for both operand types.  OP = float: the fp32 decode, KC = 16 or 32 channels per K step.  OP = _Float16: activations
+// and weights in fp16 (the precision the reference runs the HunyuanVideo VAE in, hunyuan_runner.py:40), fp32 accumulate on v_mfma_f32_32x32x16_f16, fp32
+// bias / residual / output — the residual stream and the GroupNorm statistics stay fp32, only the operands of the big convolutions are rounded; KC = 64
+// (128-byte rows) = 4 k-steps of 16: 8 NF MFMAs of 32 cycles per wave and step against 12 + NF LDS-DMA pieces per workgroup — MFMA-bound no longer, the
+// staging path sets the pace (measured in DESIGN.md §4.4).  Tile, staging, swizzle and epilogue are common: every size below derives from sizeof(OP) and
+// KC, and only the fragment type and the MFMA depend on the type (fp32: one ds_read_b128 feeds 4 MFMAs of k = 2; fp16: one MFMA of k = 16).
+template <typename OP, int NF, int KC>
+__global__ __launch_bounds__(256, 2) void vae_conv_kernel(const OP* __restrict__ xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride,
+                                                       const OP* __restrict__ w, int64_t w_row_stride, const float* __restrict__ bias,
                                                        const float* __restrict__ resid, float* __restrict__ y, int T, int Hh, int Ww, int Cin, int Cout,
                                                        int kt, int kh, int kw, int flags, int ncol) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ROWB = KC * 4;                   // bytes per staged row
-  constexpr int CPR = KC / 4;                    // 16-byte chunks per row
+  constexpr bool F16 = sizeof(OP) == 2;
+  using frag_t = std::conditional_t<F16, vc_half8_t, f32x4_t>;  // what one ds_read_b128 delivers
+  constexpr int ES = sizeof(OP);                 // bytes per operand element
+  constexpr int ROWB = KC * ES;                  // bytes per staged row
+  constexpr int CPR = ROWB / 16;                 // 16-byte chunks per row
   constexpr int RPI = 64 / CPR;                  // rows per wave-instruction
+  constexpr int NRD = CPR / 2;                   // fragment reads per row and K step (a lane half reads every second chunk)
+  constexpr int MPR = F16 ? 1 : 4;               // MFMAs fed by one fragment read
   constexpr int BN = 32 * NF;
   constexpr int A_BYTES = VC_PIX * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
   constexpr int A_INSTR = 64 / RPI;              // DMA instructions per wave for its 64 A rows
@@ -64,14 +109,14 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
   const int taps = kt * kh * kw;
 
   // descriptors: input = kt frames starting at this output frame; weights = rows co0 .. Cout
-  const int64_t fbytes = x_frame_stride * 4;
+  const int64_t fbytes = x_frame_stride * ES;
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(xp + (int64_t)frame * x_frame_stride), 0, (unsigned)(fbytes * kt), 0x00020000);
   const int wrows = min(BN, Cout - co0);
   const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(w + (int64_t)co0 * w_row_stride), 0, (unsigned)(((int64_t)(wrows - 1) * w_row_stride + (int64_t)taps * Cin) * 4), 0x00020000);
+      (void*)(w + (int64_t)co0 * w_row_stride), 0, (unsigned)(((int64_t)(wrows - 1) * w_row_stride + (int64_t)taps * Cin) * ES), 0x00020000);
 
   // per-lane DMA source offsets (bytes): A rows = this wave's 64 pixels, B rows = this wave's quarter of the couts
-  constexpr int swz_shift = (KC == 32) ? 1 : 2;  // rows sharing one 256-byte bank row
+  constexpr int swz_shift = ROWB == 128 ? 1 : 2;  // rows sharing one 256-byte bank row
   unsigned a_voff[A_INSTR], b_voff[B_INSTR];
 #pragma unroll
   for (int i = 0; i < A_INSTR; ++i) {
@@ -79,22 +124,22 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
     const int c = (lane % CPR) ^ ((r >> swz_shift) & (CPR - 1));
     const int p = p0 + r;
     const int ph = p / Ww, pw = p - ph * Ww;
-    a_voff[i] = p < HW ? (unsigned)(((int64_t)ph * x_row_stride + (int64_t)pw * x_px_stride) * 4) + (unsigned)(c << 4) : VC_OOB;
+    a_voff[i] = p < HW ? (unsigned)(((int64_t)ph * x_row_stride + (int64_t)pw * x_px_stride) * ES) + (unsigned)(c << 4) : VC_OOB;
   }
 #pragma unroll
   for (int i = 0; i < B_INSTR; ++i) {
     const int rl = i * RPI + lane / CPR;            // row within this wave's share
     const int r = wid * (BN / 4) + rl;
     const int c = (lane % CPR) ^ ((r >> swz_shift) & (CPR - 1));
-    b_voff[i] = (rl < BN / 4 && r < wrows) ? (unsigned)((int64_t)r * w_row_stride * 4) + (unsigned)(c << 4) : VC_OOB;
+    b_voff[i] = (rl < BN / 4 && r < wrows) ? (unsigned)((int64_t)r * w_row_stride * ES) + (unsigned)(c << 4) : VC_OOB;
   }
   const int kchunks = Cin / KC;
   const int nsteps = taps * kchunks;
   auto stage = [&](int s, int step) {
     const int tap = step / kchunks, kc = step - tap * kchunks;
     const int dt = tap / (kh * kw), dh = (tap / kw) % kh, dw = tap % kw;
-    const unsigned xso = (unsigned)(((int64_t)dt * x_frame_stride + (int64_t)dh * x_row_stride + (int64_t)dw * x_px_stride + (int64_t)kc * KC) * 4);
-    const unsigned wso = (unsigned)(((int64_t)tap * Cin + (int64_t)kc * KC) * 4);
+    const unsigned xso = (unsigned)(((int64_t)dt * x_frame_stride + (int64_t)dh * x_row_stride + (int64_t)dw * x_px_stride + (int64_t)kc * KC) * ES);
+    const unsigned wso = (unsigned)(((int64_t)tap * Cin + (int64_t)kc * KC) * ES);
     char* as = smem + s * STAGE + wid * (64 * ROWB);
     char* bs = smem + s * STAGE + A_BYTES + wid * ((BN / 4) * ROWB);
 #pragma unroll
@@ -105,10 +150,10 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rwt, (v_lds_ptr_t)(bs + i * 1024), 16, b_voff[i], wso, 0, 0);
   };
 
-  // fragment read offsets: row (32-row block + fl), chunk (j*2 + fh) ^ swizzle
-  int rd[KC / 8];
+  // fragment read offsets: row (32-row block + fl), read j takes chunk (j*2 + fh) ^ swizzle (fp32: k = 8j + 4fh + e for MFMA e; fp16: the 8 k values of k-step j)
+  int rd[NRD];
 #pragma unroll
-  for (int j = 0; j < KC / 8; ++j) rd[j] = fl * ROWB + ((((j << 1) | fh) ^ ((fl >> swz_shift) & (CPR - 1))) << 4);
+  for (int j = 0; j < NRD; ++j) rd[j] = fl * ROWB + ((((j << 1) | fh) ^ ((fl >> swz_shift) & (CPR - 1))) << 4);
 
   f32x16_t acc[2][NF];
 #pragma unroll
@@ -127,18 +172,21 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
     const char* ab = smem + cur * STAGE + wid * (64 * ROWB);
     const char* bb = smem + cur * STAGE + A_BYTES;
 #pragma unroll
-    for (int j = 0; j < KC / 8; ++j) {
-      f32x4_t xa[2], wb[NF];
+    for (int j = 0; j < NRD; ++j) {
+      frag_t xa[2], wb[NF];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) xa[i] = *reinterpret_cast<const f32x4_t*>(ab + i * 32 * ROWB + rd[j]);
+      for (int i = 0; i < 2; ++i) xa[i] = *reinterpret_cast<const frag_t*>(ab + i * 32 * ROWB + rd[j]);
 #pragma unroll
-      for (int n = 0; n < NF; ++n) wb[n] = *reinterpret_cast<const f32x4_t*>(bb + n * 32 * ROWB + rd[j]);
+      for (int n = 0; n < NF; ++n) wb[n] = *reinterpret_cast<const frag_t*>(bb + n * 32 * ROWB + rd[j]);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
+      for (int e = 0; e < MPR; ++e)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int n = 0; n < NF; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[n][e], xa[i][e], acc[i][n], 0, 0, 0);
+          for (int n = 0; n < NF; ++n) {
+            if constexpr (F16) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[n], xa[i], acc[i][n], 0, 0, 0);
+            else acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[n][e], xa[i][e], acc[i][n], 0, 0, 0);
+          }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -157,9 +205,6 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
       for (int g = 0; g < 4; ++g) {
         const int co = co0 + n * 32 + 8 * g + 4 * fh;
         if (co >= Cout) continue;
-        float vv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = acc[i][n][4 * g + e];
         int64_t oidx;
         if (flags & VCF_TSPLIT) {
           const int hi = co >= csplit ? 1 : 0;
@@ -167,190 +212,7 @@ __global__ __launch_bounds__(256, 2) void vae_conv_kernel(const float* __restric
         } else {
           oidx = ((int64_t)frame * HW + p) * Cout + co;
         }
-        if (vec_ok) {
-          if (bias != nullptr) {
-            const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
-            vv[0] += b4.x; vv[1] += b4.y; vv[2] += b4.z; vv[3] += b4.w;
-          }
-          if (resid != nullptr) {
-            const float4 r4 = *reinterpret_cast<const float4*>(resid + oidx);
-            vv[0] += r4.x; vv[1] += r4.y; vv[2] += r4.z; vv[3] += r4.w;
-          }
-          if (flags & VCF_CLAMP) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vv[e] = fminf(fmaxf(vv[e], -1.f), 1.f);
-          }
-          *reinterpret_cast<float4*>(y + oidx) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (co + e < Cout) {
-              float o = vv[e] + (bias != nullptr ? bias[co + e] : 0.f) + (resid != nullptr ? resid[oidx + e] : 0.f);
-              if (flags & VCF_CLAMP) o = fminf(fmaxf(o, -1.f), 1.f);
-              y[oidx + e] = o;
-            }
-        }
-      }
-  }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// 16-bit-input variant of the implicit-GEMM convolution: activations and weights in fp16 (the precision the reference runs the
-// HunyuanVideo VAE in, hunyuan_runner.py:40), fp32 accumulate on v_mfma_f32_32x32x16_f16, fp32 bias / residual / output — the residual
-// stream and the GroupNorm statistics stay fp32, only the operands of the big convolutions are rounded.  Same tile (256 pixels x 32 NF
-// couts per workgroup, wave = 64 px), same LDS-DMA staging and swizzle as the fp32 kernel; a K step is one tap x 64 channels
-// (128-byte rows) = 4 k-steps of 16: 8 NF MFMAs of 32 cycles per wave and step against 12 + NF LDS-DMA pieces per workgroup —
-// MFMA-bound no longer, the staging path sets the pace (measured in DESIGN.md §4.4).
-typedef _Float16 vc_half8_t __attribute__((ext_vector_type(8)));
-
-template <int NF>
-__global__ __launch_bounds__(256, 2) void vae_conv16_kernel(const _Float16* __restrict__ xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride,
-                                                         const _Float16* __restrict__ w, int64_t w_row_stride, const float* __restrict__ bias,
-                                                         const float* __restrict__ resid, float* __restrict__ y, int T, int Hh, int Ww, int Cin, int Cout,
-                                                         int kt, int kh, int kw, int flags, int ncol) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KC = 64;                         // channels per K step
-  constexpr int ROWB = KC * 2;                   // bytes per staged row
-  constexpr int CPR = 8, RPI = 8;                // 16-byte chunks per row, rows per wave-instruction
-  constexpr int BN = 32 * NF;
-  constexpr int A_BYTES = VC_PIX * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
-  constexpr int A_INSTR = 64 / RPI;
-  constexpr int B_INSTR = (BN / 4 + RPI - 1) / RPI;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fl = lane & 31, fh = lane >> 5;
-  const int HW = Hh * Ww;
-  const int tiles_per_frame = (HW + VC_PIX - 1) / VC_PIX;
-  const unsigned v = xcd_remap(blockIdx.x, gridDim.x);
-  const int ptile = (int)(v / (unsigned)ncol), ctile = (int)(v % (unsigned)ncol);
-  const int frame = ptile / tiles_per_frame;
-  const int p0 = (ptile % tiles_per_frame) * VC_PIX;
-  const int co0 = ctile * BN;
-  const int taps = kt * kh * kw;
-
-  const int64_t fbytes = x_frame_stride * 2;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(xp + (int64_t)frame * x_frame_stride), 0, (unsigned)(fbytes * kt), 0x00020000);
-  const int wrows = min(BN, Cout - co0);
-  const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(w + (int64_t)co0 * w_row_stride), 0, (unsigned)(((int64_t)(wrows - 1) * w_row_stride + (int64_t)taps * Cin) * 2), 0x00020000);
-
-  unsigned a_voff[A_INSTR], b_voff[B_INSTR];
-#pragma unroll
-  for (int i = 0; i < A_INSTR; ++i) {
-    const int r = wid * 64 + i * RPI + lane / CPR;
-    const int c = (lane % CPR) ^ ((r >> 1) & (CPR - 1));
-    const int p = p0 + r;
-    const int ph = p / Ww, pw = p - ph * Ww;
-    a_voff[i] = p < HW ? (unsigned)(((int64_t)ph * x_row_stride + (int64_t)pw * x_px_stride) * 2) + (unsigned)(c << 4) : VC_OOB;
-  }
-#pragma unroll
-  for (int i = 0; i < B_INSTR; ++i) {
-    const int rl = i * RPI + lane / CPR;
-    const int r = wid * (BN / 4) + rl;
-    const int c = (lane % CPR) ^ ((r >> 1) & (CPR - 1));
-    b_voff[i] = (rl < BN / 4 && r < wrows) ? (unsigned)((int64_t)r * w_row_stride * 2) + (unsigned)(c << 4) : VC_OOB;
-  }
-  const int kchunks = Cin / KC;
-  const int nsteps = taps * kchunks;
-  auto stage = [&](int s, int step) {
-    const int tap = step / kchunks, kc = step - tap * kchunks;
-    const int dt = tap / (kh * kw), dh = (tap / kw) % kh, dw = tap % kw;
-    const unsigned xso = (unsigned)(((int64_t)dt * x_frame_stride + (int64_t)dh * x_row_stride + (int64_t)dw * x_px_stride + (int64_t)kc * KC) * 2);
-    const unsigned wso = (unsigned)(((int64_t)tap * Cin + (int64_t)kc * KC) * 2);
-    char* as = smem + s * STAGE + wid * (64 * ROWB);
-    char* bs = smem + s * STAGE + A_BYTES + wid * ((BN / 4) * ROWB);
-#pragma unroll
-    for (int i = 0; i < A_INSTR; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (v_lds_ptr_t)(as + i * 1024), 16, a_voff[i], xso, 0, 0);
-#pragma unroll
-    for (int i = 0; i < B_INSTR; ++i)
-      if ((i + 1) * RPI <= BN / 4 || lane / CPR + i * RPI < BN / 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rwt, (v_lds_ptr_t)(bs + i * 1024), 16, b_voff[i], wso, 0, 0);
-  };
-
-  // fragment read offsets: row (32-row block + fl), k-step ks reads chunk (ks*2 + fh) ^ swizzle (8 halves = the lane's k values)
-  int rd[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) rd[ks] = fl * ROWB + ((((ks << 1) | fh) ^ ((fl >> 1) & (CPR - 1))) << 4);
-
-  f32x16_t acc[2][NF];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int step = 0; step < nsteps; ++step) {
-    const int cur = step & 1;
-    if (step + 1 < nsteps) stage(cur ^ 1, step + 1);
-    const char* ab = smem + cur * STAGE + wid * (64 * ROWB);
-    const char* bb = smem + cur * STAGE + A_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      vc_half8_t xa[2], wb[NF];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) xa[i] = *reinterpret_cast<const vc_half8_t*>(ab + i * 32 * ROWB + rd[ks]);
-#pragma unroll
-      for (int n = 0; n < NF; ++n) wb[n] = *reinterpret_cast<const vc_half8_t*>(bb + n * 32 * ROWB + rd[ks]);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[n], xa[i], acc[i][n], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // epilogue: identical to the fp32 kernel (fp32 bias / residual / output)
-  const bool vec_ok = (Cout & 3) == 0;
-  const int csplit = (flags & VCF_TSPLIT) ? Cout / 2 : Cout;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int p = p0 + wid * 64 + i * 32 + fl;
-    if (p >= HW) continue;
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int co = co0 + n * 32 + 8 * g + 4 * fh;
-        if (co >= Cout) continue;
-        float vv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = acc[i][n][4 * g + e];
-        int64_t oidx;
-        if (flags & VCF_TSPLIT) {
-          const int hi = co >= csplit ? 1 : 0;
-          oidx = ((int64_t)(2 * frame + hi) * HW + p) * csplit + (co - hi * csplit);
-        } else {
-          oidx = ((int64_t)frame * HW + p) * Cout + co;
-        }
-        if (vec_ok) {
-          if (bias != nullptr) {
-            const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
-            vv[0] += b4.x; vv[1] += b4.y; vv[2] += b4.z; vv[3] += b4.w;
-          }
-          if (resid != nullptr) {
-            const float4 r4 = *reinterpret_cast<const float4*>(resid + oidx);
-            vv[0] += r4.x; vv[1] += r4.y; vv[2] += r4.z; vv[3] += r4.w;
-          }
-          if (flags & VCF_CLAMP) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vv[e] = fminf(fmaxf(vv[e], -1.f), 1.f);
-          }
-          *reinterpret_cast<float4*>(y + oidx) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (co + e < Cout) {
-              float o = vv[e] + (bias != nullptr ? bias[co + e] : 0.f) + (resid != nullptr ? resid[oidx + e] : 0.f);
-              if (flags & VCF_CLAMP) o = fminf(fmaxf(o, -1.f), 1.f);
-              y[oidx + e] = o;
-            }
-        }
+        vconv_epilogue4(acc[i][n], g, co, oidx, bias, resid, y, Cout, flags, vec_ok);
       }
   }
 #endif
@@ -646,41 +508,31 @@ __global__ __launch_bounds__(256) void blend_axis_kernel(const float* __restrict
 
 
 // ------------------------------------------------------------------------------------------------
-// Halo-tiled form of the 16-bit convolution for 3x3 spatial kernels (kt = 1 or 3).  vae_conv16_kernel stages a fresh 256-pixel
-// input block for every tap — 48 KB from the L2 per 4.2 MFLOP, and the PMC profile shows it pinned at the L2's aggregate request
-// rate (11 TB/s, matrix pipe 32 % busy).  Here a workgroup owns an 8 x 32 pixel tile of one output frame and stages, per input
+// Halo-tiled form of the 16-bit convolution for 3x3 spatial kernels (kt = 1 or 3), 64 pixels per wave.  What still reaches it: by default the 3x3
+// convolutions at least 16 pixels wide whose Cout the 128-pixel kernel of vae16g.hip does not take (vae_conv16g_ok: Cout neither a multiple of 96 or
+// 128 nor <= 16) — at the released widths that is the Wan encoder's head alone (384 -> 32 couts, vae_enc.py); a kernel trace of the encoder tests
+// (profiles/vae_conv_refactor_isa.txt) shows NF = 1 for that head and for the 32-cout convolutions of the tests' dim-32 model, NF = 2 for that model's
+// 64-cout ones, and no NF = 3 / 4 launch — and any 3x3 shape on request (flag 8 of x2v_vae_conv_f16: the tests' cross-check of the 128-pixel kernel).
+// The per-tap kernel stages a fresh 256-pixel input block for every tap — 48 KB from the L2 per 4.2 MFLOP, and the PMC profile shows it pinned at the
+// L2's aggregate request rate (11 TB/s, matrix pipe 32 % busy).  Here a workgroup owns an 8 x 32 pixel tile of one output frame and stages, per input
 // frame tap dt and 64-channel slab, the 10 x 34 pixel HALO block once (44 KB); the nine spatial taps then read their shifted
 // 8 x 32 windows out of that one LDS image, so only the weights (16 KB per tap) stream per step: 187 KB per 37.7 MFLOP, 2.3x fewer
-// L2 bytes per FLOP.  Same MFMA tiling as vae_conv16_kernel (wave = 2 image rows x 32 px = two 32-row MFMA blocks, 32 NF couts).
+// L2 bytes per FLOP.  Same MFMA tiling as the per-tap kernel (wave = 2 image rows x 32 px = two 32-row MFMA blocks, 32 NF couts).
 //   * LDS: halo image [352 rows][128 B] x 2 (row r = hy*34 + hx, chunk ^= (r >> 1) & 7 applied on the DMA source as everywhere),
-//     weight slab [32 NF][128 B] x 2.  Fragment row of lane fl for tap (dh, dw), image row 2 wid + mi: r = (2 wid + mi + dh)*34 + dw + fl;
+//     weight slab [32 NF][128 B] x VH_NB.  Fragment row of lane fl for tap (dh, dw), image row 2 wid + mi: r = (2 wid + mi + dh)*34 + dw + fl;
 //     the swizzle depends on r, so the 8 fragment addresses are recomputed per tap (a few VALU against 8 NF MFMAs).
 //   * schedule: step = (slab, tap), one barrier per step, 4 compute waves + 4 loader waves (one of each per SIMD).  The weight slabs
 //     travel through a RING of VH_NB = 4 LDS slots: at step s a loader issues the weights of step s + 3 (and, on a slab's first tap, the
-//     next slab's halo: 11 pieces per loader wave, padded rows masked) and waits only until the weights of step s + 1 have landed — a
-//     counted vmcnt that leaves the two younger weight slabs (and, for its first three steps, the halo) in flight.  Round 5: with a
+//     next slab's halo: 11 pieces per loader wave, padded rows masked) and waits only until the weights of step s + VH_NEED = s + 2 have landed
+//     (the compute waves read step s + 1's first fragments in front of step s's barrier) — a counted vmcnt that leaves the youngest weight slab
+//     (and, for a slab's first steps, the halo) in flight.  Round 5: with a
 //     two-slot ring every step waited for weights issued ONE step earlier, i.e. a step lasted an L2 round trip (~2200 cycles against the
 //     step's 1024 MFMA cycles: the 45 % matrix-pipe busy of the round-1 profile), and __syncthreads() in front of the barrier drained
 //     the halo as well (hipcc's VMEM drain for the release fence) — both found in the ISA.
 // the bare instruction, not __syncthreads(): its release fence makes hipcc drain the wave's whole VMEM queue in front of the barrier (+2.8 % on the decode)
 #define VH_BARRIER() asm volatile("s_barrier" ::: "memory")
-#ifndef X2V_VH_RING
-#define X2V_VH_RING 4  // weight-slab ring slots (A/B builds: 2 = the one-step-ahead form of rounds 1-4)
-#endif
-#ifndef X2V_VH_PREFETCH
-#define X2V_VH_PREFETCH (X2V_VH_RING >= 4)  // the compute waves read step s + 1's first fragments in front of step s's barrier (A/B builds: 0)
-#endif
-#ifndef X2V_VH_INTERLEAVE
-#define X2V_VH_INTERLEAVE 1  // one fragment read behind every MFMA (slot form; A/B builds: 0 = read blocks between MFMA blocks)
-#endif
-#ifndef X2V_VH_DIST
-#define X2V_VH_DIST 1  // slot form: k-steps of fragment read-ahead.  2 (three fragment sets, step loop unrolled by 3, 239 VGPRs) was measured in round 5
-                       // and is SLOWER: 2.62 vs 2.38 s per 720p x 81f decode on one box (profiles/r05_call10_*) — the read pipeline's depth is not the limiter either
-#endif
-constexpr int VH_NB = X2V_VH_RING;
-constexpr int VH_NEED = X2V_VH_PREFETCH ? 2 : 1;  // at step s the loaders wait for the weights of step s + VH_NEED
-static_assert(VH_NB == 2 || VH_NB == 4, "ring of 2 (one step ahead) or 4 (three steps ahead)");
-static_assert(VH_NEED <= VH_NB - 1, "the cross-step fragment prefetch needs the 4-slot ring");
+constexpr int VH_NB = 4;    // weight-slab ring slots
+constexpr int VH_NEED = 2;  // at step s the loaders wait for the weights of step s + VH_NEED
 constexpr int VH_TH = 8, VH_TW = 32, VH_HW = VH_TW + 2, VH_ROWS = 352, VH_A_BYTES = VH_ROWS * 128, VH_A_PIECES = VH_ROWS / 8 / 4;
 
 template <int NF>
@@ -858,20 +710,16 @@ __global__ __launch_bounds__(512, 2) void vae_conv16h_kernel(const _Float16* __r
     }
     return a;
   };
-  // SLOT form (NF < 4): MFMA m of a k-step is followed by fragment read m of the k-step DIST ahead (2 + NF reads for 2 NF MFMAs), pinned with
-  // sched_barrier; the reads run DIST k-steps ahead through DIST + 1 fragment sets — across the step boundary, i.e. in front of the barrier (VH_NEED = 2:
-  // the next step's weights were published one barrier earlier).  Round 5 (profiles/r05_call8_* .. r05_call11_*): against the BLOCK form (all reads of a
-  // k-step, then all its MFMAs — the read / address instructions between two MFMA blocks drain the matrix pipe four times per step; still what NF = 4 runs,
-  // where 128 accumulators leave no room for more) the slot form is worth +3.5 % of the 720p decode; DIST = 2 (three sets, step loop unrolled by 3, 239 VGPRs)
-  // is 9 % SLOWER than DIST = 1.  Knock-out probes of that round (a build without MFMAs / without DMA / without barriers, results invalid by construction,
-  // git history: commit "VAE timing probes") put the decode at 75 % / 85 % / 97 % of its time: no single resource is the limit, the step is too small.
-  constexpr bool SLOT = X2V_VH_INTERLEAVE != 0 && NF < 4;
-  constexpr bool PF = X2V_VH_PREFETCH != 0 && NF < 4;  // reads run on across the step boundary (NF = 4: no registers for it — every step starts with its own first reads)
-  constexpr int DIST = SLOT && PF ? X2V_VH_DIST : 1;  // k-steps of read-ahead
-  constexpr int NSET = DIST + 1;                                   // fragment sets
-  constexpr int UNR = NSET == 3 ? 3 : 1;                           // a step has 4 k-steps: the set phase advances by 4 mod NSET per step
-  static_assert(DIST == 1 || DIST == 2, "one or two k-steps of fragment read-ahead");
-  vc_half8_t xa[NSET][2], wb[NSET][NF];
+  // SLOT form (NF < 4): two fragment sets; MFMA m of a k-step is followed by fragment read m of the NEXT k-step (2 + NF reads for 2 NF MFMAs), pinned with
+  // sched_barrier, and the reads run on across the step boundary, i.e. in front of the barrier (VH_NEED = 2: the next step's weights were published one
+  // barrier earlier).  BLOCK form (NF = 4, where 128 accumulators leave no registers for more): all reads of a k-step, then all its MFMAs, and every step
+  // starts with its own first reads — the read / address instructions between two MFMA blocks drain the matrix pipe four times per step.
+  // Round 5 (profiles/r05_call8_* .. r05_call11_*): the slot form is worth +3.5 % of the 720p decode over the block form; reading TWO k-steps ahead (three
+  // sets, step loop unrolled by 3, 239 VGPRs) was 9 % SLOWER (2.62 vs 2.38 s per 720p x 81f decode, profiles/r05_call10_*): the read pipeline's depth is
+  // not the limiter.  Knock-out probes of that round (a build without MFMAs / without DMA / without barriers, results invalid by construction, git
+  // history: commit "VAE timing probes") put the decode at 75 % / 85 % / 97 % of its time: no single resource is the limit, the step is too small.
+  constexpr bool SLOT = NF < 4;
+  vc_half8_t xa[2][2], wb[2][NF];
   // read r of k-step KS of the step addressed by A into fragment set S: r = 0: xa[0], 1 .. NF: wb[0 .. NF-1], NF + 1: xa[1]
   auto frag_read = [&](int S, int KS, const Step& A, int r) {
     if (r == 0 || r == NF + 1) {
@@ -882,61 +730,61 @@ __global__ __launch_bounds__(512, 2) void vae_conv16h_kernel(const _Float16* __r
     }
   };
   Step cur = step_addr(0, 0, 0);
-  if (PF) {  // the pipeline's head: the first DIST k-steps of the tile
+  if (SLOT) {  // the pipeline's head: the first k-step of the tile
 #pragma unroll
-    for (int d = 0; d < DIST; ++d)
-#pragma unroll
-      for (int r = 0; r < 2 + NF; ++r) frag_read(d, d, cur, r);
+    for (int r = 0; r < 2 + NF; ++r) frag_read(0, 0, cur, r);
   }
   int slab = 0, tap9 = 0;
 #pragma unroll 1
-  for (int st = 0; st < nsteps; st += UNR) {  // nsteps is a multiple of 9
+  for (int st = 0; st < nsteps; ++st) {
+    // One trip.  This loop is what is left of the step loop's unroll-by-3 form (round 5's two-k-steps-ahead build); written without it hipcc orders the
+    // step loop's scalar address instructions differently.  Kept so that the loop stays instruction-identical to the measured one (tools/vae_conv_isa_diff.py).
 #pragma unroll
-    for (int p = 0; p < UNR; ++p) {
-      int nslab = slab, ntap = tap9 + 1;
-      if (ntap == 9) {
-        ntap = 0;
-        ++nslab;
-      }
-      // (behind the tile's last step the "next step" addresses still lie inside the LDS images: those reads are harmless and unused — no branch)
-      const Step nxt = step_addr(nslab, ntap, st + p + 1);
-      if (!PF) {
+    for (int once = 0; once < 1; ++once) {
+    int nslab = slab, ntap = tap9 + 1;
+    if (ntap == 9) {
+      ntap = 0;
+      ++nslab;
+    }
+    // (behind the tile's last step the "next step" addresses still lie inside the LDS images: those reads are harmless and unused — no branch)
+    const Step nxt = step_addr(nslab, ntap, st + 1);
+    if (!SLOT) {
 #pragma unroll
-        for (int r = 0; r < 2 + NF; ++r) frag_read(0, 0, cur, r);
-      }
+      for (int r = 0; r < 2 + NF; ++r) frag_read(0, 0, cur, r);
+    }
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int cs = (4 * p + ks) % NSET, ns = (4 * p + ks + DIST) % NSET;  // sets consumed / filled by this k-step
-        const int kn = ks + DIST;                                           // the k-step read now: of this step, or of the next one
-        const bool rd = kn < 4 || PF;
-        if constexpr (SLOT) {
+    for (int ks = 0; ks < 4; ++ks) {
+      const int cs = ks & 1, ns = cs ^ 1;  // sets consumed / filled by this k-step
+      const int kn = ks + 1;               // the k-step read now: of this step, or (slot form) the first of the next one
+      const bool rd = kn < 4 || SLOT;
+      if constexpr (SLOT) {
 #pragma unroll
-          for (int m = 0; m < 2 * NF; ++m) {
-            const int i = m / NF, n = m - i * NF;
-            acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[cs][n], xa[cs][i], acc[i][n], 0, 0, 0);
-            // slot m carries read m (the last slot every read that is left: NF = 1 has 3 reads for 2 MFMAs)
+        for (int m = 0; m < 2 * NF; ++m) {
+          const int i = m / NF, n = m - i * NF;
+          acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[cs][n], xa[cs][i], acc[i][n], 0, 0, 0);
+          // slot m carries read m (the last slot every read that is left: NF = 1 has 3 reads for 2 MFMAs)
 #pragma unroll
-            for (int r = m; r < (m == 2 * NF - 1 ? 2 + NF : m + 1); ++r)
-              if (r < 2 + NF && rd) frag_read(ns, kn & 3, kn < 4 ? cur : nxt, r);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        } else {
-          if (rd) {
-#pragma unroll
-            for (int r = 0; r < 2 + NF; ++r) frag_read(ns, kn & 3, kn < 4 ? cur : nxt, r);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int n = 0; n < NF; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[cs][n], xa[cs][i], acc[i][n], 0, 0, 0);
+          for (int r = m; r < (m == 2 * NF - 1 ? 2 + NF : m + 1); ++r)
+            if (r < 2 + NF && rd) frag_read(ns, kn & 3, kn < 4 ? cur : nxt, r);
           __builtin_amdgcn_sched_barrier(0);
         }
+      } else {
+        if (rd) {
+#pragma unroll
+          for (int r = 0; r < 2 + NF; ++r) frag_read(ns, kn & 3, kn < 4 ? cur : nxt, r);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int n = 0; n < NF; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[cs][n], xa[cs][i], acc[i][n], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      VH_BARRIER();
-      cur = nxt;
-      slab = nslab;
-      tap9 = ntap;
+    }
+    VH_BARRIER();
+    cur = nxt;
+    slab = nslab;
+    tap9 = ntap;
     }
   }
 
@@ -953,33 +801,7 @@ __global__ __launch_bounds__(512, 2) void vae_conv16h_kernel(const _Float16* __r
       for (int g = 0; g < 4; ++g) {
         const int co = co0 + n * 32 + 8 * g + 4 * fh;
         if (co >= Cout) continue;
-        float vv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = acc[i][n][4 * g + e];
-        const int64_t oidx = pbase * Cout + co;
-        if (vec_ok) {
-          if (bias != nullptr) {
-            const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
-            vv[0] += b4.x; vv[1] += b4.y; vv[2] += b4.z; vv[3] += b4.w;
-          }
-          if (resid != nullptr) {
-            const float4 r4 = *reinterpret_cast<const float4*>(resid + oidx);
-            vv[0] += r4.x; vv[1] += r4.y; vv[2] += r4.z; vv[3] += r4.w;
-          }
-          if (flags & VCF_CLAMP) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vv[e] = fminf(fmaxf(vv[e], -1.f), 1.f);
-          }
-          *reinterpret_cast<float4*>(y + oidx) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (co + e < Cout) {
-              float o = vv[e] + (bias != nullptr ? bias[co + e] : 0.f) + (resid != nullptr ? resid[oidx + e] : 0.f);
-              if (flags & VCF_CLAMP) o = fminf(fmaxf(o, -1.f), 1.f);
-              y[oidx + e] = o;
-            }
-        }
+        vconv_epilogue4(acc[i][n], g, co, pbase * Cout + co, bias, resid, y, Cout, flags, vec_ok);
       }
   }
   }  // persistent tile loop
@@ -994,20 +816,31 @@ int vae_conv16g_dispatch(const void* xp, const void* cache, int64_t fs, int64_t 
 
 using namespace x2v;
 
-template <int NF, int KC>
-static int launch_vconv(const float* xp, int64_t fs, int64_t rs, int64_t ps, const float* w, int64_t wrs, const float* bias, const float* resid, float* y,
-                        int T, int Hh, int Ww, int Cin, int Cout, int kt, int kh, int kw, int flags, hipStream_t st) {
-  constexpr int lds = 2 * (VC_PIX + 32 * NF) * KC * 4;
+// 32-cout blocks per workgroup (NF) of the per-tap and the 64-pixel halo kernels for a Cout: one block up to 32 couts, three where Cout is a multiple of 96
+// (the Wan widths; multiples of 128 keep four), two up to 64, else four.  Calls f(std::integral_constant<int, NF>).
+template <class F>
+static int with_vconv_nf(int Cout, F&& f) {
+  if (Cout <= 32) return f(std::integral_constant<int, 1>{});
+  if (Cout % 128 != 0 && Cout % 96 == 0) return f(std::integral_constant<int, 3>{});
+  if (Cout <= 64) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 4>{});
+}
+
+template <typename OP, int NF, int KC>
+static int launch_vconv(const void* xp, int64_t fs, int64_t rs, int64_t ps, const void* w, int64_t wrs, const float* bias, const float* resid, float* y, int T, int Hh,
+                        int Ww, int Cin, int Cout, int kt, int kh, int kw, int flags, hipStream_t st) {
+  constexpr int lds = 2 * (VC_PIX + 32 * NF) * KC * (int)sizeof(OP);
+  constexpr bool F16 = sizeof(OP) == 2;
   {
-    int rc = ensure_dynamic_lds((const void*)vae_conv_kernel<NF, KC>, lds, "vae conv attr");
+    int rc = ensure_dynamic_lds((const void*)vae_conv_kernel<OP, NF, KC>, lds, F16 ? "vae conv16 attr" : "vae conv attr");
     if (rc != X2V_OK) return rc;
   }
   const int64_t ptiles = (int64_t)T * (((int64_t)Hh * Ww + VC_PIX - 1) / VC_PIX);
   const int ncol = (Cout + 32 * NF - 1) / (32 * NF);
-  X2V_REQUIRE(ptiles * ncol < (1ll << 31), X2V_E_SHAPE, "vae_conv: too many tiles");
-  hipLaunchKernelGGL((vae_conv_kernel<NF, KC>), dim3((unsigned)(ptiles * ncol)), dim3(256), lds, st, xp, fs, rs, ps, w, wrs, bias, resid, y, T, Hh, Ww, Cin, Cout,
-                     kt, kh, kw, flags, ncol);
-  X2V_LAUNCH_CHECK("vae_conv launch");
+  X2V_REQUIRE(ptiles * ncol < (1ll << 31), X2V_E_SHAPE, "%s: too many tiles", F16 ? "vae_conv_f16" : "vae_conv");
+  hipLaunchKernelGGL((vae_conv_kernel<OP, NF, KC>), dim3((unsigned)(ptiles * ncol)), dim3(256), lds, st, (const OP*)xp, fs, rs, ps, (const OP*)w, wrs, bias, resid, y, T,
+                     Hh, Ww, Cin, Cout, kt, kh, kw, flags, ncol);
+  X2V_LAUNCH_CHECK(F16 ? "vae_conv_f16 launch" : "vae_conv launch");
   return X2V_OK;
 }
 
@@ -1027,18 +860,11 @@ extern "C" __attribute__((visibility("default"))) int x2v_vae_conv_f32(const flo
               "vae_conv: a kt-frame input window / 128 weight rows must stay below 2 GiB (32-bit buffer offsets)");
   X2V_REQUIRE(!(flags & VCF_TSPLIT) || (Cout % 8 == 0 && resid == nullptr), X2V_E_ARG, "vae_conv: time-split output needs Cout %% 8 == 0 and no residual");
   hipStream_t st = (hipStream_t)stream;
-#define X2V_VC(NF_, KC_) return launch_vconv<NF_, KC_>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, st)
-  const bool k32 = Cin % 32 == 0;
-  if (Cout <= 32) {
-    if (k32) X2V_VC(1, 32); else X2V_VC(1, 16);
-  } else if (Cout % 128 != 0 && Cout % 96 == 0) {
-    if (k32) X2V_VC(3, 32); else X2V_VC(3, 16);
-  } else if (Cout <= 64) {
-    if (k32) X2V_VC(2, 32); else X2V_VC(2, 16);
-  } else {
-    if (k32) X2V_VC(4, 32); else X2V_VC(4, 16);
-  }
-#undef X2V_VC
+  return with_vconv_nf(Cout, [&](auto nf) {
+    constexpr int NF = decltype(nf)::value;
+    if (Cin % 32 == 0) return launch_vconv<float, NF, 32>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, st);
+    return launch_vconv<float, NF, 16>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, st);
+  });
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_vae_prep_f32(const float* x, float* y, int T, int Hh, int Ww, int C, const float* gamma,
@@ -1109,12 +935,11 @@ static int vae_prep_f16_impl(const float* x, void* y, int T, int Hh, int Ww, int
                        y_frame_stride, y_row_stride, y_px_stride, split);
   };
   // lanes per pixel: a lane takes up to four 4-channel chunks LPP apart.  The decoder's widths are 3 x 2^n chunks (96 / 192 / 384 channels = 24 / 48 / 96):
-  // a third of them per pixel keeps every lane busy (the power-of-two choice below idles a quarter of each wave)
+  // a third of them per pixel keeps every lane busy (the power-of-two choice below would idle a quarter of each wave: 523 vs 398 ms)
   const int nch = C / 4;
-  static const bool thirds = [] { const char* e = getenv("X2V_VAE_PREP_POW2"); return e == nullptr || atoi(e) == 0; }();  // A/B: 1 = the power-of-two lane groups
-  if (thirds && nch == 24) launch(std::integral_constant<int, 8>{});
-  else if (thirds && nch == 48) launch(std::integral_constant<int, 16>{});
-  else if (thirds && nch == 96) launch(std::integral_constant<int, 32>{});
+  if (nch == 24) launch(std::integral_constant<int, 8>{});
+  else if (nch == 48) launch(std::integral_constant<int, 16>{});
+  else if (nch == 96) launch(std::integral_constant<int, 32>{});
   else if (C <= 128) launch(std::integral_constant<int, 32>{});
   else launch(std::integral_constant<int, 64>{});
   X2V_LAUNCH_CHECK("vae_prep_f16 launch");
@@ -1154,23 +979,6 @@ extern "C" __attribute__((visibility("default"))) int x2v_vae_prep_ex_f16(const 
                        y_frame_stride, y_row_stride);
   }
   X2V_LAUNCH_CHECK("vae_prep_ex_f16 launch");
-  return X2V_OK;
-}
-
-template <int NF>
-static int launch_vconv16(const void* xp, int64_t fs, int64_t rs, int64_t ps, const void* w, int64_t wrs, const float* bias, const float* resid, float* y, int T, int Hh,
-                          int Ww, int Cin, int Cout, int kt, int kh, int kw, int flags, hipStream_t st) {
-  constexpr int lds = 2 * (VC_PIX + 32 * NF) * 128;
-  {
-    int rc = ensure_dynamic_lds((const void*)vae_conv16_kernel<NF>, lds, "vae conv16 attr");
-    if (rc != X2V_OK) return rc;
-  }
-  const int64_t ptiles = (int64_t)T * (((int64_t)Hh * Ww + VC_PIX - 1) / VC_PIX);
-  const int ncol = (Cout + 32 * NF - 1) / (32 * NF);
-  X2V_REQUIRE(ptiles * ncol < (1ll << 31), X2V_E_SHAPE, "vae_conv_f16: too many tiles");
-  hipLaunchKernelGGL((vae_conv16_kernel<NF>), dim3((unsigned)(ptiles * ncol)), dim3(256), lds, st, (const _Float16*)xp, fs, rs, ps, (const _Float16*)w, wrs, bias, resid,
-                     y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, ncol);
-  X2V_LAUNCH_CHECK("vae_conv_f16 launch");
   return X2V_OK;
 }
 
@@ -1219,7 +1027,7 @@ extern "C" __attribute__((visibility("default"))) int x2v_vae_conv_f16_cached(co
                                                                               float* y, int T, int Hh, int Ww, int Cin, int Cout, int kt, int kh, int kw, int flags, void* stream) {
   X2V_REQUIRE(cache != nullptr && aligned16(cache), X2V_E_ARG, "vae_conv_f16_cached: cache must be a 16-byte aligned pointer");
   X2V_REQUIRE(x2v_vae_conv_f16_cached_ok(Ww, Cin, Cout, kh, kw, flags) == 1, X2V_E_SHAPE,
-              "vae_conv_f16_cached: 3x3 kernels with Cout %% 96 == 0 or Cout <= 16 only (x2v_vae_conv_f16_cached_ok)");
+              "vae_conv_f16_cached: 3x3 kernels at least 16 pixels wide with Cin %% 32 == 0 and Cout %% 96 == 0, Cout %% 128 == 0 or Cout <= 16 only (x2v_vae_conv_f16_cached_ok)");
   return vae_conv_f16_impl(xp, cache, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, stream);
 }
 
@@ -1238,27 +1046,20 @@ static int vae_conv_f16_impl(const void* xp, const void* cache, int64_t x_frame_
   X2V_REQUIRE(!(flags & VCF_TSPLIT) || (Cout % 8 == 0 && resid == nullptr), X2V_E_ARG, "vae_conv_f16: time-split output needs Cout %% 8 == 0 and no residual");
   hipStream_t st = (hipStream_t)stream;
   X2V_REQUIRE((flags & ~31) == 0 && (!(flags & 16) || Cin >= 64), X2V_E_ARG, "vae_conv_f16: flags = 1 clamp | 2 time-split | 4 per-tap kernel | 8 64-pixel halo kernel | 16 zero tail");
-  // 3x3 spatial kernels take a halo-tiled kernel (2.3x fewer L2 bytes per FLOP than a fresh pixel block per tap) unless the image is narrower than half a tile
-  // or the caller asks for the per-tap kernel (flag 4: A/B measurements and tests): the 128-pixel x 96-cout kernel of vae16g.hip where Cout is a multiple of 96
-  // (every 3x3 convolution of the Wan decoder but its 3-channel head), else — or with flag 8 — the 64-pixel kernel below.
+  // Dispatch.  3x3 spatial kernels on images at least 16 pixels (half a tile) wide take a halo-tiled kernel (2.3x fewer L2 bytes per FLOP than a fresh pixel
+  // block per tap): the 128-pixel kernel of vae16g.hip where vae_conv16g_ok says so — Cout a multiple of 96 (every 3x3 convolution of the Wan decoder's body)
+  // or of 128 (every convolution of the HunyuanVideo VAE) or at most 16 (the 3-channel heads), Cin a multiple of 32 — else, or with flag 8, the 64-pixel
+  // kernel above.  Everything else — other kernel sizes, narrower images, the time-split epilogue, flag 4 (A/B measurements and tests) — takes the per-tap kernel.
   // Flag 16: the last 32 channels of Cin are zero padding in both operands (the split mode's 3 x 96 = 288 channels in a 320-channel buffer); the 32-channel-slab
   // kernel skips them, the others multiply the zeros.
   if (kh == 3 && kw == 3 && !(flags & (VCF_TSPLIT | 4 | 8)) && vae_conv16g_ok(Ww, Cin, Cout))
     return vae_conv16g_dispatch(xp, cache, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, flags, (flags & 16) ? 32 : 0, st);
-  if (kh == 3 && kw == 3 && !(flags & (VCF_TSPLIT | 4)) && Ww >= 16) {
-#define X2V_VC16H(NF_) return launch_vconv16h<NF_>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, flags, st)
-    if (Cout <= 32) X2V_VC16H(1);
-    else if (Cout % 128 != 0 && Cout % 96 == 0) X2V_VC16H(3);
-    else if (Cout <= 64) X2V_VC16H(2);
-    else X2V_VC16H(4);
-#undef X2V_VC16H
-  }
-#define X2V_VC16(NF_) return launch_vconv16<NF_>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, st)
-  if (Cout <= 32) X2V_VC16(1);
-  else if (Cout % 128 != 0 && Cout % 96 == 0) X2V_VC16(3);
-  else if (Cout <= 64) X2V_VC16(2);
-  else X2V_VC16(4);
-#undef X2V_VC16
+  const bool halo = kh == 3 && kw == 3 && !(flags & (VCF_TSPLIT | 4)) && Ww >= 16;
+  return with_vconv_nf(Cout, [&](auto nf) {
+    constexpr int NF = decltype(nf)::value;
+    if (halo) return launch_vconv16h<NF>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, flags, st);
+    return launch_vconv<_Float16, NF, 64>(xp, x_frame_stride, x_row_stride, x_px_stride, w, w_row_stride, bias, resid, y, T, Hh, Ww, Cin, Cout, kt, kh, kw, flags, st);
+  });
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_vae_replicate_border_f32(float* buf, int frames, int lead, int Hp, int Wp, int C, int pad, void* stream) {

@@ -1,5 +1,6 @@
-// 3x3(x kt) convolution on fp16 operands, fp32 accumulate — the GEMM-shaped form of the Wan VAE decoder's halo convolution (vae.hip's vae_conv16h_kernel is the
-// round 1-5 form and still serves Cout that is not a multiple of 96, narrow images and the A/B flag).
+// 3x3(x kt) convolution on fp16 operands, fp32 accumulate — the GEMM-shaped form of the VAEs' halo convolution.  x2v_vae_conv_f16 runs it for 3x3 kernels on images
+// at least 16 pixels wide with Cin a multiple of 32 and Cout a multiple of 96 (the Wan decoder's body), a multiple of 128 (the HunyuanVideo VAE) or at most 16 (the
+// 3-channel heads): vae_conv16g_ok below.  vae.hip's vae_conv16h_kernel is the round 1-5 form and still serves every other Cout and flag 8.
 // reference: models/video_encoders/hf/wan/vae.py — CausalConv3d :19-44 as used by ResidualBlock :185-223, Resample :70-159 and the decoder head :436-489.
 //
 // Bound: MFMA (16-bit dense peak ~2.5 PFLOP/s).  Algorithmic work 2 * T*H*W * Cout * Cin * 9 kt FLOP per launch (Cin = the operand buffer's channels: three
@@ -88,9 +89,7 @@ __device__ __forceinline__ void g_acc_zero() {
   else asm volatile("v_accvgpr_write_b32 a[%c0], 0" ::"i"(R) : G_AGPRS);
 }
 
-#ifndef X2V_G_BAR_SLOT
-#define X2V_G_BAR_SLOT 40  // MFMA slot of a step's middle tap behind which the step's barrier sits (NCB = 6; NCB = 1: its last slot but one)
-#endif
+constexpr int G_BAR_SLOT = 40;  // MFMA slot of a step's middle tap behind which the step's barrier sits (NCB >= 6; NCB = 1: its last slot but one)
 
 template <int NCB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void vae_conv16g_kernel(
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c16 = lane & 15, g4 = lane >> 4;
   constexpr int G_WP = GCfg<NCB>::WP, G_W_BYTES = GCfg<NCB>::W_BYTES, NM = GCfg<NCB>::NM, NR = GCfg<NCB>::NR;
-  constexpr int BAR = NCB >= 6 ? X2V_G_BAR_SLOT : NM - 2;
+  constexpr int BAR = NCB >= 6 ? G_BAR_SLOT : NM - 2;
   const int nslabs = kt * kchunks;
   const unsigned ntiles = (unsigned)T * (unsigned)tiles_y * (unsigned)tiles_x * (unsigned)ncol;
 
@@ -291,7 +290,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     // ---- epilogue: acc[cb][pb][e] = pixel (y0 + 4 wid + (pb >> 1), x0 + 16 (pb & 1) + c16), cout co0 + 16 cb + 4 g4 + e
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");  // the last MFMAs' results before the accumulator reads below
-    const bool vec_ok = (Cout & 3) == 0;  // else (the 3-channel head) element-wise with a bound per channel
+    // 16-byte accesses need all four couts of every lane's group to exist: a whole number of 16-cout blocks (NCB > 1: Cout is a multiple of 96 or 128; NCB = 1:
+    // Cout = 16).  Else (the 3-channel head, any Cout < 16) element-wise with a bound per channel
+    const bool vec_ok = (Cout & 3) == 0 && (NCB > 1 || Cout == 16);
     float4 bv[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {

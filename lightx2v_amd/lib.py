@@ -744,7 +744,10 @@ def vae_conv(xp, strides, weight, out, T, H, W, bias=None, resid=None, flags=0, 
     return out
 
 
-_VCONV16_FORCE = {"": 0, "halo64": VCONV_HALO64, "pertap": VCONV_PER_TAP}[os.environ.get("X2V_VAE_CONV16", "")]  # A/B runs: force one of the older 3x3 kernels
+_VCONV16_KERNELS = {"": 0, "halo64": VCONV_HALO64, "pertap": VCONV_PER_TAP}
+if os.environ.get("X2V_VAE_CONV16", "") not in _VCONV16_KERNELS:
+    raise X2VError(f"X2V_VAE_CONV16={os.environ['X2V_VAE_CONV16']!r}: accepted values are 'halo64' and 'pertap' (or unset / empty: the default dispatch)")
+_VCONV16_FORCE = _VCONV16_KERNELS[os.environ.get("X2V_VAE_CONV16", "")]  # A/B runs: force one of the older 3x3 kernels
 
 
 def vae_conv16_cached_ok(W, weight, flags=0):

@@ -307,13 +307,16 @@ def test_vae_conv16_128x96_kernel_against_conv3d_and_the_other_kernels():
     order.  Shapes: ragged tiles in H and W (tile = 16 x 32 pixels), one to four cout tiles, kt 1 and 3 with a non-zero 2-frame cache, 2..12 32-channel
     slabs (odd and even counts: both halo buffers end a tile), residual, clamp, the zero-tail flag (288 channels in a 320-channel buffer: bit-identical
     with and without the flag), several tiles per workgroup (more tiles than CUs), and the one-cout-block form the decoder's 3-channel head takes
-    (Cout 3 and 16: weight rows beyond Cout masked, element-wise stores); and the 128-cout form of the same kernel (Cout % 128 == 0 and not a multiple of 96)."""
+    (Cout 3 and 16: weight rows beyond Cout masked, element-wise stores; Cout 4, 8 and 12: multiples of 4 below the 16-cout block, which must take the
+    bounded element-wise stores as well); and the 128-cout form of the same kernel (Cout % 128 == 0 and not a multiple of 96).  For Cout <= 16 the output
+    is a view into a larger NaN-filled allocation, and every element outside the view must still be NaN afterwards: no store past Cout or past the end."""
     from lightx2v_amd import lib
 
     g = torch.Generator().manual_seed(11)
     cached_runs = 0
     for (T, H, W, Cin, Cout, kt, tail) in [(2, 8, 32, 128, 96, 1, 0), (2, 9, 11, 64, 192, 3, 0), (1, 17, 40, 288, 96, 3, 32), (3, 33, 70, 96, 384, 3, 32), (2, 16, 64, 192, 288, 1, 0),
                                            (9, 90, 160, 64, 96, 3, 0), (1, 17, 33, 64, 3, 3, 0), (2, 36, 70, 288, 3, 3, 32), (2, 9, 40, 128, 16, 1, 0),
+                                           (2, 9, 40, 64, 4, 1, 0), (1, 17, 33, 128, 8, 3, 0), (2, 20, 48, 64, 12, 3, 0),
                                            # the 128-cout form (8 x 8 accumulator tiles; the HunyuanVideo VAE's widths): one, two and four cout tiles
                                            (2, 17, 40, 128, 128, 3, 0), (1, 33, 70, 256, 256, 1, 0), (2, 16, 64, 512, 256, 3, 0), (1, 9, 33, 64, 512, 1, 0)]:
         cp = (Cin + 63) // 64 * 64
@@ -330,9 +333,19 @@ def test_vae_conv16_128x96_kernel_against_conv3d_and_the_other_kernels():
         w16[..., :Cin] = w.permute(0, 2, 3, 4, 1).cuda()
         strides = ((H + 2) * (W + 2) * cp, (W + 2) * cp, cp)
         outs = {}
+        n_out, guard = T * H * W * Cout, 256 if Cout <= 16 else 0  # floats in front of and behind the output (a multiple of 4: the view stays 16-byte aligned)
+
+        def guarded_out():
+            whole = torch.full((guard + n_out + guard,), float("nan"), device="cuda")
+            return whole, whole[guard : guard + n_out].view(T, H, W, Cout)
+
+        def assert_guard_untouched(whole, what):
+            assert torch.isnan(whole[:guard]).all() and torch.isnan(whole[guard + n_out :]).all(), f"{what}: wrote outside its output (Cout={Cout})"
+
         for flags in (0, lib.VCONV_HALO64, lib.VCONV_PER_TAP) + ((lib.VCONV_ZERO_TAIL32,) if tail else ()):
-            out = torch.full((T, H, W, Cout), float("nan"), device="cuda")
+            whole, out = guarded_out()
             lib.vae_conv16(buf, strides, w16, out, T, H, W, bias=b.cuda(), resid=res.cuda(), flags=flags | lib.VCONV_CLAMP)
+            assert_guard_untouched(whole, f"flags={flags}")
             _check(out, ref, f"16-bit conv kt={kt} {T}x{H}x{W} Cin={Cin} Cout={Cout} flags={flags}", atol=3e-4, rel=1e-5)
             outs[flags] = out
         _check(outs[0], outs[lib.VCONV_HALO64], "128 x 96 kernel vs 64-pixel halo kernel", atol=1e-5, rel=1e-6)
@@ -342,8 +355,9 @@ def test_vae_conv16_128x96_kernel_against_conv3d_and_the_other_kernels():
             cache = buf[: kt - 1].clone()
             poisoned = buf.clone()
             poisoned[: kt - 1] = float("nan")
-            out = torch.full((T, H, W, Cout), float("nan"), device="cuda")
+            whole, out = guarded_out()
             lib.vae_conv16(poisoned, strides, w16, out, T, H, W, bias=b.cuda(), resid=res.cuda(), flags=lib.VCONV_CLAMP, cache=cache)
+            assert_guard_untouched(whole, "separate cache tensor")
             assert torch.equal(out, outs[0]), "separate cache tensor"
         if tail:
             assert torch.equal(outs[0], outs[lib.VCONV_ZERO_TAIL32]), "skipping the zero slab must not change a bit"
@@ -359,3 +373,18 @@ def test_vae_conv16_128x96_kernel_against_conv3d_and_the_other_kernels():
         one = torch.empty(1, H, W, Cout, device="cuda")
         lib.vae_conv16(x[t:], strides, w16, one, 1, H, W)
         assert torch.equal(one[0], whole[t]), t
+
+
+def test_unknown_vae_conv16_kernel_name_is_an_x2v_error():
+    """X2V_VAE_CONV16 accepts 'halo64' and 'pertap'; anything else must fail with X2VError naming them, not with a KeyError (child process: the value is read at import; no GPU needed)."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys; sys.path.insert(0, %r)\ntry:\n    import lightx2v_amd.lib\nexcept Exception as e:\n    print(type(e).__name__, e)\nelse:\n    print('imported')" % root
+    for value, want in (("halo128", "X2VError"), ("halo64", "imported"), ("", "imported")):
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, X2V_VAE_CONV16=value), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.startswith(want), (value, r.stdout, r.stderr[-300:])
+        if want == "X2VError":
+            assert "halo64" in r.stdout and "pertap" in r.stdout, r.stdout
