@@ -24,7 +24,8 @@ def _stale(target, deps):
 
 def _compile(src):
     obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "x2v_common.h"), os.path.join(INCLUDE, "x2v.h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]  # every shared header: no stale object survives an edit of one
+    deps = [os.path.join(CSRC, src), *headers, os.path.join(INCLUDE, "x2v.h")]
     if _stale(obj, deps):
         subprocess.run([HIPCC, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj], check=True)
     return obj

@@ -22,7 +22,7 @@
 //   * 1-D grid, XCD-aware remap + grouped (8 m-tiles) ordering so the 64 tiles resident on one XCD share
 //     A/B panels through that XCD's L2.
 //   * M and N tails: source rows are clamped (loads stay in bounds), stores are masked.  K % 64 == 0.
-#include "x2v_common.h"
+#include "gemm256_pipe.h"
 
 namespace x2v {
 
@@ -252,24 +252,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
 
 }  // namespace x2v
 
-namespace x2v {
-// gemm256.hip: the 256x256-tile ping-pong kernel for large shapes
-template <bool FP8>
-int gemm256_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
-                     const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
-// gemm256s.hip: the same tile as one software-pipelined wave per SIMD (bf16)
-int gemm256s_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
-                      const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb);
-int gemm256s_vt_dispatch(const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* vt, int64_t ldvt, int64_t M, int N, int nk, hipStream_t st);
-// gemm256c.hip: the single-stream kernel as a continuous pipeline over output tiles (persistent workgroups, register-direct epilogue)
-bool gemm256c_ok(int nk, const GemmBlocking& gb);
-int gemm256c_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
-                      const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb);
-// gemm256c8.hip: the same continuous pipeline for the w8a8 operator (e4m3 operands, per-token / per-channel scales)
-int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
-                       const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
-}  // namespace x2v
-
 using namespace x2v;
 
 template <bool FP8, int EPI>
@@ -290,9 +272,6 @@ static int launch_gemm(const void* x, int64_t ldx_bytes, const void* w, int64_t 
 // The shape rule of variant 0 (one place: the dispatcher and x2v_gemm_kernel_choice both ask it): the 256^2 kernel wants at least
 // ~one full round of tiles (256 CUs), a K loop longer than its pipeline, and 32-bit buffer offsets over a 256-row tile.
 // bf16 takes the single-stream form of the 256^2 tile (3), fp8 / mxfp8 the ping-pong form (2).
-#ifndef X2V_GEMM256_BF16_KERNEL
-#define X2V_GEMM256_BF16_KERNEL 3
-#endif
 // The 256x256 kernels address an operand tile through a 32-bit buffer descriptor from the tile's first row: 255 rows + the K span of one row
 // (K-blocked x: (K blocks - 1) block strides + one block) must stay below 4 GiB, else the range check would wrap and valid elements read as
 // zero.  Such shapes take the 128x128 kernel (64-bit addressing).
@@ -300,6 +279,18 @@ static bool spans_fit_256(int nk, int64_t ldxb, int64_t ldwb, const GemmBlocking
   const int64_t a_kpb = gb.a_kpb > 0 && gb.a_kpb < nk ? gb.a_kpb : nk;
   const int64_t a_span = a_kpb < nk ? ((nk - 1) / a_kpb) * (int64_t)gb.a_cbs + a_kpb * 128 : (int64_t)nk * 128;
   return ldxb < (1 << 24) && ldwb < (1 << 24) && 255 * ldxb + a_span < (1ll << 32) && 255 * ldwb + (int64_t)nk * 128 < (1ll << 32);
+}
+
+// columns y spans in a row, N-blocked y (GemmBlocking) included
+static int64_t y_cols_span(int N, const GemmBlocking& gb) { return gb.y_cbw > 0 ? (int64_t)((N - 1) / gb.y_cbw) * gb.y_cbs + gb.y_cbw : (int64_t)N; }
+
+// Shapes the continuous single-stream kernels (gemm256c.hip, gemm256c8.hip) take; the others stay on gemm256s / the ping-pong kernel: an even number
+// of K tiles >= 4 (every output tile starts in LDS stage 0), N a multiple of 256 and y blocks that are whole multiples of a wave's 128 columns (a
+// wave's columns are contiguous), a residual tile addressed with y's offsets, and tile spans below 2^31 bytes — the epilogue addresses the output /
+// residual tile through descriptors of 2^31 bytes (offset 0x80000000 is its "no such row" mark).
+static bool continuous_ok(int nk, int N, int64_t ldy, int64_t ldr, const void* resid, const GemmBlocking& gb) {
+  return nk >= 4 && (nk & 1) == 0 && (gb.y_cbw <= 0 || gb.y_cbw % 128 == 0) && N % 256 == 0 && (255 * ldy + y_cols_span(N, gb)) * 2 < 0x80000000ll &&
+         (resid == nullptr || (ldr == ldy && gb.y_cbw <= 0));
 }
 
 int x2v::gemm_continuous_switch() {
@@ -314,7 +305,7 @@ int x2v::gemm_fp8_continuous_switch() {
 static int choose_kernel(int64_t M, int N, int nk, int64_t ldxb, int64_t ldwb, bool fp8, const GemmBlocking& gb = GemmBlocking()) {
   const bool fits256 = spans_fit_256(nk, ldxb, ldwb, gb);
   const int64_t tiles256 = ((M + 255) / 256) * (int64_t)((N + 255) / 256);
-  return (fits256 && tiles256 >= 192 && nk >= 8) ? (fp8 ? 2 : X2V_GEMM256_BF16_KERNEL) : 1;
+  return (fits256 && tiles256 >= 192 && nk >= 8) ? (fp8 ? 2 : 3) : 1;
 }
 
 // variant: 0 = choose by shape, 1 = 128x128 kernel, 2 = 256x256 ping-pong kernel, 3 = 256x256 single-stream kernel (bf16) in the form the
@@ -349,8 +340,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
       const int fp8_continuous_mode = gemm_fp8_continuous_switch();
       const bool unblocked = gb.a_kpb <= 0 && gb.y_cbw <= 0;
       const bool fp8_continuous_on = fp8_continuous_mode >= 2 || (fp8_continuous_mode == 1 && unblocked);
-      const int64_t y_cols_span = gb.y_cbw > 0 ? (int64_t)((N - 1) / gb.y_cbw) * gb.y_cbs + gb.y_cbw : (int64_t)N;
-      const bool can_c = gemm256c_ok(nk, gb) && N % 256 == 0 && (255 * ldy + y_cols_span) * 2 < 0x80000000ll && (resid == nullptr || (ldr == ldy && gb.y_cbw <= 0));
+      const bool can_c = continuous_ok(nk, N, ldy, ldr, resid, gb);
       if (form == 5 && !can_c) {
         set_error("gemm_fp8: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns and resid with y's row stride (nk=%d, N=%d)", nk, N);
         return X2V_E_SHAPE;
@@ -361,8 +351,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
   }
   if constexpr (!FP8) {
     // the single-stream kernel addresses its output (and residual) tile with 32-bit offsets from the tile's first row
-    const int64_t y_cols_span = gb.y_cbw > 0 ? (int64_t)((N - 1) / gb.y_cbw) * gb.y_cbs + gb.y_cbw : (int64_t)N;
-    const bool y32 = (255 * ldy + y_cols_span) * 2 < (1ll << 32) && (resid == nullptr || (255 * ldr + (int64_t)N) * 2 < (1ll << 32));
+    const bool y32 = (255 * ldy + y_cols_span(N, gb)) * 2 < (1ll << 32) && (resid == nullptr || (255 * ldr + (int64_t)N) * 2 < (1ll << 32));
     if (chosen == 3 && !y32) {
       if (kind == 3) {
         set_error("gemm: output leading dimension / block stride too large for the single-stream 256x256 kernel (32-bit tile addressing)");
@@ -371,10 +360,8 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
       return dispatch_epi<FP8>(epilogue, x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, 2 | (gm_tiles << 8), st, gb);
     }
     if (chosen == 3) {
-      // continuous form: its epilogue addresses the output / residual tile through descriptors of 2^31 bytes (offset 0x80000000 is the "no such
-      // row" mark), so the tile spans must stay below that
       const bool continuous_on = gemm_continuous_switch() != 0;
-      const bool can_c = gemm256c_ok(nk, gb) && N % 256 == 0 && (255 * ldy + y_cols_span) * 2 < 0x80000000ll && (resid == nullptr || (ldr == ldy && gb.y_cbw <= 0));  // residual tile addressed with y's offsets
+      const bool can_c = continuous_ok(nk, N, ldy, ldr, resid, gb);
       if (form == 5 && !can_c) {
         set_error("gemm: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns and resid with y's row stride (nk=%d, N=%d)", nk, N);
         return X2V_E_SHAPE;
@@ -386,17 +373,20 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
   if (chosen == 2) {
     return gemm256_dispatch<FP8>(epilogue, x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, gm_tiles, st, gb);
   }
-  switch (epilogue) {
-    case X2V_EPI_NONE: return launch_gemm<FP8, X2V_EPI_NONE>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, st, gb);
-    case X2V_EPI_GELU_TANH: return launch_gemm<FP8, X2V_EPI_GELU_TANH>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, st, gb);
-    case X2V_EPI_SILU: return launch_gemm<FP8, X2V_EPI_SILU>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, st, gb);
-    case X2V_EPI_RESIDUAL: return launch_gemm<FP8, X2V_EPI_RESIDUAL>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, st, gb);
-    default: set_error("gemm: unknown epilogue %d", epilogue); return X2V_E_ARG;
-  }
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm<FP8, decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, st, gb);
+  });
 }
 
-static int check_common(const char* who, const void* y, int64_t ldy, int64_t M, int N, const void* bias, int epilogue, const void* resid, int64_t ldr,
-                        const void* gate) {
+// The argument checks of the four public bf16 / fp8 entries.  `row`: elements of an x row that are contiguous (K, or x's K block); `N`: columns of y
+// that are (N, or y's N block); `blocked`: the wording of the _blocked entries.
+static int check_operands(const char* who, bool fp8, bool blocked, const void* x, int64_t ldx, int row, const float* sx, const void* w, int64_t ldw, const float* sw,
+                          const void* y, int64_t ldy, int64_t M, int N, int K, const void* bias, int epilogue, const void* resid, int64_t ldr, const void* gate) {
+  const int kmult = fp8 ? 128 : GB_K, ldmult = fp8 ? 16 : 8;
+  X2V_REQUIRE(x && w && y && (!fp8 || (sx && sw)), X2V_E_ARG, "%s: null pointer", who);
+  X2V_REQUIRE(K > 0 && K % kmult == 0, X2V_E_SHAPE, "%s: K=%d must be a positive multiple of %d", who, K, kmult);
+  X2V_REQUIRE(ldx % ldmult == 0 && ldw % ldmult == 0 && aligned16(x) && aligned16(w) && (!fp8 || aligned16(sw)), X2V_E_ALIGN, "%s: operand rows must be 16-byte aligned", who);
+  X2V_REQUIRE(ldx >= row && ldw >= K, X2V_E_SHAPE, blocked ? "%s: leading dimension smaller than the row" : "%s: leading dimension smaller than K", who);
   X2V_REQUIRE(M >= 0 && N > 0, X2V_E_SHAPE, "%s: bad shape M=%lld N=%d", who, (long long)M, N);
   X2V_REQUIRE(N % 8 == 0, X2V_E_SHAPE, "%s: N=%d must be a multiple of 8", who, N);
   X2V_REQUIRE(ldy % 8 == 0 && ldy >= N && aligned16(y), X2V_E_ALIGN, "%s: output rows must be 16-byte aligned", who);
@@ -411,11 +401,7 @@ static int check_common(const char* who, const void* y, int64_t ldy, int64_t M, 
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16_variant(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K,
                              int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
-  X2V_REQUIRE(x && w && y, X2V_E_ARG, "gemm_bf16: null pointer");
-  X2V_REQUIRE(K > 0 && K % GB_K == 0, X2V_E_SHAPE, "gemm_bf16: K=%d must be a positive multiple of %d", K, GB_K);
-  X2V_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && aligned16(x) && aligned16(w), X2V_E_ALIGN, "gemm_bf16: operand rows must be 16-byte aligned");
-  X2V_REQUIRE(ldx >= K && ldw >= K, X2V_E_SHAPE, "gemm_bf16: leading dimension smaller than K");
-  int rc = check_common("gemm_bf16", y, ldy, M, N, bias, epilogue, resid, ldr, gate);
+  int rc = check_operands("gemm_bf16", false, false, x, ldx, K, nullptr, w, ldw, nullptr, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
   if (rc != X2V_OK) return rc;
   if (M == 0) return X2V_OK;
   return dispatch_epi<false>(epilogue, x, ldx * 2, w, ldw * 2, bias, y, ldy, M, N, K / GB_K, resid, ldr, gate, nullptr, nullptr, variant, (hipStream_t)stream);
@@ -442,11 +428,7 @@ static int check_blocking(const char* who, int K_bytes_per_row, int64_t x_kblock
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16_blocked(const void* x, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const void* w, int64_t ldw,
                                                                             const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N,
                                                                             int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
-  X2V_REQUIRE(x && w && y, X2V_E_ARG, "gemm_bf16_blocked: null pointer");
-  X2V_REQUIRE(K > 0 && K % GB_K == 0, X2V_E_SHAPE, "gemm_bf16_blocked: K=%d must be a positive multiple of %d", K, GB_K);
-  X2V_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && aligned16(x) && aligned16(w), X2V_E_ALIGN, "gemm_bf16_blocked: operand rows must be 16-byte aligned");
-  X2V_REQUIRE(ldx >= (x_kblock > 0 ? x_kblock : K) && ldw >= K, X2V_E_SHAPE, "gemm_bf16_blocked: leading dimension smaller than the row");
-  int rc = check_common("gemm_bf16_blocked", y, ldy, M, y_nblock > 0 ? y_nblock : N, bias, epilogue, resid, ldr, gate);
+  int rc = check_operands("gemm_bf16_blocked", false, true, x, ldx, (x_kblock > 0 ? x_kblock : K), nullptr, w, ldw, nullptr, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
   if (rc != X2V_OK) return rc;
   GemmBlocking gb;
   rc = check_blocking("gemm_bf16_blocked", K * 2, (int64_t)x_kblock * 2, x_kblock_stride * 2, N, y_nblock, y_nblock_stride, epilogue, &gb);
@@ -459,11 +441,7 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_blocked(const
                                                                            int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock,
                                                                            int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr,
                                                                            const void* gate, void* stream) {
-  X2V_REQUIRE(xq && wq && y && sx && sw, X2V_E_ARG, "gemm_fp8_blocked: null pointer");
-  X2V_REQUIRE(K > 0 && K % 128 == 0, X2V_E_SHAPE, "gemm_fp8_blocked: K=%d must be a positive multiple of 128", K);
-  X2V_REQUIRE(ldx % 16 == 0 && ldw % 16 == 0 && aligned16(xq) && aligned16(wq) && aligned16(sw), X2V_E_ALIGN, "gemm_fp8_blocked: operand rows must be 16-byte aligned");
-  X2V_REQUIRE(ldx >= (x_kblock > 0 ? x_kblock : K) && ldw >= K, X2V_E_SHAPE, "gemm_fp8_blocked: leading dimension smaller than the row");
-  int rc = check_common("gemm_fp8_blocked", y, ldy, M, y_nblock > 0 ? y_nblock : N, bias, epilogue, resid, ldr, gate);
+  int rc = check_operands("gemm_fp8_blocked", true, true, xq, ldx, (x_kblock > 0 ? x_kblock : K), sx, wq, ldw, sw, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
   if (rc != X2V_OK) return rc;
   GemmBlocking gb;
   rc = check_blocking("gemm_fp8_blocked", K, x_kblock, x_kblock_stride, N, y_nblock, y_nblock_stride, epilogue, &gb);
@@ -479,11 +457,7 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16(const void* 
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
                             int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
-  X2V_REQUIRE(xq && wq && y && sx && sw, X2V_E_ARG, "gemm_fp8: null pointer");
-  X2V_REQUIRE(K > 0 && K % 128 == 0, X2V_E_SHAPE, "gemm_fp8: K=%d must be a positive multiple of 128", K);
-  X2V_REQUIRE(ldx % 16 == 0 && ldw % 16 == 0 && aligned16(xq) && aligned16(wq) && aligned16(sw), X2V_E_ALIGN, "gemm_fp8: operand rows must be 16-byte aligned");
-  X2V_REQUIRE(ldx >= K && ldw >= K, X2V_E_SHAPE, "gemm_fp8: leading dimension smaller than K");
-  int rc = check_common("gemm_fp8", y, ldy, M, N, bias, epilogue, resid, ldr, gate);
+  int rc = check_operands("gemm_fp8", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
   if (rc != X2V_OK) return rc;
   if (M == 0) return X2V_OK;
   return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
@@ -517,6 +491,6 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_kernel_choice(int
   // bit 8: variant 0 runs the CONTINUOUS-pipeline form of that tile family (gemm256c.hip / gemm256c8.hip) for a row-major y (ldy == N) and a
   // residual of y's stride — what the parity tests and the bench line record
   const bool cont = (tile == 3 && !fp8 && gemm_continuous_switch() != 0) || (tile == 2 && fp8 && gemm_fp8_continuous_switch() >= 1);
-  const bool can_c = gemm256c_ok(nk, GemmBlocking()) && N % 256 == 0 && (255 * (int64_t)N + N) * 2 < 0x80000000ll;
+  const bool can_c = continuous_ok(nk, N, N, N, nullptr, GemmBlocking());
   return tile | ((cont && can_c) ? 0x100 : 0);
 }

@@ -28,7 +28,7 @@
 //   * M / N tails: the buffer descriptors are based at the tile's first row with num_records covering only its valid
 //     rows, so rows past M (or N) read as zero through the hardware bounds check; stores are masked.
 //   * epilogue through LDS ([256][528 B]) so global stores are 16 bytes per lane, 512 bytes contiguous per row.
-#include "x2v_common.h"
+#include "gemm256_pipe.h"
 
 namespace x2v {
 
@@ -456,24 +456,16 @@ static int launch_gemm256(const void* x, int64_t ldx_bytes, const void* w, int64
 template <bool FP8>
 int gemm256_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                      const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  switch (epilogue) {
-    case X2V_EPI_NONE: return launch_gemm256<FP8, X2V_EPI_NONE>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
-    case X2V_EPI_GELU_TANH: return launch_gemm256<FP8, X2V_EPI_GELU_TANH>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
-    case X2V_EPI_SILU: return launch_gemm256<FP8, X2V_EPI_SILU>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
-    case X2V_EPI_RESIDUAL: return launch_gemm256<FP8, X2V_EPI_RESIDUAL>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
-    default: set_error("gemm: unknown epilogue %d", epilogue); return X2V_E_ARG;
-  }
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256<FP8, decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
+  });
 }
 // MXFP8 (mx.hip): e4m3 operands with e8m0 block-scale tables [K/128][rows][4]; alpha = device pointer or null.  Arguments validated by the caller.
 int gemm256_mx_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
-  switch (epilogue) {
-    case X2V_EPI_NONE: return launch_gemm256<true, X2V_EPI_NONE, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, alpha, nullptr, 4, st, sa, sb);
-    case X2V_EPI_GELU_TANH: return launch_gemm256<true, X2V_EPI_GELU_TANH, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, alpha, nullptr, 4, st, sa, sb);
-    case X2V_EPI_SILU: return launch_gemm256<true, X2V_EPI_SILU, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, alpha, nullptr, 4, st, sa, sb);
-    case X2V_EPI_RESIDUAL: return launch_gemm256<true, X2V_EPI_RESIDUAL, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, resid, ldr, gate, alpha, nullptr, 4, st, sa, sb);
-    default: set_error("gemm_mxfp8: unknown epilogue %d", epilogue); return X2V_E_ARG;
-  }
+  return with_epilogue("gemm_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256<true, decltype(epi)::value, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+  });
 }
 
 template int gemm256_dispatch<false>(int, const void*, int64_t, const void*, int64_t, const void*, void*, int64_t, int64_t, int, int, const void*, int64_t,

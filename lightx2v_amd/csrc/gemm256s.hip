@@ -12,67 +12,23 @@
 //   * no hand-off: the wave's own stream is {MFMA | at most one ds_read_b128 or one LDS-DMA issue} per slot, 128 slots per 64-wide K tile,
 //     pinned with sched_barrier; fragments for k-step s+1 are read while k-step s multiplies (0.5 KiB of LDS per MFMA-equivalent);
 //   * two LDS stages of {W tile | x tile} (2 x 64 KiB, [256 rows][128 B] images with the chunk ^= (row>>1)&7 swizzle on the DMA source
-//     offset and on the fragment address).  Per K tile t (stage t&1), in slots:
-//        0..30   reads of k-step 1 of tile t        36  lgkmcnt(0) + s_barrier "stage t&1 is free"
-//        37..    LDS-DMA of tile t+2 into stage t&1, one piece every 7th slot, running on into the first slots of tile t+1
-//        94      counted vmcnt + s_barrier "tile t+1 has landed everywhere"      96..126  reads of k-step 0 of tile t+1
-//     (slot constants below).
+//     offset and on the fragment address); which slot of a K tile carries which read, DMA piece, wait and barrier: the slot plan in
+//     gemm256_pipe.h, which this file shares with the continuous kernels gemm256c.hip / gemm256c8.hip;
 //   * M / N tails, K-blocked x and N-blocked y (GemmBlocking), the LDS-staged epilogue: as gemm256.hip.
 // AUDIT after every edit (the accumulator half is invisible to the compiler): `hipcc -S` must show .vgpr_spill_count 0,
 // .private_segment_fixed_size 0 and no v_accvgpr_* / a[..] operand outside ;;#ASMSTART / ;;#ASMEND.
-#include <type_traits>
-
-#include "x2v_common.h"
+#include "gemm256_pipe.h"
 
 namespace x2v {
+using namespace pipe;
 
-constexpr int S_M = 256, S_N = 256;
-constexpr int S_OP_BYTES = 256 * 128;          // one operand tile of one stage
-constexpr int S_STAGE_BYTES = 2 * S_OP_BYTES;  // W tile | x tile
-constexpr int S_EPI_LD = 528;                  // bytes per epilogue row (256 bf16 + 16 pad)
-constexpr int S_LDS_BYTES = 256 * S_EPI_LD;    // 135168 >= 2 stages (131072)
-// MFMA slots of a K tile (128 per wave) at which the other instructions of the stream sit:
-//   S_LATE0 + S_STEP i    the last 16 - S_EARLY LDS-DMA pieces of tile t+1            0, 2, .., 30   fragment reads of k-step 1
-//   S_FREE                lgkmcnt(0) + barrier "this tile's stage is free"
-//   S_FREE + 1 + S_STEP i the first S_EARLY pieces of tile t+2
-//   S_READY               vmcnt + barrier "tile t+1 has landed"                      S_READY + 2, + 4, ..   fragment reads of k-step 0 of t+1
-// The 64 pieces a workgroup moves per tile keep the CU's texture path busy for half of the tile's 2048 cycles: issued in a burst
-// (all four waves right behind the first barrier) they queue up and stall the issuing waves; spread over the tile they cost ~nothing.
-constexpr int S_STEP = 7, S_FREE = 36, S_READY = 94, S_LATE0 = 3;
-constexpr int S_EARLY = (127 - S_FREE - 1) / S_STEP + 1 < 16 ? (127 - S_FREE - 1) / S_STEP + 1 : 16;  // pieces of tile t+2 that fit behind S_FREE
-static_assert(S_LATE0 + (16 - S_EARLY - 1) * S_STEP < S_FREE && S_READY + 2 + 30 <= 127, "slot plan");
+constexpr int S_EPI_LD = 528;                // bytes per epilogue row (256 bf16 + 16 pad)
+constexpr int S_LDS_BYTES = 256 * S_EPI_LD;  // 135168 >= the two stages (LDS_BYTES)
+static_assert(S_LDS_BYTES >= LDS_BYTES, "the epilogue's staging area covers the two stages");
 
-typedef __attribute__((address_space(3))) void* s_lds_ptr_t;
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-// Every asm statement that touches the accumulator half names ALL of it as clobbered: hipcc must never park a value of its own in an AGPR
-// across one of them.  (Round 3: with only a0 / a255 named once at kernel entry, the register allocator put part of the hoisted residual
-// chunks into a1..a8 — `v_accvgpr_write` outside the asm blocks — and two accumulator tiles per wave were overwritten: the AUDIT rule in
-// the header exists for exactly this.)
-#define S_AGPRS "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143", "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255"
-
-template <int B, int E, class F>
-__device__ __forceinline__ void s_for(F&& f) {  // f(integral_constant<int, i>) for i = B .. E-1, fully unrolled with constant indices
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    s_for<B + 1, E>(f);
-  }
-}
-
-// accumulator tile I (= x block * 8 + W block) is a[4 I : 4 I + 3]
-template <int I>
-__device__ __forceinline__ void s_mfma(const bf16x8_t& wf, const bf16x8_t& xf) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(wf), "v"(xf), "i"(4 * I), "i"(4 * I + 3) : S_AGPRS);
-}
 template <int R>
 __device__ __forceinline__ void s_acc_zero() {
-  asm volatile("v_accvgpr_write_b32 a[%c0], 0" ::"i"(R) : S_AGPRS);
-}
-template <int R>
-__device__ __forceinline__ float s_acc_read() {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(R) : S_AGPRS);
-  return x;
+  asm volatile("v_accvgpr_write_b32 a[%c0], 0" ::"i"(R) : X2V_AGPRS);
 }
 
 // VT (epilogue NONE only): y is written TRANSPOSED per head and 64-token block — V^T [N/128][ldy/64][128][64], the operand layout of the
@@ -86,28 +42,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const unsigned short* __restrict__ gate, int ntm, int ntn, int gm_tiles, GemmBlocking gb) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  asm volatile("" ::: S_AGPRS);  // the accumulator half belongs to the asm statements of this kernel
+  claim_accumulators();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 1, wc = wid & 1;
   const int r16 = lane & 15, g16 = lane >> 4;
 
-  // ---- tile coordinates: XCD chunking + grouped ordering (gm_tiles m-tiles x all n-tiles per group), as gemm256.hip
+  // ---- this workgroup's tile: XCD chunking + grouped ordering
   const unsigned nblk = (unsigned)ntm * (unsigned)ntn;
   const unsigned v = xcd_remap(blockIdx.x, nblk);
-  const unsigned GM = (unsigned)gm_tiles;
-  const unsigned per_group = GM * (unsigned)ntn;
-  const unsigned group = v / per_group, in_g = v % per_group;
-  const unsigned first_m = group * GM;
-  const unsigned gsz = min((unsigned)ntm - first_m, GM);
-  const int tm = (int)(first_m + in_g % gsz), tn = (int)(in_g / gsz);
-  const int64_t m0 = (int64_t)tm * S_M;
-  const int n0 = tn * S_N;
+  X2V_PIPE_COORDS()
+  int tm, tn;
+  coords(v, tm, tn);
+  const int64_t m0 = (int64_t)tm * TILE;
+  const int n0 = tn * TILE;
 
-  // ---- buffer descriptors over this tile's valid rows: rows past M / N read as zero through the bounds check
+  // ---- buffer descriptors over this tile's valid rows: rows past M / N read as zero through the bounds check.  Written out here, and the K-block
+  //      wrap computed in place below: through gemm256_pipe.h's `operands` lambda / with the wrap hoisted into a named value as in the continuous
+  //      kernels, this kernel allocates one SGPR less and ~700 instructions of its stream move (tools/isa_diff.py).
   const unsigned row_bytes = (unsigned)nk * 128u;
-  const int rows_a = (int)min((int64_t)S_M, M - m0), rows_w = min(S_N, N - n0);
+  const int rows_a = (int)min((int64_t)TILE, M - m0), rows_w = min(TILE, N - n0);
   const int a_kpb = gb.a_kpb > 0 && gb.a_kpb < nk ? gb.a_kpb : nk;  // K tiles per K block of x (GemmBlocking)
   const unsigned a_span = a_kpb < nk ? (unsigned)((nk - 1) / a_kpb) * gb.a_cbs + (unsigned)a_kpb * 128u : row_bytes;
   const __amdgpu_buffer_rsrc_t ra =
@@ -117,69 +72,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // byte offsets of x's K tiles t+1 and t+2 within a row (K-blocked x: GemmBlocking) and the index of tile t+2 within its K block
   unsigned ak1 = 0, ak2 = 0;
   int akc2 = 0;
-#define S_AK_NEXT(OFF_, CNT_) { if (++(CNT_) == a_kpb) { (CNT_) = 0; (OFF_) += gb.a_cbs - (unsigned)(a_kpb - 1) * 128u; } else (OFF_) += 128u; }
+#define S_AK_NEXT(OFF_, CNT_) X2V_PIPE_NEXT_KA(OFF_, CNT_, X2V_PIPE_A_WRAP())
   S_AK_NEXT(ak2, akc2)
   ak1 = ak2;
   S_AK_NEXT(ak2, akc2)
 
-  // ---- LDS-DMA: wave `wid` stages rows [64 wid, 64 wid + 64) of both operand tiles as 8 pieces of 8 rows (1 KiB, lane-linear in LDS).
-  //      Piece i = 2 j + par: row 64 wid + 16 j + 8 par + (lane>>3); its swizzle (row>>1)&7 = ((lane>>4) + 4 par) & 7 does not depend on j,
-  //      so two per-lane offsets per operand serve all pieces and 16 j rows travel in the scalar offset with the K offset.
-  unsigned a_voff[2], w_voff[2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par) {
-    const int r = wid * 64 + par * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ (((lane >> 4) + 4 * par) & 7);
-    a_voff[par] = (unsigned)(r * lda_bytes) + (unsigned)(c << 4);
-    w_voff[par] = (unsigned)(r * ldw_bytes) + (unsigned)(c << 4);
-  }
-  const unsigned a_j = (unsigned)(16 * lda_bytes), w_j = (unsigned)(16 * ldw_bytes);
-  // piece P_ in 0..15 of a K tile: 0..7 = W pieces, 8..15 = x pieces
-#define S_DMA(P_, STAGE_, KW_, KA_)                                                                                                     \
-  {                                                                                                                                    \
-    constexpr int i_ = (P_) & 7;                                                                                                       \
-    if constexpr ((P_) < 8)                                                                                                            \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (s_lds_ptr_t)(smem + (STAGE_) * S_STAGE_BYTES + wid * 8192 + i_ * 1024), 16, w_voff[i_ & 1],         \
-                                               (unsigned)(KW_) + (unsigned)(i_ >> 1) * w_j, 0, 0);                                     \
-    else                                                                                                                               \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (s_lds_ptr_t)(smem + (STAGE_) * S_STAGE_BYTES + S_OP_BYTES + wid * 8192 + i_ * 1024), 16,            \
-                                               a_voff[i_ & 1], (unsigned)(KA_) + (unsigned)(i_ >> 1) * a_j, 0, 0);                     \
-  }
-
-  // ---- fragment addresses (16x16x32: row r16 of a 16-row block, 16-byte chunk ks*4 + g16), block offsets travel as immediates
-  int rd_x[2], rd_w[2];
-  {
-    const int swz = (r16 >> 1) & 7;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int o = r16 * 128 + ((((ks << 2) | g16) ^ swz) << 4);
-      rd_x[ks] = o + S_OP_BYTES + wr * 16384;
-      rd_w[ks] = o + wc * 16384;
-    }
-  }
-  bf16x8_t fx[2][8], fw[2][8];
-  // fragment R_ in 0..15 of k-step KS_ of the tile in stage STAGE_; order x0, W0..W7, x1..x7 (the first MFMA of a k-step needs x0 and W0)
-#define S_READ(R_, STAGE_, KS_)                                                                                                         \
-  {                                                                                                                                    \
-    if constexpr ((R_) == 0) fx[KS_][0] = *reinterpret_cast<const bf16x8_t*>(smem + (STAGE_) * S_STAGE_BYTES + rd_x[KS_]);              \
-    else if constexpr ((R_) <= 8) fw[KS_][(R_) - 1] = *reinterpret_cast<const bf16x8_t*>(smem + (STAGE_) * S_STAGE_BYTES + ((R_) - 1) * 2048 + rd_w[KS_]); \
-    else fx[KS_][(R_) - 8] = *reinterpret_cast<const bf16x8_t*>(smem + (STAGE_) * S_STAGE_BYTES + ((R_) - 8) * 2048 + rd_x[KS_]);       \
-  }
+  X2V_PIPE_DMA_OFFSETS()
+  X2V_PIPE_BF16_FRAGMENTS()
+#define S_DMA(P_, STAGE_, KW_, KA_) X2V_PIPE_DMA_AT(P_, STAGE_, ra, rw, KW_, KA_)
 #define S_SB() __builtin_amdgcn_sched_barrier(0)
 
-  s_for<0, 256>([&](auto rc) { s_acc_zero<decltype(rc)::value>(); });
+  static_for<0, 256>([&](auto rc) { s_acc_zero<decltype(rc)::value>(); });
 
-  // ---- prologue: tile 0 and the first S_EARLY pieces of tile 1 in flight, tile 0 landed, k-step 0 of tile 0 in registers
-  s_for<0, 16>([&](auto pc) { S_DMA(decltype(pc)::value, 0, 0u, 0u) });
+  // ---- prologue: tile 0 and the first EARLY pieces of tile 1 in flight, tile 0 landed, k-step 0 of tile 0 in registers
+  static_for<0, 16>([&](auto pc) { S_DMA(decltype(pc)::value, 0, 0u, 0u) });
   if (nk > 1) {
-    s_for<0, S_EARLY>([&](auto pc) { S_DMA(decltype(pc)::value, 1, 128u, ak1) });
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S_EARLY) : "memory");
+    static_for<0, EARLY>([&](auto pc) { S_DMA(decltype(pc)::value, 1, 128u, ak1) });
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EARLY) : "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __builtin_amdgcn_s_barrier();
   S_SB();
-  s_for<0, 16>([&](auto rc) { S_READ(decltype(rc)::value, 0, 0) });
+  static_for<0, 16>([&](auto rc) { X2V_PIPE_BF16_READ(decltype(rc)::value, 0, 0) });
   S_SB();
 
   // One K tile.  ST = its stage; CHK = 0: steady state (tiles t+1 and t+2 exist), 1: tail (run-time tests).
@@ -188,34 +103,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr bool CHK = decltype(chkc)::value != 0;
     const bool has1 = CHK ? (t + 1 < nk) : true, has2 = CHK ? (t + 2 < nk) : true;
     const unsigned kw1 = (unsigned)(t + 1) * 128u, kw2 = (unsigned)(t + 2) * 128u;
-    s_for<0, 128>([&](auto nc) {
+    static_for<0, 128>([&](auto nc) {
       constexpr int n = decltype(nc)::value, ks = n >> 6, xb = (n >> 3) & 7, wb = n & 7;
-      if constexpr (VT) s_mfma<xb * 8 + wb>(fx[ks][xb], fw[ks][wb]);
-      else s_mfma<xb * 8 + wb>(fw[ks][wb], fx[ks][xb]);
-      if constexpr (n < 32 && (n & 1) == 0) S_READ(n >> 1, ST, 1)  // k-step 1 of this tile
-      // the last 16 - S_EARLY pieces of tile t+1 (its stage was freed by the previous tile's first barrier)
-      if constexpr (n >= S_LATE0 && (n - S_LATE0) % S_STEP == 0 && (n - S_LATE0) / S_STEP < 16 - S_EARLY) {
-        if (has1) S_DMA(S_EARLY + (n - S_LATE0) / S_STEP, ST ^ 1, kw1, ak1)
+      if constexpr (VT) mfma_bf16<xb * 8 + wb>(fx[ks][xb], fw[ks][wb]);
+      else mfma_bf16<xb * 8 + wb>(fw[ks][wb], fx[ks][xb]);
+      if constexpr (n < 32 && (n & 1) == 0) X2V_PIPE_BF16_READ(n >> 1, ST, 1)  // k-step 1 of this tile
+      // the last 16 - EARLY pieces of tile t+1 (its stage was freed by the previous tile's first barrier)
+      if constexpr (late_slot(n)) {
+        if (has1) S_DMA(EARLY + (n - LATE0) / STEP, ST ^ 1, kw1, ak1)
       }
-      if constexpr (n == S_FREE) {
+      if constexpr (n == FREE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every fragment of this tile is in registers: the stage may be overwritten
         __builtin_amdgcn_s_barrier();
       }
-      // the first S_EARLY pieces of tile t+2 into this tile's stage
-      if constexpr (n > S_FREE && (n - S_FREE - 1) % S_STEP == 0 && (n - S_FREE - 1) / S_STEP < S_EARLY) {
-        if (has2) S_DMA((n - S_FREE - 1) / S_STEP, ST, kw2, ak2)
+      // the first EARLY pieces of tile t+2 into this tile's stage
+      if constexpr (dma_slot(n)) {
+        if (has2) S_DMA((n - FREE - 1) / STEP, ST, kw2, ak2)
       }
-      if constexpr (n == S_READY) {
+      if constexpr (n == READY) {
         if (has1) {
           // tile t+1 has landed; the pieces of tile t+2 issued so far in this tile may stay in flight
-          constexpr int newer = (S_READY - S_FREE - 1) / S_STEP + 1 < S_EARLY ? (S_READY - S_FREE - 1) / S_STEP + 1 : S_EARLY;
-          if (has2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(newer) : "memory");
+          if (has2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NEWER) : "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
         }
       }
-      if constexpr (n > S_READY + 1 && (n & 1) == 0) {
-        if (has1) S_READ((n - S_READY - 2) >> 1, ST ^ 1, 0)  // k-step 0 of the next tile
+      if constexpr (n > READY + 1 && (n & 1) == 0) {
+        if (has1) X2V_PIPE_BF16_READ((n - READY - 2) >> 1, ST ^ 1, 0)  // k-step 0 of the next tile
       }
       S_SB();
     });
@@ -234,7 +148,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     tile(c0{}, c1{}, t);
     if (t + 1 < nk) tile(c1{}, c1{}, t + 1);
   }
-#undef S_READ
 #undef S_DMA
 #undef S_AK_NEXT
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");  // the last MFMAs' results before the accumulator reads below
@@ -250,12 +163,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int gn = n0 + wc * 128 + wb * 16 + r16;
       bvt[wb] = (bias != nullptr && gn < N) ? bf2f(bias[gn]) : 0.f;
     }
-    s_for<0, 64>([&](auto ic) {
+    static_for<0, 64>([&](auto ic) {
       constexpr int I = decltype(ic)::value, xb = I >> 3, wb = I & 7;
       const int nl = wc * 128 + wb * 16 + r16, ml = wr * 128 + xb * 16 + 4 * g16;
       uint2 pk;
-      pk.x = pack_bf2(s_acc_read<4 * I + 0>() + bvt[wb], s_acc_read<4 * I + 1>() + bvt[wb]);
-      pk.y = pack_bf2(s_acc_read<4 * I + 2>() + bvt[wb], s_acc_read<4 * I + 3>() + bvt[wb]);
+      pk.x = pack_bf2(acc_read<4 * I + 0>() + bvt[wb], acc_read<4 * I + 1>() + bvt[wb]);
+      pk.y = pack_bf2(acc_read<4 * I + 2>() + bvt[wb], acc_read<4 * I + 3>() + bvt[wb]);
       *reinterpret_cast<uint2*>(smem + nl * S_EPI_LD + ml * 2) = pk;
     });
     __syncthreads();
@@ -315,10 +228,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       bv[wb] = make_uint2(0u, 0u);
       if (bias != nullptr) bv[wb] = *reinterpret_cast<const uint2*>(bias + gn);
     }
-    s_for<0, 64>([&](auto ic) {
+    static_for<0, 64>([&](auto ic) {
       constexpr int I = decltype(ic)::value, xb = I >> 3, wb = I & 7;
       const int ml = wr * 128 + xb * 16 + r16, nl = wc * 128 + wb * 16 + 4 * g16;
-      float vv[4] = {s_acc_read<4 * I + 0>(), s_acc_read<4 * I + 1>(), s_acc_read<4 * I + 2>(), s_acc_read<4 * I + 3>()};
+      float vv[4] = {acc_read<4 * I + 0>(), acc_read<4 * I + 1>(), acc_read<4 * I + 2>(), acc_read<4 * I + 3>()};
       vv[0] += bf_lo(bv[wb].x);
       vv[1] += bf_hi(bv[wb].x);
       vv[2] += bf_lo(bv[wb].y);
@@ -376,7 +289,7 @@ template <int EPI, bool VT = false>
 static int launch_gemm256s(const void* x, int64_t ldx_bytes, const void* w, int64_t ldw_bytes, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                            const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb) {
   if (gm_tiles <= 0) gm_tiles = 4;
-  const int ntm = (int)((M + S_M - 1) / S_M), ntn = (N + S_N - 1) / S_N;
+  const int ntm = (int)((M + TILE - 1) / TILE), ntn = (N + TILE - 1) / TILE;
   int rc = ensure_dynamic_lds((const void*)gemm256s_kernel<EPI, VT>, S_LDS_BYTES, "gemm256s attr");
   if (rc != X2V_OK) return rc;
   hipLaunchKernelGGL((gemm256s_kernel<EPI, VT>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), S_LDS_BYTES, st, (const char*)x, ldx_bytes, (const char*)w, ldw_bytes,
@@ -388,13 +301,9 @@ static int launch_gemm256s(const void* x, int64_t ldx_bytes, const void* w, int6
 // Called by gemm.hip's dispatcher (arguments already validated there; ld*_bytes < 16 MiB checked by the caller).
 int gemm256s_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                       const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  switch (epilogue) {
-    case X2V_EPI_NONE: return launch_gemm256s<X2V_EPI_NONE>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, gm_tiles, st, gb);
-    case X2V_EPI_GELU_TANH: return launch_gemm256s<X2V_EPI_GELU_TANH>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, gm_tiles, st, gb);
-    case X2V_EPI_SILU: return launch_gemm256s<X2V_EPI_SILU>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, nullptr, 0, nullptr, gm_tiles, st, gb);
-    case X2V_EPI_RESIDUAL: return launch_gemm256s<X2V_EPI_RESIDUAL>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, gm_tiles, st, gb);
-    default: set_error("gemm: unknown epilogue %d", epilogue); return X2V_E_ARG;
-  }
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256s<decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, gm_tiles, st, gb);
+  });
 }
 
 // V^T-producing form (x2v_gemm_bf16_vt): y = V^T [N/128][ldvt/64][128][64]; `ldvt` travels in the ldy argument

@@ -738,7 +738,7 @@ __global__ __launch_bounds__(512, 2) void vae_conv16h_kernel(const _Float16* __r
 #pragma unroll 1
   for (int st = 0; st < nsteps; ++st) {
     // One trip.  This loop is what is left of the step loop's unroll-by-3 form (round 5's two-k-steps-ahead build); written without it hipcc orders the
-    // step loop's scalar address instructions differently.  Kept so that the loop stays instruction-identical to the measured one (tools/vae_conv_isa_diff.py).
+    // step loop's scalar address instructions differently.  Kept so that the loop stays instruction-identical to the measured one (tools/isa_diff.py).
 #pragma unroll
     for (int once = 0; once < 1; ++once) {
     int nslab = slab, ntap = tap9 + 1;
