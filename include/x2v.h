@@ -442,6 +442,45 @@ int x2v_softmax_rows_causal_f32(float* s, int64_t ld, int64_t M, int N, float sc
 int x2v_blend_axis_f32(const float* a, float* b, int64_t outer, int na, int nb, int64_t inner, int64_t a_outer_stride, int64_t b_outer_stride, int extent,
                        void* stream);
 
+/* ---- CLIP ViT-H/14 image tower (fp16): the producer of i2v's clip_encoder_out (runners/wan/wan_runner.py:191-198; the reference runs the tower in fp16,
+ * :71-72).  fp16 tensors are raw IEEE half bits; LayerNorm parameters are fp32. ---- */
+
+/* epilogues of x2v_gemm_f16 */
+#define X2V_EPI16_NONE 0     /* y = fp16(acc + bias) */
+#define X2V_EPI16_GELU_ERF 1 /* y = fp16(gelu_erf(acc + bias))                       (nn.GELU() of AttentionBlock.mlp, xlm_roberta/model.py:150-153) */
+#define X2V_EPI16_RESIDUAL 2 /* y = fp16(resid + fp16(acc + bias)); y may alias resid (x + self.attn(...) / x + self.mlp(...), model.py:162-163) */
+
+/* y[M,N] = epi(x[M,K] . W[N,K]^T + bias) in fp16 with fp32 accumulation, for M of a few hundred rows (257 tokens per image) — replaces the nn.Linear calls
+ * of SelfAttention.to_qkv / proj (model.py:82,89), AttentionBlock.mlp (:150-153) and, on the patch-major operand of x2v_clip_preprocess_f16 with
+ * bias = NULL, VisionTransformer.patch_embedding (:253,278).  K % 32 == 0 (pad both operands with zero columns), N % 4 == 0; bias may be NULL.
+ * Each output value is reduced in k order whatever M: rows of a batch equal the rows computed alone, bit for bit. */
+int x2v_gemm_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K, int epilogue,
+                 const void* resid, int64_t ldr, void* stream);
+
+/* The tile x2v_gemm_f16 launches for (M, N): 0 = 128 x 64, 1 = 64 x 64, 2 = 64 x 32, 3 = 64 x 16 (host arithmetic; no reference counterpart). */
+int x2v_gemm_f16_tile_choice(int64_t M, int N);
+
+/* out[b*S + i, h*80 : h*80 + 80] = softmax(scale * q_i . k_j) v_j over the S keys of image b, non-causal, head dim 80 — replaces
+ * attention(q, k, v, attention_type="torch_sdpa") of SelfAttention.forward (model.py:82-86).  qkv is the to_qkv output [batch*S, >= 3*H*80] read in
+ * place: q | k | v at columns 0, H*80, 2*H*80 of a row.  1 <= S <= 272; scale = 0 means 80^-1/2.  fp32 softmax statistics. */
+int x2v_attn_f16_d80(const void* qkv, int64_t ld, void* out, int64_t ldo, int batch, int S, int num_heads, float scale, void* stream);
+
+/* y[M,D] = fp16(LN(x; w, b, eps)) with fp32 statistics and fp32 w, b — replaces LayerNorm.forward (model.py:47-49: super().forward(x.float()).type_as(x)).
+ * D % 8 == 0, D <= 2048. */
+int x2v_layernorm_f16(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int64_t M, int D, float eps, void* stream);
+
+/* y[b*tokens + t] = LN(fp16(tok + pos[t])), tok = cls for t = 0 and patches[b*(tokens-1) + t - 1] otherwise — replaces the concatenation with
+ * cls_embedding, the pos_embedding add and pre_norm of VisionTransformer.forward (model.py:278-287).  pos is [tokens, D] fp16 contiguous. */
+int x2v_clip_embed_f16(const void* patches, int64_t ldp, const void* cls, const void* pos, const float* w, const float* b, void* y, int64_t ldy, int batch,
+                       int tokens, int D, float eps, void* stream);
+
+/* One image [3, H, W] fp32 in [-1, 1] (read in place: channel / row strides in elements, unit column stride) -> the patch-major fp16 operand
+ * out[(image_size/patch)^2, ld_out] of the patch-embedding GEMM, column c*patch^2 + py*patch + px, columns 3*patch^2 .. ld_out zeroed — replaces
+ * F.interpolate(size=(224, 224), mode="bicubic", align_corners=False), mul_(0.5).add_(0.5) and Normalize(mean, std) of CLIPModel.visual (model.py:440-442,
+ * constants :379-380) and the unfold that Conv2d(kernel = stride = patch) implies. */
+int x2v_clip_preprocess_f16(const float* img, int64_t c_stride, int64_t row_stride, int H, int W, void* out, int64_t ld_out, int image_size, int patch,
+                            float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+
 /* Box calibration (measurement plumbing; no reference counterpart): runs bare v_mfma_f32_16x16x32_bf16 loops (operands in registers,
  * 8 waves per CU, every CU) for `milliseconds` on `stream` and returns in *tflops what the board sustained over the second half of that time.
  * bench.py calls it before and after its timed region so that a roofline fraction measured on one box can be compared with another's

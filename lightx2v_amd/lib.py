@@ -80,6 +80,12 @@ PROTOTYPES = {
     "x2v_vae_prep_ex_f32": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i64, _i64, _c_void_p],
     "x2v_vae_conv_s2_f16": [_c_void_p, _i64, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_vae_video_prep": [_c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
+    "x2v_gemm_f16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
+    "x2v_gemm_f16_tile_choice": [_i64, _i32],
+    "x2v_attn_f16_d80": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
+    "x2v_layernorm_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _f32, _c_void_p],
+    "x2v_clip_embed_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
+    "x2v_clip_preprocess_f16": [_c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _c_void_p],
     "x2v_vae_replicate_border_f32": [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
@@ -994,3 +1000,100 @@ def distill_step(cond, uncond, guide, latents, noise, sigma, one_minus_next, sig
         "distill_step",
     )
     return noise_pred, out
+
+
+# ---- CLIP image tower (fp16; csrc/clip.hip) ---------------------------------------------------------------------------------------------------------
+EPI16_NONE, EPI16_GELU_ERF, EPI16_RESIDUAL = 0, 1, 2
+
+
+def _f16rows(t, name):
+    if t.dtype != torch.float16:
+        raise X2VError(f"{name}: expected float16, got {t.dtype}")
+    return _row2d(t, name)
+
+
+def gemm_f16(x, weight_nk, bias=None, epilogue=EPI16_NONE, resid=None, out=None):
+    """x2v_gemm_f16: y[M, N] = epi(x[M, K] . W[N, K]^T + bias) in fp16 (fp32 accumulation); K % 32 == 0, N % 4 == 0."""
+    x, w = _f16rows(x, "gemm_f16 x"), _f16rows(weight_nk, "gemm_f16 weight")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise X2VError(f"gemm_f16: x {tuple(x.shape)} and weight {tuple(w.shape)} disagree on K")
+    bias = _vec(bias, "gemm_f16 bias", N, dtype=torch.float16)
+    out = torch.empty((M, N), dtype=torch.float16, device=x.device) if out is None else _f16rows(out, "gemm_f16 out")
+    if out.shape != (M, N) or (resid is not None and _f16rows(resid, "gemm_f16 resid").shape != (M, N)):
+        raise X2VError(f"gemm_f16: out / resid must be [{M}, {N}]")
+    init()
+    _check(_lib.x2v_gemm_f16(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, epilogue, _p(resid), 0 if resid is None else resid.stride(0),
+                             _stream()), "gemm_f16")
+    return out
+
+
+def gemm_f16_tile_choice(M, N):
+    """x2v_gemm_f16_tile_choice: (rows, columns) of the workgroup tile x2v_gemm_f16 launches for (M, N) — host arithmetic."""
+    t = _lib.x2v_gemm_f16_tile_choice(M, N)
+    _check(min(t, 0), "gemm_f16_tile_choice")
+    return ((128, 64), (64, 64), (64, 32), (64, 16))[t]
+
+
+def attention_f16_d80(qkv, batch, num_heads, out=None, scale=0.0):
+    """x2v_attn_f16_d80 on the to_qkv output qkv [batch * S, 3 * num_heads * 80] (read in place) -> [batch * S, num_heads * 80] fp16."""
+    qkv = _f16rows(qkv, "attention_f16_d80 qkv")
+    D = num_heads * 80
+    if qkv.shape[1] != 3 * D or batch < 1 or qkv.shape[0] % batch:
+        raise X2VError(f"attention_f16_d80: qkv {tuple(qkv.shape)} is not [batch * S, 3 * {num_heads} * 80] for batch {batch}")
+    out = torch.empty((qkv.shape[0], D), dtype=torch.float16, device=qkv.device) if out is None else _f16rows(out, "attention_f16_d80 out")
+    if out.shape != (qkv.shape[0], D):
+        raise X2VError(f"attention_f16_d80: out must be [{qkv.shape[0]}, {D}]")
+    init()
+    _check(_lib.x2v_attn_f16_d80(_p(qkv), qkv.stride(0), _p(out), out.stride(0), batch, qkv.shape[0] // batch, num_heads, scale, _stream()), "attention_f16_d80")
+    return out
+
+
+def layernorm_f16(x, weight, bias, eps=1e-5, out=None):
+    """x2v_layernorm_f16: fp16 rows, fp32 weight / bias and statistics, one rounding."""
+    x = _f16rows(x, "layernorm_f16 x")
+    D = x.shape[1]
+    weight, bias = _vec(weight, "layernorm_f16 weight", D, dtype=torch.float32), _vec(bias, "layernorm_f16 bias", D, dtype=torch.float32)
+    if weight is None or bias is None:
+        raise X2VError("layernorm_f16: weight and bias are required")
+    out = torch.empty_like(x) if out is None else _f16rows(out, "layernorm_f16 out")
+    if out.shape != x.shape:
+        raise X2VError(f"layernorm_f16: out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    init()
+    _check(_lib.x2v_layernorm_f16(_p(x), x.stride(0), _p(weight), _p(bias), _p(out), out.stride(0), x.shape[0], D, eps, _stream()), "layernorm_f16")
+    return out
+
+
+def clip_embed(patches, cls, pos, weight, bias, batch, eps=1e-5, out=None):
+    """x2v_clip_embed_f16: patches [batch * (T - 1), D] fp16, cls [D], pos [T, D] fp16, pre_norm weight / bias fp32 -> [batch * T, D] fp16."""
+    patches = _f16rows(patches, "clip_embed patches")
+    D = patches.shape[1]
+    if batch < 1 or patches.shape[0] == 0 or patches.shape[0] % batch:
+        raise X2VError(f"clip_embed: patches {tuple(patches.shape)} is not [batch * (T - 1), D] for batch {batch}")
+    T = patches.shape[0] // batch + 1
+    cls, pos = _vec(cls, "clip_embed cls", D, dtype=torch.float16), _vec(pos, "clip_embed pos", T * D, dtype=torch.float16)
+    weight, bias = _vec(weight, "clip_embed weight", D, dtype=torch.float32), _vec(bias, "clip_embed bias", D, dtype=torch.float32)
+    out = torch.empty((batch * T, D), dtype=torch.float16, device=patches.device) if out is None else _f16rows(out, "clip_embed out")
+    if out.shape != (batch * T, D):
+        raise X2VError(f"clip_embed: out must be [{batch * T}, {D}], got {tuple(out.shape)}")
+    init()
+    _check(_lib.x2v_clip_embed_f16(_p(patches), patches.stride(0), _p(cls), _p(pos), _p(weight), _p(bias), _p(out), out.stride(0), batch, T, D, eps, _stream()), "clip_embed")
+    return out
+
+
+def clip_preprocess(img, out, image_size, patch, mean, std):
+    """x2v_clip_preprocess_f16: img [3, H, W] fp32 in [-1, 1] (unit W stride, read in place) -> out [(image_size / patch)^2, >= 3 patch^2] fp16 rows.
+    The kernel writes whole rows of the row stride (columns beyond 3 patch^2 are zeroed), so `out` must own its rows: no column-sliced view."""
+    _f32c(img, "clip_preprocess img")
+    if img.dim() != 3 or img.shape[0] != 3 or img.stride(2) != 1:
+        raise X2VError(f"clip_preprocess: expected a [3, H, W] image with unit W stride, got {tuple(img.shape)} strides {img.stride()}")
+    out = _f16rows(out, "clip_preprocess out")
+    if out.shape[0] != (image_size // patch) ** 2:
+        raise X2VError(f"clip_preprocess: out has {out.shape[0]} rows, expected {(image_size // patch) ** 2}")
+    if out.shape[1] != out.stride(0):
+        raise X2VError(f"clip_preprocess: out is a column slice ({out.shape[1]} of a row stride of {out.stride(0)}); the kernel zero-fills every row up to its stride")
+    init()
+    _check(_lib.x2v_clip_preprocess_f16(_p(img), img.stride(0), img.stride(1), img.shape[1], img.shape[2], _p(out), out.stride(0), image_size, patch, *[float(m) for m in mean],
+                                        *[float(s) for s in std], _stream()), "clip_preprocess")
+    return out

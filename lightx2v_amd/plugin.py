@@ -4,6 +4,7 @@
     x2v.register_into_reference()          # adds our keys to lightx2v.utils.registry_factory registries
     x2v.use_fused_wan_block()              # optional: WanModel picks the fused HIP block driver
     x2v.use_fused_hunyuan_block()          # optional: HunyuanModel picks the fused HIP double / single block driver
+    x2v.use_hip_clip_encoder()             # optional: WanRunner.load_image_encoder builds the HIP CLIP image tower (i2v)
 
 After that an unchanged LightX2V config selects the HIP path by string:
     "mm_config": {"mm_type": "Hip-bf16"}   (or "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip")
@@ -60,6 +61,17 @@ def use_fused_wan_block():
             self.transformer_infer_class = wan.WanTransformerInfer
 
     ref_model.WanModel._init_infer_class = _init_infer_class
+
+
+def use_hip_clip_encoder():
+    """Make WanRunner.load_image_encoder (runners/wan/wan_runner.py:52-84) build this package's CLIPModel: the runner module binds the class by name
+    (`from ...xlm_roberta.model import CLIPModel`, :21) and calls it with the reference's keyword arguments, and `run_image_encoder` (:193-202) only
+    calls `.visual(videos, config)`.  `clip_quantized: true` configs raise NotImplementedError (the q_linear.py classes are not built)."""
+    from lightx2v.models.runners.wan import wan_runner
+
+    from . import clip
+
+    wan_runner.CLIPModel = clip.CLIPModel
 
 
 def use_fused_hunyuan_block():

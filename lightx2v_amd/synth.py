@@ -137,6 +137,53 @@ def synth_i2v_inputs(dims, target_shape, seed=42, device="cpu"):
     return {"clip_encoder_out": clip.to(device), "vae_encode_out": y.to(device)}
 
 
+# CLIP ViT-H/14 image tower (input_encoders/hf/xlm_roberta/model.py:388-408 clip_xlm_roberta_vit_h_14) and a 3-block, 2-head tower of the same head dim 80
+CLIP_DIMS = {
+    "clip-vit-h-14": dict(dim=1280, heads=16, layers=32, mlp_ratio=4, image_size=224, patch_size=14, out_dim=1024),
+    "clip-tiny": dict(dim=160, heads=2, layers=3, mlp_ratio=4, image_size=224, patch_size=14, out_dim=1024),
+}
+CLIP_MEAN = [0.48145466, 0.4578275, 0.40821073]  # model.py:379-380
+CLIP_STD = [0.26862954, 0.26130258, 0.27577711]
+
+
+def synth_clip_weights(dims, seed=0, device="cpu", dtype=torch.float16):
+    """The visual half of the published CLIP checkpoint (names and shapes of XLMRobertaCLIP.state_dict() without `textual.*`: VisionTransformer.__init__,
+    model.py:251-272, plus `log_scale` :362).  Linear weights are drawn at std 1 / sqrt(fan_in), second linears of a block (proj, mlp.2) at half of it, so
+    that the residual stream of a 31-block fp16 forward stays O(10): far from the fp16 range (checked on the CPU by tests/test_clip_host.py)."""
+    D, L, P = dims["dim"], dims["layers"], dims["patch_size"]
+    F, T = int(D * dims["mlp_ratio"]), (dims["image_size"] // P) ** 2 + 1
+    gen = torch.Generator().manual_seed(seed + 4242)
+    wd = {}
+
+    def rn(shape, std, dt=dtype):
+        return _randn(shape, std, gen, device, dt)
+
+    def lin(name, n, k, gain=1.0):
+        wd[f"{name}.weight"] = rn((n, k), gain / math.sqrt(k))
+        wd[f"{name}.bias"] = rn((n,), 0.02)
+
+    def ln(name):
+        wd[f"{name}.weight"] = (1.0 + rn((D,), 0.05, torch.float32)).to(dtype)
+        wd[f"{name}.bias"] = rn((D,), 0.02)
+
+    wd["log_scale"] = torch.tensor(math.log(1 / 0.07), dtype=torch.float32, device=device)
+    wd["visual.cls_embedding"] = rn((1, 1, D), 1.0)
+    wd["visual.pos_embedding"] = rn((1, T, D), 0.5)
+    wd["visual.patch_embedding.weight"] = rn((D, 3, P, P), 1.0 / math.sqrt(3 * P * P))
+    ln("visual.pre_norm")
+    for i in range(L):
+        p = f"visual.transformer.{i}"
+        ln(f"{p}.norm1")
+        lin(f"{p}.attn.to_qkv", 3 * D, D)
+        lin(f"{p}.attn.proj", D, D, 0.5)
+        ln(f"{p}.norm2")
+        lin(f"{p}.mlp.0", F, D)
+        lin(f"{p}.mlp.2", D, F, 0.5)
+    ln("visual.post_norm")
+    wd["visual.head"] = rn((D, dims["out_dim"]), 1.0 / math.sqrt(D))
+    return wd
+
+
 def synth_inputs(dims, target_shape, seed=42, device="cpu"):
     """Latents exactly as the reference seeds them (wan/scheduler.py:25-28,54-63: randn(target_shape),
     fp32, seed 42) but always drawn from the CPU stream so CPU oracle and GPU path see identical noise

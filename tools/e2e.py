@@ -3,7 +3,8 @@
 final latents — the quantity BASELINE.json's north star asks for next to the per-step number ("end-to-end wall-clock and frames/sec").
 Synthetic weights and inputs of the named shape (no text encoder: its output is an input here, as in bench.py).  One JSON line.
     python tools/e2e.py [--workload wan14b_720px81f] [--steps 50] [--fp8|--mxfp8] [--distill] [--teacache T]
-    python tools/e2e.py --i2v --image PATH | --encode   (image → VAE encode → loop → decode; --encode: a seeded synthetic 720p image)
+    python tools/e2e.py --i2v --image PATH | --encode   (image → CLIP tower + VAE encode → loop → decode; --encode: a seeded synthetic 720p image;
+                                                         --clip-ckpt PATH: the CLIP checkpoint instead of seeded synthetic tower weights)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/e2e.py --gpus N ...
         (N GPUs of one node: Ulysses sequence parallel denoise loop over RCCL + the halo-split `decode_dist` VAE decode)"""
 import argparse
@@ -30,7 +31,8 @@ def main():
     ap.add_argument("--vae32", action="store_true", help="VAE convolutions on the fp32 matrix instruction (default: hi/lo fp16 split, fp32-grade)")
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--image", default=None, help="i2v: build vae_encode_out from this image (PIL) with the HIP VAE encoder, timed as vae_encode_s")
+    ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
+    ap.add_argument("--clip-ckpt", default=None, help="i2v with --image / --encode: CLIP checkpoint (.pth / .safetensors) for the HIP image tower (default: seeded synthetic weights)")
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
     a = ap.parse_args()
     from lightx2v_amd import launch
@@ -83,8 +85,9 @@ def main():
         vae_sd = {**vae_sd, **synth.synth_wan_vae_encoder_weights(dim=96, seed=0)}
     decoder = vae.WanVAE(vae_sd, dim=96, conv16=(True if a.vae16 else False if a.vae32 else "split"), parallel=world > 1)
     if encode:
-        from lightx2v_amd import vae_enc
+        from lightx2v_amd import clip, vae_enc
 
+        clip_model = clip.CLIPModel(torch.float16, "cuda", a.clip_ckpt or synth.synth_clip_weights(synth.CLIP_DIMS["clip-vit-h-14"], seed=0, device="cuda"), False, None, None)
         _, _, th, tw = wl["target_shape"]
         if a.image is not None:  # TF.to_tensor(img).sub_(0.5).div_(0.5) of run_vae_encoder (wan_runner.py:205)
             import numpy as np
@@ -97,6 +100,7 @@ def main():
         if vae_enc.i2v_latent_hw(img.shape[1], img.shape[2], 8 * th, 8 * tw, cfg["vae_stride"], cfg["patch_size"]) != (th, tw):
             raise SystemExit(f"--image: a {img.shape[2]}x{img.shape[1]} image gives another latent grid than the workload's {tw}x{th} (use the workload's aspect ratio)")
         vae_enc.run_vae_encoder(decoder, img, **enc_args)  # warm-up: allocates the encoder's buffers
+        clip.run_image_encoder(clip_model, img.cuda())
     # warm-up outside the clock: one step on a scratch scheduler state (allocator pools, lazy tables) and a short decode
     sch.step_pre(0)
     model.infer(inputs)
@@ -114,7 +118,11 @@ def main():
 
     fence()
     te = time.perf_counter()
-    if encode:
+    tc = te
+    if encode:  # WanRunner.run_image_encoder → run_vae_encoder (wan_runner.py:191-248)
+        inputs["image_encoder_output"]["clip_encoder_out"] = clip.run_image_encoder(clip_model, img.cuda())
+        fence()
+        tc = time.perf_counter()
         inputs["image_encoder_output"]["vae_encode_out"] = vae_enc.run_vae_encoder(decoder, img, **enc_args)[0]
         fence()
     t0 = time.perf_counter()
@@ -130,8 +138,10 @@ def main():
            "teacache_thresh": a.teacache, "vae_conv_operands": "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
            "frames": frames, "video_shape": list(video.shape), "fps_denoise_only": frames / (t1 - t0), "fps_with_vae": frames / (t2 - t0),
            "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}
-    if encode:  # the conditioning latents were built from an image here; the CLIP output stays a seeded stand-in
-        rec.update(vae_encode_s=t0 - te, total_with_encode_s=t2 - te, conditioning=f"image {os.path.basename(a.image)}" if a.image else "seeded synthetic image")
+    if encode:  # both conditioning tensors were built from the image here
+        rec.update(clip_encode_s=tc - te, vae_encode_s=t0 - tc, total_with_encode_s=t2 - te,
+                   conditioning=(f"image {os.path.basename(a.image)}" if a.image else "seeded synthetic image") + ": clip_encoder_out from the HIP CLIP tower (" +
+                   (f"checkpoint {os.path.basename(a.clip_ckpt)}" if a.clip_ckpt else "seeded synthetic weights") + "), vae_encode_out from the HIP VAE encoder")
     if a.teacache > 0:
         rec_c, rec_u = list(getattr(sch, "caching_records", [])), list(getattr(sch, "caching_records_2", []))
         rec["teacache_forwards_computed"] = int(sum(bool(v) for v in rec_c + rec_u))
