@@ -572,8 +572,12 @@ __global__ __launch_bounds__(256) void gate_residual_kernel(unsigned short* __re
 template <int ACT>
 __device__ __forceinline__ float act_f(float x) {
   if constexpr (ACT == X2V_EPI_GELU_TANH) return gelu_tanh_f(x);
-  else if constexpr (ACT == X2V_ACT_GELU_ERF) return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f));  // torch gelu(approximate="none") on a bf16 tensor: fp32 math
-  else return silu_f(x);
+  else if constexpr (ACT == X2V_ACT_GELU_ERF) {
+    // torch gelu(approximate="none") on a bf16 tensor: fp32 math.  Below -3 the sum 1 + erf cancels (at x < -5.9 to exactly 0, where the
+    // function is still ~ -1e-9): there 1 + erf(z) is taken as erfc(-z), which keeps its relative accuracy down the whole tail
+    if (x < -3.0f) return 0.5f * x * erfcf(-x * 0.7071067811865476f);
+    return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f));
+  } else return silu_f(x);
 }
 
 template <int ACT>
@@ -658,6 +662,10 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(unsigned short* __re
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       v[j] = (ROUND == X2V_ROUND_REF) ? rbf(rbf(v[j] * rs) * wv[j]) : (scale_here ? v[j] * rs * wv[j] * oscale : rbf(v[j] * rs * wv[j]));
+  } else if (ROUND != X2V_ROUND_REF && tok >= l_rope) {
+    // no norm, no rotation: the store below is the row's one rounding, so the scale goes in front of it (oscale is 1 for k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] *= oscale;
   }
   if (tok < l_rope) {
     float c[8], sn[8];
