@@ -148,6 +148,16 @@ int x2v_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const 
 int x2v_gemm_bf16_variant(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K,
                           int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream);
 
+/* x2v_gemm_bf16_variant with X2V_EPI_RESIDUAL and a ROW PERIOD of the residual: resid holds resid_period rows (ld = ldr) and output row r is
+ * y[r] = bf16(resid[r mod resid_period] + bf16(bf16(acc + bias) * gate)) — the bytes the plain entry writes when given resid repeated M / resid_period
+ * times, without the copy.  It is the fan-out of a CFG step whose two forwards share everything up to block 0's cross-attention (same latents, same
+ * timestep: transformer_infer.py runs that front twice): one residual stream of S rows, a stacked cross-attention output of 2 S rows.
+ * resid_period = 0: the plain entry.  y must not overlap resid (X2V_E_ARG); M and resid_period below 2^31.  Every kernel takes every period, except
+ * that the continuous forms (variant 5) need a multiple of 8 that is >= 256 with the residual inside 2^31 bytes — variant 0 / 3 then take the
+ * one-tile-per-workgroup form, variant 5 answers X2V_E_SHAPE.  Error texts start with the entry's name, as everywhere. */
+int x2v_gemm_bf16_resid_period(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K,
+                               const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant, void* stream);
+
 /* x2v_gemm_bf16 on block-strided operands — what lets the Ulysses exchange buffers (attentions/distributed/comm/all2all.py:6-89) be GEMM
  * operands in place instead of being transposed by copies (all2all.py:29-33, :70-75,87):
  *   x K-blocked (x_kblock > 0): element k of row m at x[(k / x_kblock) * x_kblock_stride + m * ldx + k % x_kblock] — the received
@@ -263,6 +273,11 @@ int x2v_gemm_fp8(const void* xq, int64_t ldx, const float* sx, const void* wq, i
 int x2v_gemm_fp8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
                          int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant,
                          void* stream);
+
+/* x2v_gemm_fp8_variant with X2V_EPI_RESIDUAL and a row period of the residual (see x2v_gemm_bf16_resid_period). */
+int x2v_gemm_fp8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                              int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant,
+                              void* stream);
 
 /* x2v_gemm_fp8 on block-strided operands (see x2v_gemm_bf16_blocked; x_kblock in e4m3 elements = bytes, a multiple of 128; sx stays [M]). */
 int x2v_gemm_fp8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq, int64_t ldw, const float* sw,

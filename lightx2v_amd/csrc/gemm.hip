@@ -229,10 +229,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
     const int gn = n0 + cc * 8;
     if (gm < M && gn < N) {
       uint4 o = *reinterpret_cast<const uint4*>(smem + row * G_EPI_LD + cc * 16);
-      if (EPI == X2V_EPI_RESIDUAL) {
+      if (epi_is_residual(EPI)) {
         float yv[8], xv[8], ov[8];
         unpack8(o, yv);
-        unpack8(*reinterpret_cast<const uint4*>(resid + gm * ldr + gn), xv);
+        int64_t rrow = gm;
+        if constexpr (EPI == EPI_RESIDUAL_PERIODIC) rrow = (int64_t)((unsigned)gm % (unsigned)gb.r_period);  // row period (M < 2^31: dispatcher)
+        unpack8(*reinterpret_cast<const uint4*>(resid + rrow * ldr + gn), xv);
         if (gate != nullptr) {
           float gv[8];
           unpack8(*reinterpret_cast<const uint4*>(gate + gn), gv);
@@ -288,9 +290,14 @@ static int64_t y_cols_span(int N, const GemmBlocking& gb) { return gb.y_cbw > 0 
 // of K tiles >= 4 (every output tile starts in LDS stage 0), N a multiple of 256 and y blocks that are whole multiples of a wave's 128 columns (a
 // wave's columns are contiguous), a residual tile addressed with y's offsets, and tile spans below 2^31 bytes — the epilogue addresses the output /
 // residual tile through descriptors of 2^31 bytes (offset 0x80000000 is its "no such row" mark).
+// A residual row period (GemmBlocking::r_period): their residual loads cover 4 (bf16) / 8 (w8a8) rows of a tile each and take the row of the first
+// one, wrapped once: the period is a multiple of 8, at least a tile's 256 rows, and its rows lie within 2^31 bytes of resid.
+static bool resid_period_continuous_ok(int N, int64_t ldr, const GemmBlocking& gb) {
+  return gb.r_period <= 0 || (gb.r_period % 8 == 0 && gb.r_period >= 256 && ((int64_t)gb.r_period * ldr + N) * 2 < 0x80000000ll);
+}
 static bool continuous_ok(int nk, int N, int64_t ldy, int64_t ldr, const void* resid, const GemmBlocking& gb) {
   return nk >= 4 && (nk & 1) == 0 && (gb.y_cbw <= 0 || gb.y_cbw % 128 == 0) && N % 256 == 0 && (255 * ldy + y_cols_span(N, gb)) * 2 < 0x80000000ll &&
-         (resid == nullptr || (ldr == ldy && gb.y_cbw <= 0));
+         (resid == nullptr || (ldr == ldy && gb.y_cbw <= 0 && resid_period_continuous_ok(N, ldr, gb)));
 }
 
 int x2v::gemm_continuous_switch() {
@@ -342,7 +349,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
       const bool fp8_continuous_on = fp8_continuous_mode >= 2 || (fp8_continuous_mode == 1 && unblocked);
       const bool can_c = continuous_ok(nk, N, ldy, ldr, resid, gb);
       if (form == 5 && !can_c) {
-        set_error("gemm_fp8: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns and resid with y's row stride (nk=%d, N=%d)", nk, N);
+        set_error("gemm_fp8: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns, resid with y's row stride and a residual row period that is a multiple of 8 and >= 256 (nk=%d, N=%d, resid_period=%d)", nk, N, gb.r_period);
         return X2V_E_SHAPE;
       }
       if (form == 5 || (kind == 0 && fp8_continuous_on && can_c))
@@ -351,7 +358,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
   }
   if constexpr (!FP8) {
     // the single-stream kernel addresses its output (and residual) tile with 32-bit offsets from the tile's first row
-    const bool y32 = (255 * ldy + y_cols_span(N, gb)) * 2 < (1ll << 32) && (resid == nullptr || (255 * ldr + (int64_t)N) * 2 < (1ll << 32));
+    const bool y32 = (255 * ldy + y_cols_span(N, gb)) * 2 < (1ll << 32) && (resid == nullptr || ((gb.r_period > 0 ? gb.r_period - 1 : 255) * ldr + (int64_t)N) * 2 < (1ll << 32));  // a periodic residual is addressed from its first row
     if (chosen == 3 && !y32) {
       if (kind == 3) {
         set_error("gemm: output leading dimension / block stride too large for the single-stream 256x256 kernel (32-bit tile addressing)");
@@ -363,7 +370,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
       const bool continuous_on = gemm_continuous_switch() != 0;
       const bool can_c = continuous_ok(nk, N, ldy, ldr, resid, gb);
       if (form == 5 && !can_c) {
-        set_error("gemm: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns and resid with y's row stride (nk=%d, N=%d)", nk, N);
+        set_error("gemm: the continuous single-stream kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns, resid with y's row stride and a residual row period that is a multiple of 8 and >= 256 (nk=%d, N=%d, resid_period=%d)", nk, N, gb.r_period);
         return X2V_E_SHAPE;
       }
       if (form == 5 || (form == 0 && continuous_on && can_c)) return gemm256c_dispatch(epilogue, x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, gm_tiles, st, gb);
@@ -373,7 +380,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
   if (chosen == 2) {
     return gemm256_dispatch<FP8>(epilogue, x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, gm_tiles, st, gb);
   }
-  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm<FP8, decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, st, gb);
   });
 }
@@ -448,6 +455,41 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_blocked(const
   if (rc != X2V_OK) return rc;
   if (M == 0) return X2V_OK;
   return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
+}
+
+// The residual row period of the _resid_period entries: resid holds `period` rows, output row r combines with row r mod period.  y is written while
+// other workgroups still read resid, so the two may not overlap (the plain epilogue's y == resid is row r onto row r; here it is not).
+static int check_resid_period(const char* who, const void* y, int64_t ldy, int64_t M, int N, const void* resid, int64_t ldr, int64_t period, GemmBlocking* gb) {
+  X2V_REQUIRE(period >= 0 && period < (1ll << 31) && M < (1ll << 31), X2V_E_SHAPE, "%s: resid_period=%lld and M=%lld must be below 2^31", who, (long long)period, (long long)M);
+  if (period == 0 || M == 0) return X2V_OK;
+  const char *y0 = (const char*)y, *y1 = y0 + ((M - 1) * ldy + N) * 2, *r0 = (const char*)resid, *r1 = r0 + ((period - 1) * ldr + N) * 2;
+  X2V_REQUIRE(y1 <= r0 || r1 <= y0, X2V_E_ARG, "%s: with a resid_period, y must not overlap resid", who);
+  gb->r_period = (int)period;
+  return X2V_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16_resid_period(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M,
+                                                                                 int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant,
+                                                                                 void* stream) {
+  int rc = check_operands("gemm_bf16_resid_period", false, false, x, ldx, K, nullptr, w, ldw, nullptr, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_resid_period("gemm_bf16_resid_period", y, ldy, M, N, resid, ldr, resid_period, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  return dispatch_epi<false>(X2V_EPI_RESIDUAL, x, ldx * 2, w, ldw * 2, bias, y, ldy, M, N, K / GB_K, resid, ldr, gate, nullptr, nullptr, variant, (hipStream_t)stream, gb);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias,
+                                                                                void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period,
+                                                                                const void* gate, int variant, void* stream) {
+  int rc = check_operands("gemm_fp8_resid_period", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_resid_period("gemm_fp8_resid_period", y, ldy, M, N, resid, ldr, resid_period, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  return dispatch_epi<true>(X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K,

@@ -412,10 +412,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
       // N-blocked y (GemmBlocking): column block gn / y_cbw starts y_cbs elements after the previous one
       const int64_t ycol = gb.y_cbw > 0 ? (int64_t)(gn / gb.y_cbw) * gb.y_cbs + gn % gb.y_cbw : gn;
       uint4 o = *reinterpret_cast<const uint4*>(smem + row * T_EPI_LD + cc * 16);
-      if (EPI == X2V_EPI_RESIDUAL) {
+      if (epi_is_residual(EPI)) {
         float yv[8], xv[8], ov[8];
         unpack8(o, yv);
-        unpack8(*reinterpret_cast<const uint4*>(resid + gmr * ldr + gn), xv);
+        int64_t rrow = gmr;
+        if constexpr (EPI == EPI_RESIDUAL_PERIODIC) rrow = (int64_t)((unsigned)gmr % (unsigned)gb.r_period);  // row period (M < 2^31: dispatcher)
+        unpack8(*reinterpret_cast<const uint4*>(resid + rrow * ldr + gn), xv);
         if (gate != nullptr) {
           float gv[8];
           unpack8(*reinterpret_cast<const uint4*>(gate + gn), gv);
@@ -456,7 +458,7 @@ static int launch_gemm256(const void* x, int64_t ldx_bytes, const void* w, int64
 template <bool FP8>
 int gemm256_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                      const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm256<FP8, decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
   });
 }

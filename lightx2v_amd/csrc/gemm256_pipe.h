@@ -38,6 +38,25 @@ int with_epilogue(const char* who, int epilogue, const void* resid, int64_t ldr,
     default: set_error("%s: unknown epilogue %d", who, epilogue); return X2V_E_ARG;
   }
 }
+// the same for the kernels that take a residual row period (GemmBlocking::r_period > 0: the EPI_RESIDUAL_PERIODIC instantiation)
+template <class F>
+int with_epilogue(const char* who, int epilogue, const void* resid, int64_t ldr, const void* gate, const GemmBlocking& gb, F&& f) {
+  if (epilogue == X2V_EPI_RESIDUAL && gb.r_period > 0) return f(std::integral_constant<int, EPI_RESIDUAL_PERIODIC>{}, resid, ldr, gate);
+  return with_epilogue(who, epilogue, resid, ldr, gate, f);
+}
+
+// ---- residual row period, device side (EPI_RESIDUAL_PERIODIC; the caller guarantees M < 2^31 and that resid's period rows do not overlap y).
+//      The residual is addressed from ITS first row (not from the tile's, as the plain epilogue does): the residual row of a tile's first row
+//      once per tile, then per access either the row of any local row (the kernels that load one row per lane) ..
+__device__ __forceinline__ unsigned resid_tile_row(int64_t m0, int period) { return (unsigned)m0 % (unsigned)period; }
+__device__ __forceinline__ unsigned resid_row(unsigned tile_row, int local, int period) { return (tile_row + (unsigned)local) % (unsigned)period; }
+//      .. or, in the continuous kernels, the first row of a chunk of CH rows that one load instruction covers (wave-uniform: a scalar add, compare
+//      and select).  Tiles, wave parts and chunks start at multiples of CH and the period is a multiple of CH (dispatcher: resid_period_continuous_ok),
+//      so a chunk never straddles the period; the period is >= 256, so `base` (< period) + a local row (< 128) wraps at most once.
+__device__ __forceinline__ unsigned resid_chunk_row(unsigned base, int local, int period) {
+  const unsigned r = base + (unsigned)local;
+  return r >= (unsigned)period ? r - (unsigned)period : r;
+}
 
 // ---- host: grid of a persistent kernel = one workgroup per CU, CUs rounded down to whole XCD octets (the kernels' chunking counts on it), or one
 //      workgroup per output tile when there are fewer tiles than that

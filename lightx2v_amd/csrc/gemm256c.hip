@@ -81,7 +81,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   unsigned s_bias = 0u;   // the wave's first column in bias / gate, bytes
   int rows_left = 0;      // valid rows of the current tile below row wr*128 + (lane>>4): phase-B row 16 xb + 4 i of the lane exists iff it is < rows_left
   const unsigned y_row = (unsigned)(ldy * 2);  // one row of y (and of the residual: ldr == ldy, y row-major — dispatcher), bytes
-  constexpr bool RES = EPI == X2V_EPI_RESIDUAL;
+  constexpr bool RES = epi_is_residual(EPI);
+  constexpr bool RP = EPI == EPI_RESIDUAL_PERIODIC;  // output row r combines with residual row r mod gb.r_period
+  // RP: the residual is addressed from ITS first row; a chunk's row travels in the scalar offset, the lane keeps its row within the chunk
+  const unsigned lane_off_r = (unsigned)(l4 * ldy * 2) + (unsigned)(16 * c16);
+  unsigned s_rrow = 0u;  // RP: residual row of the wave's first row of the current tile (wave-uniform)
   constexpr int NXLOAD = RES ? 8 + 1 + 4 : 8;  // bias (8) [+ gate (1) + the residual chunks of x block 0 (4)]
 
   // Set up the epilogue addressing of output tile (tm, tn).  Runs when the tile becomes current (scalar instructions + one vector subtract).
@@ -98,7 +102,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     s_col = col * 2u;
     s_bias = (unsigned)gn0 * 2u;
     rows_left = (int)min((int64_t)TILE, M - m0) - wr * 128 - l4;
-    if constexpr (RES) {
+    if constexpr (RP) {
+      r_res = __builtin_amdgcn_make_buffer_rsrc((void*)resid, 0, 0x80000000u, 0x00020000);
+      s_rrow = resid_tile_row(m0 + wr * 128, gb.r_period);
+      r_gate = __builtin_amdgcn_make_buffer_rsrc((void*)gate, 0, gate != nullptr ? (unsigned)N * 2u : 0u, 0x00020000);
+    } else if constexpr (RES) {
       r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(resid + m0 * ldy), 0, 0x80000000u, 0x00020000);
       r_gate = __builtin_amdgcn_make_buffer_rsrc((void*)gate, 0, gate != nullptr ? (unsigned)N * 2u : 0u, 0x00020000);
     }
@@ -106,6 +114,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto row_voff = [&](int row16) { return row16 < rows_left ? lane_off : 0x80000000u; };  // phase-B vector offset of local row `row16` (= 16 xb + 4 i)
   auto res_load = [&](auto xbc, auto ic) {  // residual chunk i of x block xb: the 16 bytes phase B's store i of that block will overwrite
     constexpr int xb = decltype(xbc)::value, i = decltype(ic)::value;
+    if constexpr (RP)  // the chunk's 4 rows lie on one side of the period (gemm256_pipe.h: resid_chunk_row)
+      e_res[xb & 1][i] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_res, 16 * xb + 4 * i < rows_left ? lane_off_r : 0x80000000u,
+                                                                                           s_col + resid_chunk_row(s_rrow, 16 * xb + 4 * i, gb.r_period) * y_row, 0));
+    else
     e_res[xb & 1][i] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_res, row_voff(16 * xb + 4 * i), s_col + (unsigned)(16 * xb + 4 * i) * y_row, 0));
   };
   // epilogue-operand load J_ of the current output tile (LAST K tile)
@@ -203,7 +215,7 @@ static int launch_gemm256c(const void* x, int64_t ldx_bytes, const void* w, int6
 // Called by gemm.hip's dispatcher, which also decides which shapes take this kernel (continuous_ok there).
 int gemm256c_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                       const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm256c<decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, gm_tiles, st, gb);
   });
 }

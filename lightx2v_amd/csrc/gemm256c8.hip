@@ -130,7 +130,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   unsigned s_bias = 0u;  // the wave's first column in bias / gate (bf16), bytes; scales (fp32): twice that
   int rows_left = 0;     // valid rows of the current tile below row wr*128 + (lane>>3): phase-B row 32 xb + 8 i of the lane exists iff it is < rows_left
   const unsigned y_row = (unsigned)(ldy * 2);  // one row of y (and of the residual: ldr == ldy, y row-major — dispatcher), bytes
-  constexpr bool RES = EPI == X2V_EPI_RESIDUAL;
+  constexpr bool RES = epi_is_residual(EPI);
+  constexpr bool RP = EPI == EPI_RESIDUAL_PERIODIC;  // output row r combines with residual row r mod gb.r_period (as gemm256c.hip; chunks of 8 rows here)
+  const unsigned lane_off_r = (unsigned)(l8 * ldy * 2) + (unsigned)(16 * c8);
+  unsigned s_rrow = 0u;  // RP: residual row of the wave's first row of the current tile (wave-uniform)
   constexpr int NXLOAD = RES ? C8_NX_RES : C8_NX_PLAIN;
 
   auto epilogue_setup = [&](int tm, int tn) {
@@ -149,7 +152,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     s_col = col * 2u;
     s_bias = (unsigned)gn0 * 2u;
     rows_left = (int)min((int64_t)TILE, M - m0) - wr * 128 - l8;
-    if constexpr (RES) {
+    if constexpr (RP) {
+      r_res = __builtin_amdgcn_make_buffer_rsrc((void*)resid, 0, 0x80000000u, 0x00020000);
+      s_rrow = resid_tile_row(m0 + wr * 128, gb.r_period);
+      r_gate = __builtin_amdgcn_make_buffer_rsrc((void*)gate, 0, gate != nullptr ? (unsigned)N * 2u : 0u, 0x00020000);
+    } else if constexpr (RES) {
       r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(resid + m0 * ldy), 0, 0x80000000u, 0x00020000);
       r_gate = __builtin_amdgcn_make_buffer_rsrc((void*)gate, 0, gate != nullptr ? (unsigned)N * 2u : 0u, 0x00020000);
     }
@@ -158,6 +165,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // half-block hb = 4 ch + xb in walk order; residual chunk i of it: the 16 bytes phase B's store i of that half-block will overwrite
   auto res_load = [&](auto hbc, auto ic) {
     constexpr int hb = decltype(hbc)::value, ch = hb >> 2, xb = hb & 3, i = decltype(ic)::value;
+    if constexpr (RP)  // the chunk's 8 rows lie on one side of the period (gemm256_pipe.h: resid_chunk_row)
+      e_res[hb & 1][i] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_res, 32 * xb + 8 * i < rows_left ? lane_off_r : 0x80000000u,
+                                                                                           s_col + (unsigned)(ch * 128) + resid_chunk_row(s_rrow, 32 * xb + 8 * i, gb.r_period) * y_row, 0));
+    else
     e_res[hb & 1][i] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_res, row_voff(32 * xb + 8 * i), s_col + (unsigned)(ch * 128) + (unsigned)(32 * xb + 8 * i) * y_row, 0));
   };
   // per-column operands of column half ch: scales and bias in phase-A layout (tile wb = 2 ch + (j >> 2), g = j & 3: columns 32 wb + 8 g + 4 fh ..+3)
@@ -298,7 +309,7 @@ int launch_gemm256c8(const void* x, int64_t ldx_bytes, const void* w, int64_t ld
 // Called by gemm.hip's dispatcher, which also decides which shapes take this kernel (continuous_ok there).
 int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  return with_epilogue("gemm_fp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+  return with_epilogue("gemm_fp8", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm256c8<decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, gb);
   });
 }

@@ -209,7 +209,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     //      into the registers the fragments no longer need, so that ONE memory latency runs under the accumulator -> LDS pass instead of eight
     //      dependent round trips inside the store loop (the residual variant ran 8 % below the plain one per FLOP: ~10 us of a 117 us tile).
     u32x4_t rres[32];
-    if constexpr (EPI == X2V_EPI_RESIDUAL) {
+    if constexpr (EPI == EPI_RESIDUAL_PERIODIC) {
+      // row period: the residual addressed from ITS first row, each chunk (one row per lane) at its own row mod the period
+      const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)resid, 0, 0xffffffffu, 0x00020000);
+      const unsigned row0 = resid_tile_row(m0, gb.r_period);
+  #pragma unroll
+      for (int it = 0; it < 32; ++it) {
+        rres[it] = u32x4_t{0u, 0u, 0u, 0u};
+        if (ecol_ok && m0 + erow + 8 * it < M)
+          rres[it] = __builtin_amdgcn_raw_buffer_load_b128(rr, (resid_row(row0, erow + 8 * it, gb.r_period) * (unsigned)ldr + (unsigned)egn) * 2u, 0u, 0);
+      }
+    } else if constexpr (EPI == X2V_EPI_RESIDUAL) {
       const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(resid + m0 * ldr), 0, 0xffffffffu, 0x00020000);
       const unsigned r_voff = (unsigned)((erow * ldr + egn) * 2), r_step = (unsigned)(8 * ldr * 2);
   #pragma unroll
@@ -250,7 +260,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     });
     __syncthreads();
     // ---- epilogue phase 2: 16-byte stores, 32 lanes per 512-byte output row
-    if constexpr (EPI == X2V_EPI_RESIDUAL) {
+    if constexpr (epi_is_residual(EPI)) {
       float gv[8];  // per-column gate chunk: the same 8 columns in every iteration of this thread
       {
         uint4 g4 = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
@@ -301,7 +311,7 @@ static int launch_gemm256s(const void* x, int64_t ldx_bytes, const void* w, int6
 // Called by gemm.hip's dispatcher (arguments already validated there; ld*_bytes < 16 MiB checked by the caller).
 int gemm256s_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                       const void* resid, int64_t ldr, const void* gate, int gm_tiles, hipStream_t st, GemmBlocking gb) {
-  return with_epilogue("gemm", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+  return with_epilogue("gemm", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm256s<decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, gm_tiles, st, gb);
   });
 }

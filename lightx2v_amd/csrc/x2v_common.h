@@ -49,12 +49,19 @@ int ensure_dynamic_lds(const void* kernel, int bytes, const char* what);
 // (kt / a_kpb) * a_cbs + (kt % a_kpb) * 128 bytes from the row's start — and y as N-blocks — column n at (n / y_cbw) * y_cbs + n % y_cbw
 // elements from the row's start.  These are the [N_ranks][S/N][(H/N)d] buffers of the Ulysses exchanges read / written in place.
 // a_kpb <= 0 / y_cbw <= 0: plain row-major.
+// r_period > 0 (residual epilogue, x2v_gemm_*_resid_period): output row r combines with row r mod r_period of resid — a residual of r_period rows
+// fanned out over M rows without being copied.  It sits in the padding the struct had, so the kernels' argument layout is what it was.
 struct GemmBlocking {
   int a_kpb = 0;        // K-tiles (128 B) per x block
   unsigned a_cbs = 0;   // bytes between x blocks
   int y_cbw = 0;        // columns per y block (a multiple of 8)
+  int r_period = 0;     // rows of resid (0: M, row r reads row r)
   int64_t y_cbs = 0;    // elements between y blocks
 };
+// Template value of the residual epilogue WITH a row period (never crosses the ABI): a kernel instantiation of its own, so that the kernels of
+// X2V_EPI_RESIDUAL keep their instruction streams (tools/isa_diff.py, profiles/gemm_resid_period_isa.txt).
+constexpr int EPI_RESIDUAL_PERIODIC = 0x100 | X2V_EPI_RESIDUAL;
+constexpr bool epi_is_residual(int epi) { return epi == X2V_EPI_RESIDUAL || epi == EPI_RESIDUAL_PERIODIC; }
 
 // Batch strides and launch form of the pre-transposed-V attention kernel (attn.hip; tools/probes/attn_pc.hip takes the same struct)
 struct AttnBatch {

@@ -41,6 +41,8 @@ PROTOTYPES = {
     "x2v_gate_residual_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
     "x2v_activation_bf16": [_c_void_p, _c_void_p, _i64, _i32, _c_void_p],
     "x2v_gemm_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "x2v_gemm_bf16_resid_period": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i64, _c_void_p, _i32, _c_void_p],
+    "x2v_gemm_fp8_resid_period": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i64, _c_void_p, _i32, _c_void_p],
     "x2v_gemm_bf16_variant": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
     "x2v_gemm_bf16_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_fp8_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64,
@@ -319,9 +321,34 @@ def gemm_blocked(x, weight_nk, bias=None, epilogue=EPI_NONE, out=None):
     return out
 
 
-def gemm(x, weight_nk, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0):
+def _resid_period_out(who, resid, resid_period, out, M, N, x):
+    """(out [M, N], resid [period, N]) of a residual epilogue with a row period: the output is a tensor of its own (never resid itself)."""
+    r2 = _row2d(_bf16(resid, "resid"), "resid")
+    if resid_period <= 0 or tuple(r2.shape) != (resid_period, N) or resid_period > M:
+        raise X2VError(f"{who}: resid is {tuple(r2.shape)}, expected {(resid_period, N)} with 0 < resid_period <= M={M}")
+    out2 = torch.empty((M, N), dtype=torch.bfloat16, device=x.device) if out is None else _row2d(out, "out")
+    if _bf16(out2, "out").shape != (M, N):
+        raise X2VError(f"{who}: out is {tuple(out2.shape)}, expected {(M, N)}")
+    return out2, r2
+
+
+def gemm(x, weight_nk, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0, resid_period=0):
     """y = epi(x @ weight_nk.T + bias); weight_nk is the checkpoint's [N,K] tensor.  variant: see x2v_gemm_bf16_variant.
-    A 3-D `x` ([B, M, K/B], K-blocked) or 3-D `out` ([B, M, N/B], N-blocked) goes through x2v_gemm_bf16_blocked."""
+    A 3-D `x` ([B, M, K/B], K-blocked) or 3-D `out` ([B, M, N/B], N-blocked) goes through x2v_gemm_bf16_blocked.
+    resid_period > 0 (residual epilogue): `resid` is [resid_period, N] and output row r combines with its row r % resid_period
+    (x2v_gemm_bf16_resid_period); the output is a new tensor unless `out` is given."""
+    if resid_period:
+        if epilogue != EPI_RESIDUAL or resid is None or x.dim() != 2 or (out is not None and out.dim() != 2):
+            raise X2VError("gemm: resid_period needs the residual epilogue on row-major operands")
+        x2, w2 = _row2d(_bf16(x, "x"), "x"), _row2d(_bf16(weight_nk, "weight"), "weight")
+        (M, K), N = x2.shape, w2.shape[0]
+        if w2.shape[1] != K:
+            raise X2VError(f"gemm: x [M,{K}] vs weight [{N},{w2.shape[1]}]")
+        out2, r2 = _resid_period_out("gemm", resid, resid_period, out, M, N, x)
+        init()
+        _check(_lib.x2v_gemm_bf16_resid_period(_p(x2), x2.stride(0), _p(w2), w2.stride(0), _p(_vec(bias, "gemm bias", N)), _p(out2), out2.stride(0), M, N, K, _p(r2), r2.stride(0),
+                                               resid_period, _p(_vec(gate, "gemm gate", N)), variant, _stream()), "gemm_bf16_resid_period")
+        return out2
     if x.dim() == 3 or (out is not None and out.dim() == 3):
         if epilogue != EPI_RESIDUAL:
             return gemm_blocked(x, weight_nk, bias, epilogue, out)
@@ -610,12 +637,18 @@ def gemm_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogu
     return out2
 
 
-def gemm_fp8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0):
+def gemm_fp8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0, resid_period=0):
+    """resid_period: as gemm() (x2v_gemm_fp8_resid_period)."""
     M, K = xq.shape
     N = wq_nk.shape[0]
     if xq.dtype != torch.float8_e4m3fn or wq_nk.dtype != torch.float8_e4m3fn:
         raise X2VError("gemm_fp8: operands must be float8_e4m3fn (OCP; gfx950)")
-    if epilogue == EPI_RESIDUAL:
+    if resid_period:
+        if epilogue != EPI_RESIDUAL or resid is None:
+            raise X2VError("gemm_fp8: resid_period needs the residual epilogue")
+        out2, r2 = _resid_period_out("gemm_fp8", resid, resid_period, out, M, N, xq)
+        gate = _vec(gate, "gemm_fp8 gate", N)
+    elif epilogue == EPI_RESIDUAL:
         out2 = _row2d(resid if out is None else out, "out")
         r2 = _row2d(_bf16(resid, "resid"), "resid")
         gate = _vec(gate, "gemm_fp8 gate", N)
@@ -628,6 +661,10 @@ def gemm_fp8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=N
     bias = _vec(bias, "gemm_fp8 bias", N)
     init()
     if M == 0:
+        return out2
+    if resid_period:
+        _check(_lib.x2v_gemm_fp8_resid_period(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, _p(r2), r2.stride(0),
+                                              resid_period, _p(gate), variant, _stream()), "gemm_fp8_resid_period")
         return out2
     _check(
         _lib.x2v_gemm_fp8_variant(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, epilogue, _p(r2), 0 if r2 is None else r2.stride(0), _p(gate), variant, _stream()),

@@ -73,14 +73,16 @@ class MMWeightHip(_Movable):
         self.weight = self.lazy_load_file.get_tensor(self.weight_name).to(torch.bfloat16)
         self.bias = self.lazy_load_file.get_tensor(self.bias_name).to(torch.bfloat16) if self.bias_name is not None else None
 
-    def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None):
+    accepts_resid_period = True  # apply(..., resid_period=): the residual epilogue reading resid row r % resid_period (lib.gemm)
+
+    def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None, resid_period=0):
         """`row_slice` (a slice over the N output channels) runs the layer on that block of weight rows only — weight, bias (and, in the
         quantised classes, the per-channel scales) sliced together; used where one checkpoint tensor feeds two consumers with different
         epilogues (HunyuanVideo's linear1 = [qkv | mlp], hunyuan/infer/transformer_infer.py:329-334)."""
         w, b = self.weight, self.bias
         if row_slice is not None:
             w, b = w[row_slice], (None if b is None else b[row_slice])
-        return lib.gemm(input_tensor, w, b, epilogue=epilogue, resid=resid, gate=gate, out=out)
+        return lib.gemm(input_tensor, w, b, epilogue=epilogue, resid=resid, gate=gate, out=out, resid_period=resid_period)
 
     def apply_vt(self, input_tensor, num_heads):
         """The layer's output as V^T [H, ceil(M/64), 128, 64] (the attention kernel's operand) — from the GEMM epilogue when the shape takes
@@ -105,6 +107,7 @@ class MMWeightFp8Hip(_Movable):
     # apply() takes the Ulysses exchange buffers in place (round 5): an N-blocked 3-D `out` goes to x2v_gemm_fp8_blocked, a K-blocked 3-D bf16
     # input is de-blocked by its quantisation pass (lib.quant_fp8_rowwise -> x2v_quant_fp8_rowwise_blocked) and multiplied row-major
     accepts_blocked = True
+    accepts_resid_period = True  # as MMWeight.apply (lib.gemm_fp8)
 
     def __init__(self, weight_name, bias_name, lazy_load=False, lazy_load_file=None):
         self.weight_name, self.bias_name = weight_name, bias_name
@@ -143,14 +146,14 @@ class MMWeightFp8Hip(_Movable):
         """LayerNorm (+affine, +modulate) and `quantize_input` of its output in one kernel (bit-identical to the two in sequence)."""
         return lib.layernorm_quant_fp8(x, weight, bias, scale, shift, eps)
 
-    def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None, quantized=None):
+    def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None, quantized=None, resid_period=0):
         xq, sx = self.quantize_input(input_tensor) if quantized is None else quantized
         w, sw, b = self.weight, self.weight_scale, self.bias
         if row_slice is not None:
             w, sw, b = w[row_slice], sw[row_slice], (None if b is None else b[row_slice])
         if out is not None and out.dim() == 3:  # N-blocked y: a seq->head send buffer [N, S/N, (H/N) d]
             return lib.gemm_fp8_blocked(xq, sx, w, sw, b, epilogue=epilogue, out=out)
-        return lib.gemm_fp8(xq, sx, w, sw, b, epilogue=epilogue, resid=resid, gate=gate, out=out)
+        return lib.gemm_fp8(xq, sx, w, sw, b, epilogue=epilogue, resid=resid, gate=gate, out=out, resid_period=resid_period)
 
     def state_dict(self, destination=None):
         destination = {} if destination is None else destination

@@ -307,8 +307,11 @@ class WanTransformerInfer:
         self.attn_time_hook = None  # bench.py: callable(kind) -> context manager timing the attention launch
         self.cache_cross_kv = bool(_cfg(config, "cache_cross_kv", True))
         self._cross_kv_cache = {}  # (id(block weights), id(context)) -> (context, version, k, v); see _cross_kv
-        # CFG pair mode (WanModel._forward_pair): x holds BOTH forwards of a step, [cond rows | pad | uncond rows | pad], (S, S_pad) here
+        # CFG pair mode (WanModel._forward_pair): x holds BOTH forwards of a step, [cond rows | pad | uncond rows | pad], (S, S_pad) here.
+        # With the CFG-shared front (cfg_front_form) x enters block 0 as ONE slot of S_pad rows — the two forwards are the same computation up to
+        # block 0's cross-attention K / V — and leaves that block's cross-attention output projection stacked.
         self._pair = None
+        self.front_form = None  # what the last pair pass ran: "shared" / "unshared"
 
     def set_scheduler(self, scheduler):
         self.scheduler = scheduler
@@ -365,17 +368,23 @@ class WanTransformerInfer:
         # projections and the norm+RoPE kernel
         if self._pair is not None:
             # both CFG forwards in one pass: projections and row kernels run on the stacked rows, the two self-attentions are one launch
+            # (block 0 of the CFG-shared front: one slot, one self-attention — the same batched entry and key walk, so a row's bits do not change)
             S, Sp = self._pair
+            nb = s_local // Sp
             if not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
                 vt = weights.self_attn_v.apply_vt(n1, self.num_heads)
             else:
                 vt = lib.transpose_heads(weights.self_attn_v.apply(n1, **mmkw), self.num_heads)
             q = weights.self_attn_q.apply(n1, **mmkw)
             k = weights.self_attn_k.apply(n1, **mmkw)
-            for b in range(2):  # token b*Sp + i of either forward sits at grid position i
+            for b in range(nb):  # token b*Sp + i of either forward sits at grid position i
                 rows = slice(b * Sp, b * Sp + S)
                 lib.rmsnorm_rope_(q[rows], k[rows], weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
-            attn = lib.attention_batched(q, k, vt, self.num_heads, 2, Sp, S, prescaled=True, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
+            # Only the S token rows of a slot are queries, as in a separate forward: the attention kernel decides its lazy O rescale per WAVE
+            # (attn.hip: `__any` over the wave's rows), so a padding row that was a query could switch the rescale on for the token rows sharing
+            # its wave and change their low bits.  The padding rows of the output are zero-filled instead (finite: they become V^T columns).
+            attn = self._slot_rows_zero_padding(q.new_empty(q.shape), nb, S, Sp)
+            lib.attention_batched(q, k, vt, self.num_heads, nb, Sp, S, out=attn, prescaled=True, all_rows_query=False, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
             return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
         if pa is None and fast and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
             v, vt = None, weights.self_attn_v.apply_vt(n1, self.num_heads)  # V^T from the v projection's epilogue (the attention kernel's operand)
@@ -394,6 +403,14 @@ class WanTransformerInfer:
         else:
             attn = pa(q=q, k=k, v=v if v_pending is None else v_pending, num_heads=self.num_heads, head_dim=self.head_dim, timer=self._timed, variant=variant)
         return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
+
+    @staticmethod
+    def _slot_rows_zero_padding(t, slots, S, Sp):
+        """t [slots * Sp, D] with the padding rows [S, Sp) of every slot zeroed (the token rows are left for a kernel to write)."""
+        if Sp > S:
+            for b in range(slots):
+                t[b * Sp + S : (b + 1) * Sp].zero_()
+        return t
 
     blocked_exchange = True  # Ulysses: exchange buffers as kernel operands (False: the reference's row-major form with its transposing copies)
 
@@ -422,10 +439,13 @@ class WanTransformerInfer:
 
         if self._pair is not None:
             S, Sp = self._pair
-            attn = torch.empty_like(q)
-            for b, ctx in enumerate(context):  # (conditional, unconditional) contexts; every row of a forward's slot is a query
-                rows = slice(b * Sp, (b + 1) * Sp)
-                attend(q[rows], ctx, out=attn[rows])
+            fan_out = x.shape[0] == Sp  # the CFG-shared front: one q for both contexts; from here on the two forwards differ
+            attn = self._slot_rows_zero_padding(q.new_empty((2 * Sp, q.shape[1])), 2, S, Sp)
+            for b, ctx in enumerate(context):  # (conditional, unconditional) contexts; the token rows of a forward's slot are the queries (see infer_self_attn)
+                rows = slice(b * Sp, b * Sp + S)
+                attend(q[:S] if fan_out else q[rows], ctx, out=attn[rows])
+            if fan_out:  # the residual stream goes from Sp shared rows to the stacked 2 Sp in the epilogue: output row r reads x[r mod Sp]
+                return weights.cross_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=None, resid_period=Sp)
             return weights.cross_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=None)
         return weights.cross_attn_o.apply(attend(q, context), epilogue=lib.EPI_RESIDUAL, resid=x, gate=None)
 
@@ -591,6 +611,25 @@ def cfg_form_by_size(seq_len, num_heads):
     (tests/test_gpu_model.py)."""
     workgroups = ((int(seq_len) + 255) // 256) * int(num_heads)
     return "pair" if workgroups >= 2048 else "streams"
+
+
+def cfg_front_form(config, transformer_infer, x_cond, x_uncond, block0=None, form="pair"):
+    """'shared' or 'unshared': whether a CFG step runs block 0's front — norm1 + modulate, the q / k / v projections, q / k RMSNorm + RoPE, self-attention,
+    the o projection with its gated residual, norm3, the cross-attention q projection and its RMSNorm — ONCE for both forwards.  The forwards of a
+    step start from the same latents and timestep (wan/model.py:197-226) and differ only in the text context, which first enters in block 0's
+    cross-attention K / V, so that front is the same computation twice: at Wan-14B 720p one self-attention, five D x D projections and four row
+    passes of the 40 + 40 a step runs.  Shared only
+      * in the pair pass (`form` "pair"; the two-stream form "streams" and one forward after the other "separate" keep both halves),
+      * with the plain single-GPU block driver (no TeaCache — its skipped and residual-replay steps are per branch —, no Ulysses),
+      * when both halves ARE one tensor (`x_cond is x_uncond`: the same pre-infer output, not merely equal values; a hook that hands the two
+        forwards different inputs gets both computed),
+      * when block 0's cross-attention output projection can fan the residual out (operator classes with `accepts_resid_period`),
+      * and config `cfg_shared_front` (default on) does not turn it off — the switch that lets the two forms be timed in one process."""
+    tr = transformer_infer
+    ok = (form == "pair" and bool(_cfg(config, "cfg_shared_front", True)) and x_cond is x_uncond and type(tr) is WanTransformerInfer
+          and tr.parallel_attention is None and tr.blocks_num >= 1
+          and (block0 is None or getattr(block0.compute_phases[2].cross_attn_o, "accepts_resid_period", False)))
+    return "shared" if ok else "unshared"
 
 
 class CfgBranchStreams:
@@ -759,21 +798,31 @@ class WanModel:
         return (bool(want) and type(tr) is WanTransformerInfer and tr.parallel_attention is None and tr.round_mode == lib.ROUND_FP32
                 and tr.attention_type == "hip_flash" and self.scheduler.latents.is_cuda)
 
+    def _pair_inputs(self, inputs):
+        """What the pair pass starts from: (embed, grid_sizes, (x_cond, x_uncond), embed0, seq_lens, freqs, (ctx_cond, ctx_uncond)).  The two forwards
+        of a step share latents and timestep, so ONE pre-infer output serves both — the same tensor object twice, which is what cfg_front_form asks
+        for; a subclass that gives the forwards different token inputs returns two tensors and gets both halves computed."""
+        embed, grid_sizes, (x, embed0, seq_lens, freqs, ctx_c) = self.pre_infer.infer(self.pre_weight, inputs, positive=True)
+        ctx_u = self.pre_infer.full_context(self.pre_weight, inputs, False)
+        return embed, grid_sizes, (x, x), embed0, seq_lens, freqs, (ctx_c, ctx_u)
+
     def _forward_pair(self, inputs):
         tr = self.transformer_infer
-        embed, grid_sizes, (x, embed0, seq_lens, freqs, ctx_c) = self.pre_infer.infer(self.pre_weight, inputs, positive=True)
+        embed, grid_sizes, xs, embed0, seq_lens, freqs, ctxs = self._pair_inputs(inputs)
+        x = xs[0]
         S = x.shape[0]
-        if int(seq_lens[0]) != S:
+        if int(seq_lens[0]) != S or xs[1].shape != x.shape:
             return None  # token buffer padded beyond the grid: the separate forwards handle it
-        ctx_u = self.pre_infer.full_context(self.pre_weight, inputs, False)
         Sp = (S + 63) // 64 * 64  # a forward's slot: whole 64-token blocks of V^T
-        X = torch.empty((2 * Sp, x.shape[1]), dtype=x.dtype, device=x.device)
-        for b in range(2):
-            X[b * Sp : b * Sp + S].copy_(x)
+        tr.front_form = cfg_front_form(self.config, tr, xs[0], xs[1], self.transformer_weights.blocks[0])
+        slots = 1 if tr.front_form == "shared" else 2  # shared front: block 0 stacks the stream in its cross-attention output projection
+        X = torch.empty((slots * Sp, x.shape[1]), dtype=x.dtype, device=x.device)
+        for b in range(slots):
+            X[b * Sp : b * Sp + S].copy_(xs[b])
             X[b * Sp + S : (b + 1) * Sp].zero_()  # padding rows: zero in, finite throughout (every kernel writes all rows of its output)
         tr._pair = (S, Sp)
         try:
-            X = tr.infer(self.transformer_weights, grid_sizes, embed, X, embed0, seq_lens, freqs, (ctx_c, ctx_u))
+            X = tr.infer(self.transformer_weights, grid_sizes, embed, X, embed0, seq_lens, freqs, ctxs)
         finally:
             tr._pair = None
         rows = self.post_infer.infer_rows(self.post_weight, X, embed)
@@ -821,7 +870,7 @@ def default_config(dims, **overrides):
         freq_dim=256, text_len=dims.get("text_len", 512), in_dim=16, out_dim=16, eps=1e-6, patch_size=(1, 2, 2), vae_stride=(4, 8, 8),
         cpu_offload=False, mm_config={"mm_type": "Hip-bf16"}, self_attn_1_type="hip_flash", cross_attn_1_type="hip_flash", attention_type="hip_flash",
         feature_caching="NoCaching", parallel_attn_type=None, enable_cfg=True, sample_guide_scale=6.0, sample_shift=8.0, infer_steps=50, seed=42,
-        target_video_length=81, target_shape=(16, 21, 90, 160),
+        target_video_length=81, target_shape=(16, 21, 90, 160), cfg_shared_front=True,
     )
     cfg.update(overrides)
     return cfg
