@@ -496,6 +496,37 @@ int x2v_clip_embed_f16(const void* patches, int64_t ldp, const void* cls, const 
 int x2v_clip_preprocess_f16(const float* img, int64_t c_stride, int64_t row_stride, int H, int W, void* out, int64_t ld_out, int image_size, int patch,
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
 
+/* ---- umT5-XXL text encoder (bf16): the producer of text_encoder_output["context"] / ["context_null"] (runners/wan/wan_runner.py:178-191; the model is
+ * models/input_encoders/hf/t5/model.py, T5Encoder.forward :314-347).  Its T5LayerNorm (:68-72) is x2v_rmsnorm_bf16 with X2V_ROUND_FP32. ---- */
+
+/* epilogues of x2v_gemm_rows_bf16 */
+#define X2V_EPIR_NONE 0     /* y = bf16(acc) */
+#define X2V_EPIR_RESIDUAL 2 /* y = bf16(resid + bf16(acc)); y may alias resid          (x + self.attn(...) / x + self.ffn(...), t5/model.py:202-203) */
+#define X2V_EPIR_GEGLU 3    /* W is [2N, K], row 2n = fc1 row n, row 2n + 1 = gate.0 row n: y = bf16(bf16(acc_fc1) * gelu_tanh(bf16(acc_gate))), the GELU
+                             * in fp32 by the module's formula (:58)                     (self.fc1(x) * self.gate(x), :165) */
+
+/* y[M,N] = epi(x[M,K] . W[N,K]^T) in bf16 with fp32 accumulation for 1 <= M <= 4096, the weight-streaming small-M form (the kernel of x2v_gemm_f16
+ * instantiated for bf16) — replaces the bias-free nn.Linear calls of T5Attention q / k / v / o (t5/model.py:110-112,134; q, k, v as one [3 dim_attn, dim]
+ * weight) and T5FeedForward gate.0 / fc1 / fc2 (:165,168).  K % 32 == 0, N % 4 == 0 (N % 2 == 0 and W of 2N rows with X2V_EPIR_GEGLU); resid is read by
+ * X2V_EPIR_RESIDUAL only (else NULL).  Each output value is reduced in k order whatever M: rows of a packed batch equal the rows computed alone, bit for bit. */
+int x2v_gemm_rows_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, void* y, int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid,
+                       int64_t ldr, void* stream);
+
+/* The tile x2v_gemm_rows_bf16 launches for (M, N, epilogue): 0 = 128 x 64, 1 = 64 x 64, 2 = 64 x 32, 3 = 64 x 16 rows of x by rows of W (host arithmetic;
+ * no reference counterpart). */
+int x2v_gemm_rows_bf16_tile_choice(int64_t M, int N, int epilogue);
+
+/* out[r0_b + i, h*64 : h*64 + 64] = softmax_j(scale * q_i . k_j + bias[h][j - i + 511]) v_j over the keys of sequence b only, non-causal, head dim 64 —
+ * replaces the einsum / attn_bias / softmax / einsum of T5Attention.forward (t5/model.py:115-129) with the block's T5RelativeEmbedding (:255-263) and the
+ * padding mask (:121) folded in: `batch` <= 8 sequences of 1..512 tokens are packed row after row, sequence b being rows cu_seqlens[b] .. cu_seqlens[b+1] - 1
+ * (r0_b = cu_seqlens[b]), and keys outside a query's own sequence never contribute.  cu_seqlens is a HOST array of batch + 1 increasing ints, passed on to
+ * the kernel by value (no copy, no sync).  qkv is the fused q | k | v GEMM output read in place: columns 0, H*64, 2*H*64 of a row of stride ld.  bias is a
+ * device table [H][1023] fp32, entry [h][d + 511] for key position - query position = d.  scale multiplies q . k as given (T5 passes 1: "T5 does not use
+ * scaling", :123).  fp32 scores, bias and softmax statistics with the row maximum subtracted; P rounded to bf16 for the PV product, fp32 accumulation, one
+ * rounding of the output. */
+int x2v_attn_bf16_d64_relbias(const void* qkv, int64_t ld, const float* bias, void* out, int64_t ldo, const int* cu_seqlens, int batch, int num_heads,
+                              float scale, void* stream);
+
 /* Box calibration (measurement plumbing; no reference counterpart): runs bare v_mfma_f32_16x16x32_bf16 loops (operands in registers,
  * 8 waves per CU, every CU) for `milliseconds` on `stream` and returns in *tflops what the board sustained over the second half of that time.
  * bench.py calls it before and after its timed region so that a roofline fraction measured on one box can be compared with another's

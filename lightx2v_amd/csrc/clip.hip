@@ -2,12 +2,7 @@
 // reference: models/input_encoders/hf/xlm_roberta/model.py — CLIPModel.visual :436-450, VisionTransformer.forward :274-295, AttentionBlock :157-164,
 // SelfAttention :75-91, LayerNorm :47-49.
 //
-// gemm_f16_kernel — y[M,N] = epi(x[M,K] . W[N,K]^T + b) on v_mfma_f32_16x16x32_f16 for M of a few hundred rows (257 tokens per image).  No LDS: the launch is
-//   bound by streaming W once, x (<= 2.6 MB) is served from L2.  D = W . x^T, so a lane ends up with 4 consecutive output columns of one row (8-byte stores,
-//   bias / residual reads of the same shape).  Workgroup = 4 waves stacked along M, wave tile (16 MT) x (16 NT); a lane's fragment of either operand is 16
-//   contiguous bytes of one row.  A 4-deep register ring of k-steps keeps 4 x (MT + NT) 16-byte loads per lane in flight.  The launcher takes the largest tile
-//   of {128x64, 64x64, 64x32, 64x16} that still yields >= 192 workgroups.  Every output value is reduced in k order by one lane whatever the tile and whatever
-//   M: batching images is bit-identical.
+// gemm_rows_kernel<_Float16> (gemm_rows.h, shared with the bf16 text encoder) — y[M,N] = epi(x[M,K] . W[N,K]^T + b), the weight-streaming small-M GEMM.
 // attn_f16_d80_kernel — non-causal attention, head dim 80, <= 272 keys, q/k/v read in place from the QKV GEMM's output rows.  Workgroup = (64 query rows, one
 //   head of one image); the head's K [272][80] and V^T [80][288] live in LDS (93 KiB), zero-filled beyond the last key.  S^T = K . Q^T (three k-steps over d:
 //   32 + 32 + 16, the last half zero in both operands) leaves a query's 272 scores in 17 accumulator tiles of the 4 lanes that share its column: the softmax
@@ -21,97 +16,10 @@
 
 #include <algorithm>
 
+#include "gemm_rows.h"
 #include "x2v_common.h"
 
 namespace x2v {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-// ---- GEMM ----------------------------------------------------------------------------------------------------------------------------------------------
-constexpr int GF_RING = 4;
-
-template <int MT, int NT>
-__global__ __launch_bounds__(256) void gemm_f16_kernel(const _Float16* __restrict__ x, int64_t ldx, const _Float16* __restrict__ w, int64_t ldw,
-                                                       const _Float16* __restrict__ bias, _Float16* y, int64_t ldy, int M, int N, int K, int epi,
-                                                       const _Float16* resid, int64_t ldr) {  // y may alias resid: neither is __restrict__
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c16 = lane & 15, g4 = lane >> 4;
-  const int n0 = blockIdx.x * 16 * NT, m0 = blockIdx.y * 64 * MT + wid * 16 * MT;
-  if (m0 >= M) return;  // no barrier in this kernel: a wave without rows leaves
-  // rows beyond M / N read the last valid row (never stored)
-  const _Float16* xr[MT];
-  const _Float16* wr[NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) xr[i] = x + (int64_t)min(m0 + 16 * i + c16, M - 1) * ldx + g4 * 8;
-#pragma unroll
-  for (int j = 0; j < NT; ++j) wr[j] = w + (int64_t)min(n0 + 16 * j + c16, N - 1) * ldw + g4 * 8;
-
-  f32x4_t acc[NT][MT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int i = 0; i < MT; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int ksteps = K / 32, last = ksteps - 1;
-  half8_t xf[GF_RING][MT], wf[GF_RING][NT];
-#pragma unroll
-  for (int s = 0; s < GF_RING; ++s) {
-    const int ko = min(s, last) * 32;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) xf[s][i] = *reinterpret_cast<const half8_t*>(xr[i] + ko);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) wf[s][j] = *reinterpret_cast<const half8_t*>(wr[j] + ko);
-  }
-  for (int ks = 0; ks < ksteps; ks += GF_RING) {
-#pragma unroll
-    for (int s = 0; s < GF_RING; ++s) {
-      if (ks + s < ksteps) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int i = 0; i < MT; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][j], xf[s][i], acc[j][i], 0, 0, 0);
-      }
-      const int ko = min(ks + s + GF_RING, last) * 32;  // past the end: the last k-step again (read, not used)
-#pragma unroll
-      for (int i = 0; i < MT; ++i) xf[s][i] = *reinterpret_cast<const half8_t*>(xr[i] + ko);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) wf[s][j] = *reinterpret_cast<const half8_t*>(wr[j] + ko);
-    }
-  }
-
-  // acc[j][i][e] = row m0 + 16 i + c16, column n0 + 16 j + 4 g4 + e (N % 4 == 0: a group of 4 columns is wholly inside or outside)
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int m = m0 + 16 * i + c16;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int n = n0 + 16 * j + 4 * g4;
-      if (n >= N) continue;
-      float v[4] = {acc[j][i][0], acc[j][i][1], acc[j][i][2], acc[j][i][3]};
-      if (bias != nullptr) {
-        const half4_t bv = *reinterpret_cast<const half4_t*>(bias + n);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
-      }
-      if (epi == X2V_EPI16_GELU_ERF) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = gelu_erf_f(v[e]);
-      } else if (epi == X2V_EPI16_RESIDUAL) {  // torch: x + linear(...) on two fp16 tensors
-        const half4_t rv = *reinterpret_cast<const half4_t*>(resid + (int64_t)m * ldr + n);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (float)rv[e] + (float)(_Float16)v[e];
-      }
-      half4_t o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (_Float16)v[e];
-      *reinterpret_cast<half4_t*>(y + (int64_t)m * ldy + n) = o;
-    }
-  }
-}
 
 // ---- attention -----------------------------------------------------------------------------------------------------------------------------------------
 constexpr int AT_D = 80;
@@ -310,57 +218,17 @@ __global__ __launch_bounds__(256) void clip_preprocess_kernel(const float* __res
   }
 }
 
-template <int MT, int NT>
-static void launch_gemm_f16(dim3 grid, hipStream_t st, const _Float16* x, int64_t ldx, const _Float16* w, int64_t ldw, const _Float16* bias, _Float16* y, int64_t ldy, int M,
-                            int N, int K, int epi, const _Float16* resid, int64_t ldr) {
-  hipLaunchKernelGGL((gemm_f16_kernel<MT, NT>), grid, dim3(256), 0, st, x, ldx, w, ldw, bias, y, ldy, M, N, K, epi, resid, ldr);
-}
-
 }  // namespace x2v
 
 using namespace x2v;
 
-// tile code: 0 = 128 x 64, 1 = 64 x 64, 2 = 64 x 32, 3 = 64 x 16
-static const int kGemmF16Tiles[4][2] = {{2, 4}, {1, 4}, {1, 2}, {1, 1}};
-
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_f16_tile_choice(int64_t M, int N) {
-  if (M <= 0 || N <= 0) return X2V_E_SHAPE;
-  for (int t = 0; t < 3; ++t) {
-    const int64_t bm = 64 * kGemmF16Tiles[t][0], bn = 16 * kGemmF16Tiles[t][1];
-    if (((M + bm - 1) / bm) * ((N + bn - 1) / bn) >= 192) return t;
-  }
-  return 3;
-}
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_f16_tile_choice(int64_t M, int N) { return gemm_rows_tile_choice(M, N); }
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M,
                                                                    int N, int K, int epilogue, const void* resid, int64_t ldr, void* stream) {
   X2V_REQUIRE(x && w && y, X2V_E_ARG, "gemm_f16: null pointer");
   X2V_REQUIRE(epilogue == X2V_EPI16_NONE || epilogue == X2V_EPI16_GELU_ERF || epilogue == X2V_EPI16_RESIDUAL, X2V_E_ARG, "gemm_f16: unknown epilogue %d", epilogue);
-  X2V_REQUIRE(epilogue != X2V_EPI16_RESIDUAL || resid != nullptr, X2V_E_ARG, "gemm_f16: the residual epilogue needs resid");
-  X2V_REQUIRE(M >= 0 && M < (1ll << 31) && N > 0 && K > 0, X2V_E_SHAPE, "gemm_f16: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
-  X2V_REQUIRE(K % 32 == 0, X2V_E_SHAPE, "gemm_f16: K=%d must be a multiple of 32 (pad the operands with zero columns)", K);
-  X2V_REQUIRE(N % 4 == 0, X2V_E_SHAPE, "gemm_f16: N=%d must be a multiple of 4", N);
-  X2V_REQUIRE(ldx >= K && ldw >= K && ldy >= N && ldx % 8 == 0 && ldw % 8 == 0 && ldy % 4 == 0 && (resid == nullptr || (ldr >= N && ldr % 4 == 0)), X2V_E_ALIGN,
-              "gemm_f16: leading dimensions must cover the rows (ldx, ldw multiples of 8, ldy, ldr of 4 halves)");
-  X2V_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(bias) && aligned16(resid), X2V_E_ALIGN, "gemm_f16: pointers must be 16-byte aligned");
-  if (M == 0) return X2V_OK;
-  const int t = x2v_gemm_f16_tile_choice(M, N);
-  const int mt = kGemmF16Tiles[t][0], nt = kGemmF16Tiles[t][1];
-  const dim3 grid((unsigned)((N + 16 * nt - 1) / (16 * nt)), (unsigned)((M + 64 * mt - 1) / (64 * mt)));
-  X2V_REQUIRE(grid.y < 65536, X2V_E_SHAPE, "gemm_f16: M=%lld is beyond this kernel's grid (a skinny-M GEMM)", (long long)M);
-  hipStream_t st = (hipStream_t)stream;
-  const _Float16 *xp = (const _Float16*)x, *wp = (const _Float16*)w, *bp = (const _Float16*)bias, *rp = (const _Float16*)resid;
-  _Float16* yp = (_Float16*)y;
-  if (t == 0)
-    launch_gemm_f16<2, 4>(grid, st, xp, ldx, wp, ldw, bp, yp, ldy, (int)M, N, K, epilogue, rp, ldr);
-  else if (t == 1)
-    launch_gemm_f16<1, 4>(grid, st, xp, ldx, wp, ldw, bp, yp, ldy, (int)M, N, K, epilogue, rp, ldr);
-  else if (t == 2)
-    launch_gemm_f16<1, 2>(grid, st, xp, ldx, wp, ldw, bp, yp, ldy, (int)M, N, K, epilogue, rp, ldr);
-  else
-    launch_gemm_f16<1, 1>(grid, st, xp, ldx, wp, ldw, bp, yp, ldy, (int)M, N, K, epilogue, rp, ldr);
-  X2V_LAUNCH_CHECK("gemm_f16 launch");
-  return X2V_OK;
+  return gemm_rows_launch<_Float16>("gemm_f16", x, ldx, w, ldw, bias, y, ldy, M, N, K, epilogue, resid, ldr, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_attn_f16_d80(const void* qkv, int64_t ld, void* out, int64_t ldo, int batch, int S, int num_heads, float scale,

@@ -88,6 +88,9 @@ PROTOTYPES = {
     "x2v_layernorm_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _f32, _c_void_p],
     "x2v_clip_embed_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
     "x2v_clip_preprocess_f16": [_c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _c_void_p],
+    "x2v_gemm_rows_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
+    "x2v_gemm_rows_bf16_tile_choice": [_i64, _i32, _i32],
+    "x2v_attn_bf16_d64_relbias": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, ctypes.POINTER(_i32), _i32, _i32, _f32, _c_void_p],
     "x2v_vae_replicate_border_f32": [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
@@ -1133,4 +1136,76 @@ def clip_preprocess(img, out, image_size, patch, mean, std):
     init()
     _check(_lib.x2v_clip_preprocess_f16(_p(img), img.stride(0), img.stride(1), img.shape[1], img.shape[2], _p(out), out.stride(0), image_size, patch, *[float(m) for m in mean],
                                         *[float(s) for s in std], _stream()), "clip_preprocess")
+    return out
+
+
+# ---- umT5 text encoder (bf16; csrc/t5.hip) ------------------------------------------------------------------------------------------------------------
+EPIR_NONE, EPIR_RESIDUAL, EPIR_GEGLU = 0, 2, 3
+ATTN_D64_MAX_BATCH, ATTN_D64_MAX_LEN = 8, 512
+
+
+def _bf16rows(t, name):
+    return _row2d(_bf16(t, name), name)
+
+
+def gemm_rows_bf16(x, weight_nk, epilogue=EPIR_NONE, resid=None, out=None):
+    """x2v_gemm_rows_bf16: y[M, N] = epi(x[M, K] . W^T) in bf16 (fp32 accumulation), M <= 4096; K % 32 == 0, N % 4 == 0.  W is [N, K], or [2N, K] with
+    EPIR_GEGLU (rows of fc1 and gate.0 interleaved)."""
+    x, w = _bf16rows(x, "gemm_rows_bf16 x"), _bf16rows(weight_nk, "gemm_rows_bf16 weight")
+    M, K = x.shape
+    if w.shape[1] != K:
+        raise X2VError(f"gemm_rows_bf16: x {tuple(x.shape)} and weight {tuple(w.shape)} disagree on K")
+    if epilogue == EPIR_GEGLU and w.shape[0] % 2:
+        raise X2VError(f"gemm_rows_bf16: the GEGLU epilogue needs an even number of weight rows, got {w.shape[0]}")
+    N = w.shape[0] // 2 if epilogue == EPIR_GEGLU else w.shape[0]
+    if (resid is not None) != (epilogue == EPIR_RESIDUAL):
+        raise X2VError("gemm_rows_bf16: resid goes with EPIR_RESIDUAL, and only with it")
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device) if out is None else _bf16rows(out, "gemm_rows_bf16 out")
+    if out.shape != (M, N) or (resid is not None and _bf16rows(resid, "gemm_rows_bf16 resid").shape != (M, N)):
+        raise X2VError(f"gemm_rows_bf16: out / resid must be [{M}, {N}]")
+    init()
+    _check(_lib.x2v_gemm_rows_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), M, N, K, epilogue, _p(resid), 0 if resid is None else resid.stride(0), _stream()),
+           "gemm_rows_bf16")
+    return out
+
+
+def gemm_rows_bf16_tile_choice(M, N, epilogue=EPIR_NONE):
+    """x2v_gemm_rows_bf16_tile_choice: (rows of x, rows of W) of the workgroup tile x2v_gemm_rows_bf16 launches — host arithmetic."""
+    t = _lib.x2v_gemm_rows_bf16_tile_choice(M, N, epilogue)
+    _check(min(t, 0), "gemm_rows_bf16_tile_choice")
+    return ((128, 64), (64, 64), (64, 32), (64, 16))[t]
+
+
+def _cu_seqlens(cu_seqlens, rows, who):
+    cu = [int(c) for c in cu_seqlens]
+    if not 2 <= len(cu) <= ATTN_D64_MAX_BATCH + 1:
+        raise X2VError(f"{who}: {len(cu) - 1} sequences; the kernel takes 1..{ATTN_D64_MAX_BATCH} (batch <= {ATTN_D64_MAX_BATCH})")
+    lens = [b - a for a, b in zip(cu, cu[1:])]
+    if cu[0] < 0 or min(lens) < 1:
+        raise X2VError(f"{who}: cu_seqlens {cu} must start at >= 0 and increase")
+    if max(lens) > ATTN_D64_MAX_LEN:
+        raise X2VError(f"{who}: a sequence of {max(lens)} tokens; the kernel holds at most {ATTN_D64_MAX_LEN} keys (length <= {ATTN_D64_MAX_LEN})")
+    if cu[-1] > rows:
+        raise X2VError(f"{who}: cu_seqlens ends at row {cu[-1]} but qkv has {rows} rows")
+    return (_i32 * len(cu))(*cu), len(cu) - 1
+
+
+def attention_bf16_d64_relbias(qkv, bias, cu_seqlens, num_heads, out=None, scale=1.0):
+    """x2v_attn_bf16_d64_relbias on the fused q | k | v GEMM output qkv [rows, 3 * num_heads * 64] (read in place; a row stride beyond its columns is fine, a
+    column slice that starts inside a row is not) -> [rows, num_heads * 64] bf16.  cu_seqlens: host ints, sequence b = rows cu[b] .. cu[b + 1] - 1;
+    bias [num_heads, 1023] fp32 on the device.  Rows outside every sequence are not written."""
+    who = "attention_bf16_d64_relbias"
+    qkv = _bf16rows(qkv, who + " qkv")
+    D = num_heads * 64
+    if qkv.shape[1] != 3 * D:
+        raise X2VError(f"{who}: qkv {tuple(qkv.shape)} is not [rows, 3 * {num_heads} * 64] (q | k | v side by side; pass the whole rows, not a column slice)")
+    bias = _vec(bias, who + " bias", num_heads * 1023, dtype=torch.float32)
+    if bias is None:
+        raise X2VError(f"{who}: bias is required")
+    cu, batch = _cu_seqlens(cu_seqlens, qkv.shape[0], who)
+    out = torch.empty((qkv.shape[0], D), dtype=torch.bfloat16, device=qkv.device) if out is None else _bf16rows(out, who + " out")
+    if out.shape != (qkv.shape[0], D):
+        raise X2VError(f"{who}: out must be [{qkv.shape[0]}, {D}]")
+    init()
+    _check(_lib.x2v_attn_bf16_d64_relbias(_p(qkv), qkv.stride(0), _p(bias), _p(out), out.stride(0), cu, batch, num_heads, float(scale), _stream()), who)
     return out

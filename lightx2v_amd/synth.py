@@ -184,10 +184,50 @@ def synth_clip_weights(dims, seed=0, device="cpu", dtype=torch.float16):
     return wd
 
 
+# umT5-XXL encoder (input_encoders/hf/t5/model.py:498-512 umt5_xxl) and a 2-block, 4-head encoder of the same head dim 64
+T5_DIMS = {
+    "umt5-xxl": dict(vocab=256384, dim=4096, dim_attn=4096, ffn=10240, heads=64, layers=24, buckets=32),
+    "t5-tiny": dict(vocab=384, dim=256, dim_attn=256, ffn=640, heads=4, layers=2, buckets=32),
+}
+
+
+def synth_t5_weights(dims, seed=0, device="cpu"):
+    """The encoder checkpoint (names and shapes of T5Encoder.state_dict() with shared_pos=False: model.py:299-309, T5SelfAttention :184-188), bf16, drawn on
+    `device`.  Standard deviations follow the module's init_weights (:36-53) — embedding 1, k / v / fc1 / gate dim^-1/2, o dim_attn^-1/2, fc2 ffn^-1/2 — except
+    q at 2 (dim 64)^-1/2 (scores O(1) without the softmax scale T5 omits) and the position tables at N(0, 1): a dropped, transposed or sign-flipped bias
+    moves the output far beyond any tolerance.  Norm weights 1 + 0.1 N(0, 1)."""
+    D, A, F, H, L = dims["dim"], dims["dim_attn"], dims["ffn"], dims["heads"], dims["layers"]
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev if dev.type != "cpu" else "cpu").manual_seed(seed + 515)
+    wd = {}
+
+    def rn(shape, std):
+        return _randn(shape, std, gen, dev, torch.bfloat16)
+
+    def norm():
+        return (1.0 + _randn((D,), 0.1, gen, dev, torch.float32)).to(torch.bfloat16)
+
+    wd["token_embedding.weight"] = rn((dims["vocab"], D), 1.0)
+    for i in range(L):
+        p = f"blocks.{i}"
+        wd[f"{p}.norm1.weight"] = norm()
+        wd[f"{p}.attn.q.weight"] = rn((A, D), 2.0 * (D * 64) ** -0.5)
+        wd[f"{p}.attn.k.weight"] = rn((A, D), D**-0.5)
+        wd[f"{p}.attn.v.weight"] = rn((A, D), D**-0.5)
+        wd[f"{p}.attn.o.weight"] = rn((D, A), A**-0.5)
+        wd[f"{p}.norm2.weight"] = norm()
+        wd[f"{p}.ffn.gate.0.weight"] = rn((F, D), D**-0.5)
+        wd[f"{p}.ffn.fc1.weight"] = rn((F, D), D**-0.5)
+        wd[f"{p}.ffn.fc2.weight"] = rn((D, F), F**-0.5)
+        wd[f"{p}.pos_embedding.embedding.weight"] = rn((dims["buckets"], H), 1.0)
+    wd["norm.weight"] = norm()
+    return wd
+
+
 def synth_inputs(dims, target_shape, seed=42, device="cpu"):
     """Latents exactly as the reference seeds them (wan/scheduler.py:25-28,54-63: randn(target_shape),
     fp32, seed 42) but always drawn from the CPU stream so CPU oracle and GPU path see identical noise
-    (SURVEY.md appendix A.10); context/context_null stand in for the T5 output (seeds +1/+2)."""
+    (SURVEY.md appendix A.10); context/context_null stand in for the T5 output (seeds +1/+2; lightx2v_amd.t5 computes the real thing from token ids)."""
     g = torch.Generator().manual_seed(seed)
     latents = torch.randn(*target_shape, generator=g, dtype=torch.float32)
     text_dim = dims.get("text_dim", 4096)

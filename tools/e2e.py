@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """End-to-end wall clock of the hot path on one GPU: the full denoise loop (all infer_steps, CFG) followed by the VAE decode of the
 final latents — the quantity BASELINE.json's north star asks for next to the per-step number ("end-to-end wall-clock and frames/sec").
-Synthetic weights and inputs of the named shape (no text encoder: its output is an input here, as in bench.py).  One JSON line.
+Synthetic weights and inputs of the named shape (the text encoder's output is an input here, as in bench.py, unless --t5 is given).  One JSON line.
     python tools/e2e.py [--workload wan14b_720px81f] [--steps 50] [--fp8|--mxfp8] [--distill] [--teacache T]
     python tools/e2e.py --i2v --image PATH | --encode   (image → CLIP tower + VAE encode → loop → decode; --encode: a seeded synthetic 720p image;
                                                          --clip-ckpt PATH: the CLIP checkpoint instead of seeded synthetic tower weights)
+    python tools/e2e.py --t5   (context / context_null from seeded token ids through the HIP umT5-XXL encoder, seeded weights, timed as t5_encode_s)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/e2e.py --gpus N ...
         (N GPUs of one node: Ulysses sequence parallel denoise loop over RCCL + the halo-split `decode_dist` VAE decode)"""
 import argparse
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
     ap.add_argument("--clip-ckpt", default=None, help="i2v with --image / --encode: CLIP checkpoint (.pth / .safetensors) for the HIP image tower (default: seeded synthetic weights)")
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
+    ap.add_argument("--t5", action="store_true", help="build context / context_null from seeded token ids (77- and 126-token prompts) with the HIP umT5-XXL encoder (seeded weights), timed as t5_encode_s")
     a = ap.parse_args()
     from lightx2v_amd import launch
 
@@ -101,6 +103,16 @@ def main():
             raise SystemExit(f"--image: a {img.shape[2]}x{img.shape[1]} image gives another latent grid than the workload's {tw}x{th} (use the workload's aspect ratio)")
         vae_enc.run_vae_encoder(decoder, img, **enc_args)  # warm-up: allocates the encoder's buffers
         clip.run_image_encoder(clip_model, img.cuda())
+    if a.t5:
+        from lightx2v_amd import t5
+
+        if dims.get("text_dim", 4096) != synth.T5_DIMS["umt5-xxl"]["dim"]:
+            raise SystemExit(f"--t5: the workload's text_dim {dims.get('text_dim')} is not umT5-XXL's {synth.T5_DIMS['umt5-xxl']['dim']}")
+        t5_model = t5.T5EncoderModel(dims.get("text_len", 512), torch.bfloat16, "cuda", synth.synth_t5_weights(synth.T5_DIMS["umt5-xxl"], seed=0, device="cuda"))
+        gt = torch.Generator().manual_seed(7)
+        t5_ids = [torch.randint(1, synth.T5_DIMS["umt5-xxl"]["vocab"], (1, n), generator=gt) for n in (77, 126)]  # prompt, negative prompt
+        t5_args = (t5_ids[0], torch.ones_like(t5_ids[0]), t5_ids[1], torch.ones_like(t5_ids[1]))
+        t5.run_text_encoder(t5_model, *t5_args)  # warm-up: allocates the encoder's workspace
     # warm-up outside the clock: one step on a scratch scheduler state (allocator pools, lazy tables) and a short decode
     sch.step_pre(0)
     model.infer(inputs)
@@ -117,6 +129,10 @@ def main():
             torch.cuda.synchronize()
 
     fence()
+    tt = time.perf_counter()
+    if a.t5:  # WanRunner.run_text_encoder (wan_runner.py:178-191): both prompts in one packed pass
+        inputs["text_encoder_output"] = dict(inputs["text_encoder_output"], **t5.run_text_encoder(t5_model, *t5_args))
+        fence()
     te = time.perf_counter()
     tc = te
     if encode:  # WanRunner.run_image_encoder → run_vae_encoder (wan_runner.py:191-248)
@@ -142,6 +158,8 @@ def main():
         rec.update(clip_encode_s=tc - te, vae_encode_s=t0 - tc, total_with_encode_s=t2 - te,
                    conditioning=(f"image {os.path.basename(a.image)}" if a.image else "seeded synthetic image") + ": clip_encoder_out from the HIP CLIP tower (" +
                    (f"checkpoint {os.path.basename(a.clip_ckpt)}" if a.clip_ckpt else "seeded synthetic weights") + "), vae_encode_out from the HIP VAE encoder")
+    if a.t5:
+        rec.update(t5_encode_s=te - tt, text_conditioning="context / context_null from seeded token ids (77 / 126 tokens) through the HIP umT5-XXL encoder, seeded weights")
     if a.teacache > 0:
         rec_c, rec_u = list(getattr(sch, "caching_records", [])), list(getattr(sch, "caching_records_2", []))
         rec["teacache_forwards_computed"] = int(sum(bool(v) for v in rec_c + rec_u))
