@@ -284,6 +284,57 @@ int x2v_gemm_fp8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kb
                          const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid,
                          int64_t ldr, const void* gate, void* stream);
 
+/* ---- w8a8 int8: the reference's W-int8-channel-sym-A-int8-channel-sym-dynamic-* operators (mm_weight.py:322-354 Vllm, :592-... Sgl-ActVllm;
+ * weight load :185-201, activation quantiser :247-249).  Numeric contract, every fp32 operation IEEE and correctly rounded:
+ *   activation  amax = max|x[m,:]|, scale[m] = amax / 127.0f, inv = 127.0f / amax, q = clamp(rint(float(x) * inv), -128, 127), round half to
+ *               even (restated from vLLM's dynamic scaled_int8_quant(x, scale=None, azp=None, symmetric=True)); an all-zero row gives codes 0
+ *               and scale 0, and no NaN reaches the codes
+ *   weight      per output channel, IntegerQuantizer(8, True, "per_channel"): scale = max(amax, 1e-5) / 127, q = clamp(round(w / scale), -128, 127)
+ *               (done at load by the operator class, or by tools/convert_ckpt.py --linear_dtype torch.int8)
+ *   product     acc_i32 = xq[M,K] . wq[N,K]^T exactly (v_mfma_i32_32x32x32_i8), float(acc) by v_cvt_f32_i32 (round to nearest even), then
+ *               y = epi(float(acc) * sx[m] * sw[n] + bias[n]) -> bf16 in the statement order and with the rounding points of x2v_gemm_fp8
+ * Codes are two's-complement int8 bytes. */
+
+/* Per-token dynamic int8 quantisation (see the contract above).  Arguments and limits of x2v_quant_fp8_rowwise: K % 8 == 0, K <= 16384. */
+int x2v_quant_int8_rowwise(const void* x, int64_t ldx, void* xq, int64_t ldq, float* scale, int64_t M, int K, void* stream);
+
+/* The same reading a K-blocked x and writing row-major codes (see x2v_quant_fp8_rowwise_blocked). */
+int x2v_quant_int8_rowwise_blocked(const void* x, int64_t ldx, int x_kblock, int64_t x_kblock_stride, void* xq, int64_t ldq, float* scale, int64_t M, int K,
+                                   void* stream);
+
+/* x2v_layernorm_bf16 fused with x2v_quant_int8_rowwise on its output, bit-identical to the two calls in sequence.  512 < D <= 16384. */
+int x2v_layernorm_quant_int8(const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift, void* xq, int64_t ldq, float* sx,
+                             int64_t M, int D, float eps, void* stream);
+
+/* y[M,N] = epi(float(xq[M,K] . wq[N,K]^T) * sx[m] * sw[n] + bias[n]) -> bf16 — replaces torch.ops._C.cutlass_scaled_mm on int8 operands
+ * (mm_weight.py:346-353) / sgl_kernel.int8_scaled_mm (:616-...).  Arguments of x2v_gemm_fp8.  K % 128 == 0, N % 8 == 0, K <= 65536 (|acc| < 2^31). */
+int x2v_gemm_int8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                  int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
+
+/* Same, selecting the kernel.  variant & 0xff: 0 = by shape, 1 = the 128x128 kernel (gemm.hip's structure on v_mfma_i32_32x32x32_i8; every legal
+ * shape), 5 = the continuous 256x256 kernel (gemm256ci8.hip: gemm256c8's pipeline and shape conditions — K a multiple of 256 and >= 512, N a multiple
+ * of 256, y blocks that are multiples of 128 columns, resid with y's row stride, a residual row period that is a multiple of 8 and >= 256 — else
+ * X2V_E_SHAPE; bit-equal with variant 1).  Variant 0 takes it where x2v_gemm_fp8's rule takes a 256x256 kernel and these conditions hold.  There is
+ * no int8 ping-pong kernel: 2, 3 and 4 return X2V_E_ARG.  Bits 8..15 = m-tiles per scheduling group of the 256x256 kernel (0 = default). */
+int x2v_gemm_int8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                          int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant,
+                          void* stream);
+
+/* x2v_gemm_int8_variant with X2V_EPI_RESIDUAL and a row period of the residual (see x2v_gemm_bf16_resid_period). */
+int x2v_gemm_int8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                               int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant,
+                               void* stream);
+
+/* x2v_gemm_int8 on block-strided operands (see x2v_gemm_fp8_blocked; x_kblock in codes = bytes, a multiple of 128; sx stays [M]). */
+int x2v_gemm_int8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq, int64_t ldw, const float* sw,
+                          const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid,
+                          int64_t ldr, const void* gate, void* stream);
+
+/* Which kernel variant 0 of x2v_gemm_int8_variant launches for this shape, with x2v_gemm_kernel_choice's convention: low byte = tile family
+ * (1 = the 128x128 kernel, 2 = the 256x256 kernel), bit 8 = its continuous form (the only 256x256 int8 kernel: 2 comes with bit 8), for a
+ * row-major y.  Negative = X2V_E_SHAPE.  Host-only. */
+int x2v_gemm_int8_kernel_choice(int64_t M, int N, int K, int64_t ldx, int64_t ldw);
+
 /* MXFP8 (OCP microscaling) activation / weight quantisation — replaces lightx2v_kernel.gemm.scaled_fp8_quant
  * (lightx2v_kernel/python/lightx2v_kernel/gemm.py:73-83, csrc/gemm/mxfp8_quant_kernels_sm120.cu:139-196): per 32 consecutive K
  * elements one e8m0 scale = the smallest power of two >= max|x|/448, elements = e4m3fn_rne(x / scale).

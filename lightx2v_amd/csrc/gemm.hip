@@ -42,7 +42,9 @@ __device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
 // swizzled byte offset of 16-byte chunk `c` of row `r` in a [rows][128 B] tile
 __device__ __forceinline__ int swz_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
-template <bool FP8, int EPI>
+// I8 (with FP8 = true: the w8a8 operand and scale plumbing): int8 codes on v_mfma_i32_32x32x32_i8, four k-steps of 32 per 128-byte stage row, an
+// exact int32 accumulator converted to fp32 (v_cvt_f32_i32, round to nearest even) in front of the dequantisation.
+template <bool FP8, int EPI, bool I8>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                       const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
                                                       int N, int nk, const unsigned short* __restrict__ resid, int64_t ldr,
@@ -94,25 +96,25 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
   // ---- MFMA fragment read offsets (bytes within a tile image); wave (wr, wc) owns rows wr*64.., cols wc*64..
   const int wr = wid >> 1, wc = wid & 1;
   const int fl = lane & 31, fh = lane >> 5;
-  // chunk order: bf16 step ks (K=16) reads chunk ks*2+fh; fp8 step s (K=64) reads chunks s*4+fh*2+{0,1}.
+  // chunk order: bf16 step ks (K=16) and int8 step ks (K=32) read chunk ks*2+fh; fp8 step s (K=64) reads chunks s*4+fh*2+{0,1}.
   // In both cases A and B use the same (half-wave, element) -> k map, which is all an MFMA requires.
   int a_off[2][4], b_off[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int c = FP8 ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
+      const int c = (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
       a_off[i][ks] = swz_off(wr * 64 + i * 32 + fl, c);
       b_off[i][ks] = swz_off(wc * 64 + i * 32 + fl, c) + GB_M * 128;
     }
 
-  f32x16_t acc[2][2];
+  std::conditional_t<I8, i32x16_t, f32x16_t> acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
 
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -134,6 +136,20 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
+      }
+    } else if constexpr (I8) {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        i32x4_t xa[2], wb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          xa[i] = *reinterpret_cast<const i32x4_t*>(base + a_off[i][ks]);
+          wb[i] = *reinterpret_cast<const i32x4_t*>(base + b_off[i][ks]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wb[j], xa[i], acc[i][j], 0, 0, 0);
       }
     } else {
 #pragma unroll
@@ -194,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
         const int nl = wc * 64 + j * 32 + 8 * g + 4 * fh;
         float vv[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = acc[i][j][4 * g + e];
+        for (int e = 0; e < 4; ++e) vv[e] = (float)acc[i][j][4 * g + e];
         if constexpr (FP8) {
           vv[0] = vv[0] * sxv[i] * swv[j][g].x;
           vv[1] = vv[1] * sxv[i] * swv[j][g].y;
@@ -256,15 +272,15 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
 
 using namespace x2v;
 
-template <bool FP8, int EPI>
+template <bool FP8, int EPI, bool I8 = false>
 static int launch_gemm(const void* x, int64_t ldx_bytes, const void* w, int64_t ldw_bytes, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, hipStream_t st, GemmBlocking gb) {
   const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
   {
-    int rc = ensure_dynamic_lds((const void*)gemm_kernel<FP8, EPI>, G_LDS_BYTES, "gemm attr");
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<FP8, EPI, I8>, G_LDS_BYTES, "gemm attr");
     if (rc != X2V_OK) return rc;
   }
-  hipLaunchKernelGGL((gemm_kernel<FP8, EPI>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)x, ldx_bytes, (const char*)w,
+  hipLaunchKernelGGL((gemm_kernel<FP8, EPI, I8>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)x, ldx_bytes, (const char*)w,
                      ldw_bytes, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)resid, ldr,
                      (const unsigned short*)gate, sx, sw, ntm, ntn, gb);
   X2V_LAUNCH_CHECK("gemm launch");
@@ -508,6 +524,83 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_variant(const
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
                             int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
   return x2v_gemm_fp8_variant(xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
+}
+
+// ---- w8a8 int8 (the reference's W-int8-channel-sym-A-int8-channel-sym-dynamic presets): the fp8 entries' signatures and argument checks, int8 codes,
+//      an exact int32 accumulator.  Two kernels: the 128x128 one (variant 1, every legal shape) and the continuous 256x256 one (gemm256ci8.hip, variant 5,
+//      gemm256c8's shapes); variant 0 chooses with choose_kernel's rule; there is no int8 ping-pong kernel (2, 3, 4: X2V_E_ARG).  K <= 65536 keeps
+//      |acc| <= K * 2^14 below 2^31.  The rule is set from profiles/int8_gemm_bench.json: at the six shapes of the w8a8 step (M = 75 600; K, N in
+//      {5120, 13824}; plain, GELU, gated residual) the continuous kernel takes 0.68-0.73 of the 128x128 kernel's time (1.08-1.11x gemm256c8's), so it
+//      gets every shape the fp8 256x256 kernel gets and its form accepts; below choose_kernel's thresholds the two were not timed against each other.
+static int check_int8_k(const char* who, int K) {
+  X2V_REQUIRE(K <= 65536, X2V_E_SHAPE, "%s: K=%d above 65536 could overflow the int32 accumulator", who, K);
+  return X2V_OK;
+}
+
+static int dispatch_int8(const char* who, int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
+                         const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int variant, hipStream_t st, GemmBlocking gb = GemmBlocking()) {
+  const int kind = variant & 0xff, gm_tiles = (variant >> 8) & 0xff;
+  X2V_REQUIRE(kind == 0 || kind == 1 || kind == 5, X2V_E_ARG, "%s: variant %d: int8 has the 128x128 kernel (1) and the continuous 256x256 form (5) only", who, kind);
+  const bool can_c = spans_fit_256(nk, ldxb, ldwb, gb) && continuous_ok(nk, N, ldy, ldr, resid, gb);
+  X2V_REQUIRE(kind != 5 || can_c, X2V_E_SHAPE,
+              "%s: the continuous 256x256 kernel needs an even number of K tiles >= 4, N %% 256 == 0, y blocks that are multiples of 128 columns, resid with y's row stride, a residual row period that is a multiple of 8 and >= 256, and tile spans below 4 GiB (nk=%d, N=%d, resid_period=%d)",
+              who, nk, N, gb.r_period);
+  if (kind == 5 || (kind == 0 && can_c && choose_kernel(M, N, nk, ldxb, ldwb, true, gb) == 2))
+    return gemm256ci8_dispatch(epilogue, x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, resid, ldr, gate, sx, sw, gm_tiles, st, gb);
+  return with_epilogue(who, epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm<true, decltype(epi)::value, true>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, st, gb);
+  });
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                                                                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant,
+                                                                            void* stream) {
+  int rc = check_operands("gemm_int8", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
+  if (rc == X2V_OK) rc = check_int8_k("gemm_int8", K);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  return dispatch_int8("gemm_int8", epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                                                                    int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return x2v_gemm_int8_variant(xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias,
+                                                                                 void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period,
+                                                                                 const void* gate, int variant, void* stream) {
+  int rc = check_operands("gemm_int8_resid_period", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
+  if (rc == X2V_OK) rc = check_int8_k("gemm_int8_resid_period", K);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_resid_period("gemm_int8_resid_period", y, ldy, M, N, resid, ldr, resid_period, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  return dispatch_int8("gemm_int8_resid_period", X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq,
+                                                                            int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock,
+                                                                            int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr,
+                                                                            const void* gate, void* stream) {
+  int rc = check_operands("gemm_int8_blocked", true, true, xq, ldx, (x_kblock > 0 ? x_kblock : K), sx, wq, ldw, sw, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
+  if (rc == X2V_OK) rc = check_int8_k("gemm_int8_blocked", K);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_blocking("gemm_int8_blocked", K, x_kblock, x_kblock_stride, N, y_nblock, y_nblock_stride, epilogue, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  return dispatch_int8("gemm_int8_blocked", epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
+}
+
+// the int8 twin of x2v_gemm_kernel_choice: low byte = tile family (1: the 128x128 kernel, 2: the 256x256 one), bit 8 = its continuous form — the only
+// 256x256 int8 kernel, so 2 always comes with it; for a row-major y (ldy == N) and no residual, as there
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_kernel_choice(int64_t M, int N, int K, int64_t ldx, int64_t ldw) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 128 != 0 || K > 65536 || ldx < K || ldw < K) return X2V_E_SHAPE;
+  const int nk = K / 128;
+  const bool c = choose_kernel(M, N, nk, ldx, ldw, true) == 2 && continuous_ok(nk, N, N, N, nullptr, GemmBlocking());
+  return c ? (2 | 0x100) : 1;
 }
 
 // v projection with V^T output (the operand of x2v_attn_fwd_bf16_vt) straight from the GEMM epilogue: only the single-stream 256x256 kernel

@@ -27,6 +27,10 @@ int gemm256c_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, 
 int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
 
+// gemm256ci8.hip: the same continuous pipeline for the w8a8 int8 operator (v_mfma_i32_32x32x32_i8, int32 accumulators)
+int gemm256ci8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
+                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
+
 // ---- host: run-time epilogue -> template argument.  f(integral_constant<int, EPI>, resid, ldr, gate); the non-residual epilogues get no residual.
 template <class F>
 int with_epilogue(const char* who, int epilogue, const void* resid, int64_t ldr, const void* gate, F&& f) {

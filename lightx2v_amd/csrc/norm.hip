@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "quant_int8.h"
 #include "x2v_common.h"
 
 namespace x2v {
@@ -156,8 +157,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const unsigned short* __
 // bf16 activation never goes to HBM, and the one quantised copy serves every projection that consumes it.  The normalised values are
 // rounded to bf16 exactly where layernorm_kernel rounds them (same expression order), so codes and scales are bit-identical to
 // x2v_layernorm_bf16 followed by x2v_quant_fp8_rowwise.  One block per row.
-template <int CH>
-__global__ __launch_bounds__(256) void layernorm_fp8_kernel(const unsigned short* __restrict__ x, int64_t ldx, const unsigned short* __restrict__ w,
+// I8: the same in front of the per-token int8 quantiser (quant_int8.h; x2v_layernorm_quant_int8 == x2v_layernorm_bf16 + x2v_quant_int8_rowwise).
+template <int CH, bool I8>
+__global__ __launch_bounds__(256) void layernorm_quant_kernel(const unsigned short* __restrict__ x, int64_t ldx, const unsigned short* __restrict__ w,
                                                             const unsigned short* __restrict__ b, const unsigned short* __restrict__ scale,
                                                             const unsigned short* __restrict__ shift, unsigned char* __restrict__ xq, int64_t ldq,
                                                             float* __restrict__ sx, int D, float eps) {
@@ -223,21 +225,32 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const unsigned short
     }
   }
   amax = block_max<4>(amax, red);
-  const float qs = fmaxf(amax / 448.0f, 1.0f / (448.0f * 512.0f));  // quant_fp8_rowwise_kernel's scale rule
-  if (t == 0) sx[row] = qs;
+  if constexpr (I8) {
+    if (t == 0) sx[row] = int8_scale(amax);
+    const float inv = int8_inv_scale(amax);
 #pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    if (!r.ok[c]) continue;
-    const int e = (c * 256 + t) * 8;
-    float v[8];
+    for (int c = 0; c < CH; ++c) {
+      if (!r.ok[c]) continue;
+      const int e = (c * 256 + t) * 8;
+      *reinterpret_cast<uint2*>(xq + row * ldq + e) = int8_codes8(r.v[c], inv);
+    }
+  } else {
+    const float qs = fmaxf(amax / 448.0f, 1.0f / (448.0f * 512.0f));  // quant_fp8_rowwise_kernel's scale rule
+    if (t == 0) sx[row] = qs;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = fminf(fmaxf(r.v[c][j] / qs, -448.f), 448.f);
-    unsigned lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-    *reinterpret_cast<uint2*>(xq + row * ldq + e) = make_uint2(lo, hi);
+    for (int c = 0; c < CH; ++c) {
+      if (!r.ok[c]) continue;
+      const int e = (c * 256 + t) * 8;
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = fminf(fmaxf(r.v[c][j] / qs, -448.f), 448.f);
+      unsigned lo = 0, hi = 0;
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
+      *reinterpret_cast<uint2*>(xq + row * ldq + e) = make_uint2(lo, hi);
+    }
   }
 }
 
@@ -795,23 +808,34 @@ extern "C" __attribute__((visibility("default"))) int x2v_layernorm_bf16_variant
   return X2V_OK;
 }
 
-extern "C" __attribute__((visibility("default"))) int x2v_layernorm_quant_fp8(const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift,
-                                                                              void* xq, int64_t ldq, float* sx, int64_t M, int D, float eps, void* stream) {
-  X2V_REQUIRE(x && xq && sx, X2V_E_ARG, "layernorm_quant_fp8: null pointer");
-  X2V_REQUIRE((scale == nullptr) == (shift == nullptr), X2V_E_ARG, "layernorm_quant_fp8: scale and shift must be given together");
-  X2V_REQUIRE(D > 512 && D % 8 == 0 && D <= 16384, X2V_E_SHAPE, "layernorm_quant_fp8: D=%d must be a multiple of 8 in (512, 16384] (smaller rows: call the two kernels)", D);
+template <bool I8>
+static int layernorm_quant(const char* who, const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift, void* xq, int64_t ldq, float* sx, int64_t M,
+                           int D, float eps, void* stream) {
+  X2V_REQUIRE(x && xq && sx, X2V_E_ARG, "%s: null pointer", who);
+  X2V_REQUIRE((scale == nullptr) == (shift == nullptr), X2V_E_ARG, "%s: scale and shift must be given together", who);
+  X2V_REQUIRE(D > 512 && D % 8 == 0 && D <= 16384, X2V_E_SHAPE, "%s: D=%d must be a multiple of 8 in (512, 16384] (smaller rows: call the two kernels)", who, D);
   X2V_REQUIRE(ldx % 8 == 0 && ldq % 8 == 0 && aligned16(x) && ((uintptr_t)xq % 8) == 0 && aligned16(w) && aligned16(b) && aligned16(scale) && aligned16(shift), X2V_E_ALIGN,
-              "layernorm_quant_fp8: row alignment");
+              "%s: row alignment", who);
   if (M <= 0) return X2V_OK;
   const int ch = chunks_for(D, 4);
   int rc = dispatch_ch(ch, D, [&](auto chc) {
     constexpr int CH = decltype(chc)::value;
-    hipLaunchKernelGGL((layernorm_fp8_kernel<CH>), dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, (const unsigned short*)w,
+    hipLaunchKernelGGL((layernorm_quant_kernel<CH, I8>), dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, (const unsigned short*)w,
                        (const unsigned short*)b, (const unsigned short*)scale, (const unsigned short*)shift, (unsigned char*)xq, ldq, sx, D, eps);
   });
   if (rc != X2V_OK) return rc;
-  X2V_LAUNCH_CHECK("layernorm_quant_fp8 launch");
+  X2V_LAUNCH_CHECK(I8 ? "layernorm_quant_int8 launch" : "layernorm_quant_fp8 launch");
   return X2V_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_layernorm_quant_fp8(const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift,
+                                                                              void* xq, int64_t ldq, float* sx, int64_t M, int D, float eps, void* stream) {
+  return layernorm_quant<false>("layernorm_quant_fp8", x, ldx, w, b, scale, shift, xq, ldq, sx, M, D, eps, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_layernorm_quant_int8(const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift,
+                                                                               void* xq, int64_t ldq, float* sx, int64_t M, int D, float eps, void* stream) {
+  return layernorm_quant<true>("layernorm_quant_int8", x, ldx, w, b, scale, shift, xq, ldq, sx, M, D, eps, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_layernorm_bf16(const void* x, int64_t ldx, const void* w, const void* b, const void* scale, const void* shift, void* y,

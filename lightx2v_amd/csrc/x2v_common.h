@@ -15,6 +15,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
+typedef int i32x16_t __attribute__((ext_vector_type(16)));
 
 constexpr int kWave = 64;  // CDNA wavefront width
 

@@ -65,6 +65,15 @@ PROTOTYPES = {
     "x2v_gemm_mxfp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
     "x2v_gemm_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_fp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
+    "x2v_quant_int8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_quant_int8_rowwise_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_layernorm_quant_int8": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _f32, _c_void_p],
+    "x2v_gemm_int8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "x2v_gemm_int8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
+    "x2v_gemm_int8_resid_period": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i64, _c_void_p, _i32, _c_void_p],
+    "x2v_gemm_int8_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64,
+                              _c_void_p, _c_void_p],
+    "x2v_gemm_int8_kernel_choice": [_i64, _i32, _i32, _i64, _i64],
     "x2v_unipc_step_f32": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, ctypes.POINTER(_f32), _i32, _i32, _i64,
                            _c_void_p],
     "x2v_distill_step_f32": [_c_void_p, _c_void_p, _f32, _c_void_p, _i32, _c_void_p, _f32, _f32, _f32, _c_void_p, _c_void_p, _i64, _c_void_p],
@@ -533,9 +542,23 @@ def attention(q, k, v, num_heads, head_dim=128, scale=0.0, out=None, variant=0, 
     return out2
 
 
-def quant_fp8_rowwise(x):
-    """(e4m3 codes [M, K] row-major, fp32 scales [M, 1]) of a bf16 x [M, K] — or of a K-blocked x [B, M, K/B] (the Ulysses head->seq receive
-    buffer; x2v_quant_fp8_rowwise_blocked: the codes come out row-major, the de-blocking rides in the quantisation pass)."""
+# The two w8a8 code types: torch dtype of the codes, what the error messages call it, the tag in the wrappers' names, and the C entries.  The fp8 and
+# int8 wrappers below are the same argument checks over these.
+class _W8A8:
+    def __init__(self, dtype, dtype_name, tag, quant_blocked, layernorm_quant, gemm_variant, gemm_resid_period, gemm_blocked):
+        self.dtype, self.dtype_name, self.tag = dtype, dtype_name, tag
+        self.quant_blocked, self.layernorm_quant = quant_blocked, layernorm_quant
+        self.gemm_variant, self.gemm_resid_period, self.gemm_blocked = gemm_variant, gemm_resid_period, gemm_blocked
+
+
+_FP8 = _W8A8(torch.float8_e4m3fn, "float8_e4m3fn (OCP; gfx950)", "fp8", _lib.x2v_quant_fp8_rowwise_blocked, _lib.x2v_layernorm_quant_fp8, _lib.x2v_gemm_fp8_variant,
+             _lib.x2v_gemm_fp8_resid_period, _lib.x2v_gemm_fp8_blocked)
+_INT8 = _W8A8(torch.int8, "int8", "int8", _lib.x2v_quant_int8_rowwise_blocked, _lib.x2v_layernorm_quant_int8, _lib.x2v_gemm_int8_variant,
+              _lib.x2v_gemm_int8_resid_period, _lib.x2v_gemm_int8_blocked)
+
+
+def _quant8_rowwise(x, kind):
+    dtype, tag = kind.dtype, kind.tag
     if x.dim() == 3:
         kb, kbs, ldx = _blocks3d(_bf16(x, "x"), "x")
         M, K = x.shape[1], kb * x.shape[0]
@@ -543,33 +566,55 @@ def quant_fp8_rowwise(x):
     else:
         x2 = _row2d(_bf16(x, "x"), "x")
         (M, K), kb, kbs, ldx = x2.shape, 0, 0, x2.stride(0)
-    xq = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    xq = torch.empty((M, K), dtype=dtype, device=x.device)
     s = torch.empty((M, 1), dtype=torch.float32, device=x.device)
     init()
     if M == 0:
         return xq, s
-    _check(_lib.x2v_quant_fp8_rowwise_blocked(_p(x2), ldx, kb, kbs, _p(xq), xq.stride(0), _p(s), M, K, _stream()), "quant_fp8_rowwise")
+    _check(kind.quant_blocked(_p(x2), ldx, kb, kbs, _p(xq), xq.stride(0), _p(s), M, K, _stream()), f"quant_{tag}_rowwise")
+    return xq, s
+
+
+def quant_fp8_rowwise(x):
+    """(e4m3 codes [M, K] row-major, fp32 scales [M, 1]) of a bf16 x [M, K] — or of a K-blocked x [B, M, K/B] (the Ulysses head->seq receive
+    buffer; x2v_quant_fp8_rowwise_blocked: the codes come out row-major, the de-blocking rides in the quantisation pass)."""
+    return _quant8_rowwise(x, _FP8)
+
+
+def quant_int8_rowwise(x):
+    """quant_fp8_rowwise for the int8 operator: (int8 codes [M, K] row-major, fp32 scales [M, 1] = amax / 127) — x2v_quant_int8_rowwise_blocked."""
+    return _quant8_rowwise(x, _INT8)
+
+
+def _layernorm_quant8(x, weight, bias, scale, shift, eps, kind):
+    dtype, tag = kind.dtype, kind.tag
+    x2 = _row2d(_bf16(x, "x"), "x")
+    M, D = x2.shape
+    if D <= 512:
+        return _quant8_rowwise(layernorm(x2, weight, bias, scale, shift, eps), kind)
+    if (scale is None) != (shift is None):
+        raise X2VError(f"layernorm_quant_{tag}: scale and shift must be given together")
+    weight, bias = _vec(weight, "layernorm weight", D), _vec(bias, "layernorm bias", D)
+    scale, shift = _vec(scale, "layernorm scale", D), _vec(shift, "layernorm shift", D)
+    xq = torch.empty((M, D), dtype=dtype, device=x.device)
+    s = torch.empty((M, 1), dtype=torch.float32, device=x.device)
+    init()
+    if M == 0:
+        return xq, s
+    _check(kind.layernorm_quant(_p(x2), x2.stride(0), _p(weight), _p(bias), _p(scale), _p(shift), _p(xq), xq.stride(0), _p(s), M, D, eps, _stream()),
+           f"layernorm_quant_{tag}")
     return xq, s
 
 
 def layernorm_quant_fp8(x, weight=None, bias=None, scale=None, shift=None, eps=1e-6):
     """(e4m3 codes [M, D], fp32 scales [M, 1]) of LN(x)[*w+b][*(1+scale)+shift] — x2v_layernorm_quant_fp8, bit-identical to
     quant_fp8_rowwise(layernorm(...)).  Rows of <= 512 elements go through the two kernels."""
-    x2 = _row2d(_bf16(x, "x"), "x")
-    M, D = x2.shape
-    if D <= 512:
-        return quant_fp8_rowwise(layernorm(x2, weight, bias, scale, shift, eps))
-    if (scale is None) != (shift is None):
-        raise X2VError("layernorm_quant_fp8: scale and shift must be given together")
-    weight, bias = _vec(weight, "layernorm weight", D), _vec(bias, "layernorm bias", D)
-    scale, shift = _vec(scale, "layernorm scale", D), _vec(shift, "layernorm shift", D)
-    xq = torch.empty((M, D), dtype=torch.float8_e4m3fn, device=x.device)
-    s = torch.empty((M, 1), dtype=torch.float32, device=x.device)
-    init()
-    if M == 0:
-        return xq, s
-    _check(_lib.x2v_layernorm_quant_fp8(_p(x2), x2.stride(0), _p(weight), _p(bias), _p(scale), _p(shift), _p(xq), xq.stride(0), _p(s), M, D, eps, _stream()), "layernorm_quant_fp8")
-    return xq, s
+    return _layernorm_quant8(x, weight, bias, scale, shift, eps, _FP8)
+
+
+def layernorm_quant_int8(x, weight=None, bias=None, scale=None, shift=None, eps=1e-6):
+    """layernorm_quant_fp8 for the int8 operator — x2v_layernorm_quant_int8, bit-identical to quant_int8_rowwise(layernorm(...))."""
+    return _layernorm_quant8(x, weight, bias, scale, shift, eps, _INT8)
 
 
 def quant_mxfp8(x):
@@ -640,87 +685,117 @@ def gemm_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogu
     return out2
 
 
-def gemm_fp8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0, resid_period=0):
-    """resid_period: as gemm() (x2v_gemm_fp8_resid_period)."""
+def _gemm8(kind, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period):
+    dtype, dtype_name, tag = kind.dtype, kind.dtype_name, kind.tag
     M, K = xq.shape
     N = wq_nk.shape[0]
-    if xq.dtype != torch.float8_e4m3fn or wq_nk.dtype != torch.float8_e4m3fn:
-        raise X2VError("gemm_fp8: operands must be float8_e4m3fn (OCP; gfx950)")
+    if xq.dtype != dtype or wq_nk.dtype != dtype:
+        raise X2VError(f"gemm_{tag}: operands must be {dtype_name}")
     if resid_period:
         if epilogue != EPI_RESIDUAL or resid is None:
-            raise X2VError("gemm_fp8: resid_period needs the residual epilogue")
-        out2, r2 = _resid_period_out("gemm_fp8", resid, resid_period, out, M, N, xq)
-        gate = _vec(gate, "gemm_fp8 gate", N)
+            raise X2VError(f"gemm_{tag}: resid_period needs the residual epilogue")
+        out2, r2 = _resid_period_out(f"gemm_{tag}", resid, resid_period, out, M, N, xq)
+        gate = _vec(gate, f"gemm_{tag} gate", N)
     elif epilogue == EPI_RESIDUAL:
         out2 = _row2d(resid if out is None else out, "out")
         r2 = _row2d(_bf16(resid, "resid"), "resid")
-        gate = _vec(gate, "gemm_fp8 gate", N)
+        gate = _vec(gate, f"gemm_{tag} gate", N)
     else:
         out2 = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device) if out is None else _row2d(out, "out")
         r2 = None
     if wq_nk.shape[1] != K or not xq.is_cuda or not wq_nk.is_cuda or xq.stride(1) != 1 or wq_nk.stride(1) != 1:
-        raise X2VError(f"gemm_fp8: xq {tuple(xq.shape)} / wq {tuple(wq_nk.shape)} must be device matrices with unit inner stride and equal K")
-    sw, sx = _vec(sw, "gemm_fp8 weight scales", N, torch.float32), _vec(sx, "gemm_fp8 activation scales", M, torch.float32)
-    bias = _vec(bias, "gemm_fp8 bias", N)
+        raise X2VError(f"gemm_{tag}: xq {tuple(xq.shape)} / wq {tuple(wq_nk.shape)} must be device matrices with unit inner stride and equal K")
+    sw, sx = _vec(sw, f"gemm_{tag} weight scales", N, torch.float32), _vec(sx, f"gemm_{tag} activation scales", M, torch.float32)
+    bias = _vec(bias, f"gemm_{tag} bias", N)
     init()
     if M == 0:
         return out2
     if resid_period:
-        _check(_lib.x2v_gemm_fp8_resid_period(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, _p(r2), r2.stride(0),
-                                              resid_period, _p(gate), variant, _stream()), "gemm_fp8_resid_period")
+        _check(kind.gemm_resid_period(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, _p(r2), r2.stride(0),
+                                              resid_period, _p(gate), variant, _stream()), f"gemm_{tag}_resid_period")
         return out2
     _check(
-        _lib.x2v_gemm_fp8_variant(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, epilogue, _p(r2), 0 if r2 is None else r2.stride(0), _p(gate), variant, _stream()),
-        "gemm_fp8",
+        kind.gemm_variant(_p(xq), xq.stride(0), _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out2), out2.stride(0), M, N, K, epilogue, _p(r2), 0 if r2 is None else r2.stride(0), _p(gate), variant, _stream()),
+        f"gemm_{tag}",
     )
     return out2
+
+
+def gemm_fp8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0, resid_period=0):
+    """resid_period: as gemm() (x2v_gemm_fp8_resid_period)."""
+    return _gemm8(_FP8, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period)
+
+
+def gemm_int8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None, variant=0, resid_period=0):
+    """epi(float(xq . wq^T) * sx * sw + bias) -> bf16 on int8 codes with an exact int32 accumulator (x2v_gemm_int8_variant / _resid_period);
+    arguments as gemm_fp8.  variant: 1 = the 128x128 kernel (every legal shape), 5 = the continuous 256x256 kernel (X2VError where the shape does not
+    allow it), 0 = chosen by shape (gemm_int8_kernel_choice tells which); 2, 3, 4 are refused: there is no int8 ping-pong kernel."""
+    return _gemm8(_INT8, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period)
+
+
+def gemm_int8_kernel_choice(M, N, K, ldx=None, ldw=None, with_form=False):
+    """gemm_kernel_choice for gemm_int8's variant 0 (x2v_gemm_int8_kernel_choice)."""
+    rc = _lib.x2v_gemm_int8_kernel_choice(M, N, K, K if ldx is None else ldx, K if ldw is None else ldw)
+    if rc < 0:
+        raise X2VError(f"gemm_int8_kernel_choice: bad shape M={M} N={N} K={K}")
+    return (rc & 0xff, bool(rc & 0x100)) if with_form else rc & 0xff
+
+
+def _gemm8_blocked(kind, xq, sx, wq_nk, sw, bias, epilogue, out, resid, gate):
+    dtype, tag = kind.dtype, kind.tag
+    if wq_nk.dtype != dtype or xq.dtype != dtype or wq_nk.dim() != 2 or wq_nk.stride(1) != 1 or not wq_nk.is_cuda or not xq.is_cuda:
+        raise X2VError(f"gemm_{tag}_blocked: operands must be {str(dtype).removeprefix('torch.')} device tensors (weight [N, K] with unit inner stride)")
+    N, K = wq_nk.shape
+    if xq.dim() == 3:
+        kb, kbs, ldx = _blocks3d(xq, "xq")
+        M = xq.shape[1]
+        if kb * xq.shape[0] != K:
+            raise X2VError(f"gemm_{tag}_blocked: xq blocks {tuple(xq.shape)} do not make K={K}")
+    else:
+        if xq.dim() != 2 or xq.stride(1) != 1 or xq.shape[1] != K:
+            raise X2VError(f"gemm_{tag}_blocked: xq {tuple(xq.shape)} vs weight [{N},{K}]")
+        kb, kbs, ldx, M = 0, 0, xq.stride(0), xq.shape[0]
+    r2 = None
+    if epilogue == EPI_RESIDUAL:
+        if resid is None:
+            raise X2VError(f"gemm_{tag}_blocked: residual epilogue needs resid")
+        r2 = _row2d(_bf16(resid, "resid"), "resid")
+        out = resid if out is None else out
+        gate = _vec(gate, f"gemm_{tag}_blocked gate", N)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    if out.dim() == 3:
+        nb, nbs, ldy = _blocks3d(_bf16(out, "out"), "out")
+        if nb * out.shape[0] != N or out.shape[1] != M:
+            raise X2VError(f"gemm_{tag}_blocked: out blocks {tuple(out.shape)} do not make [{M}, {N}]")
+    else:
+        o2 = _row2d(_bf16(out, "out"), "out")
+        nb, nbs, ldy = 0, 0, o2.stride(0)
+        if tuple(o2.shape) != (M, N):
+            raise X2VError(f"gemm_{tag}_blocked: out is {tuple(o2.shape)}, expected {(M, N)}")
+    sw, sx = _vec(sw, f"gemm_{tag}_blocked weight scales", N, torch.float32), _vec(sx, f"gemm_{tag}_blocked activation scales", M, torch.float32)
+    bias = _vec(bias, f"gemm_{tag}_blocked bias", N)
+    init()
+    if M == 0:
+        return out
+    _check(
+        kind.gemm_blocked(_p(xq), ldx, kb, kbs, _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out), ldy, nb, nbs, M, N, K, epilogue, _p(r2),
+                                  0 if r2 is None else r2.stride(0), _p(gate) if epilogue == EPI_RESIDUAL else None, _stream()),
+        f"gemm_{tag}_blocked",
+    )
+    return out
 
 
 def gemm_fp8_blocked(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, out=None, resid=None, gate=None):
     """x2v_gemm_fp8_blocked: the w8a8 GEMM on block-strided operands (see gemm_blocked).  `xq`: e4m3 codes [M, K] or K-blocked [B, M, K/B]
     (the codes of the ROW's quantisation, `sx` [M] stays per row); `out`: None / [M, N] or N-blocked [B', M, N/B'] (preallocated); the residual
     epilogue needs a row-major `resid` (= the output).  Returns the output tensor."""
-    if wq_nk.dtype != torch.float8_e4m3fn or xq.dtype != torch.float8_e4m3fn or wq_nk.dim() != 2 or wq_nk.stride(1) != 1 or not wq_nk.is_cuda or not xq.is_cuda:
-        raise X2VError("gemm_fp8_blocked: operands must be float8_e4m3fn device tensors (weight [N, K] with unit inner stride)")
-    N, K = wq_nk.shape
-    if xq.dim() == 3:
-        kb, kbs, ldx = _blocks3d(xq, "xq")
-        M = xq.shape[1]
-        if kb * xq.shape[0] != K:
-            raise X2VError(f"gemm_fp8_blocked: xq blocks {tuple(xq.shape)} do not make K={K}")
-    else:
-        if xq.dim() != 2 or xq.stride(1) != 1 or xq.shape[1] != K:
-            raise X2VError(f"gemm_fp8_blocked: xq {tuple(xq.shape)} vs weight [{N},{K}]")
-        kb, kbs, ldx, M = 0, 0, xq.stride(0), xq.shape[0]
-    r2 = None
-    if epilogue == EPI_RESIDUAL:
-        if resid is None:
-            raise X2VError("gemm_fp8_blocked: residual epilogue needs resid")
-        r2 = _row2d(_bf16(resid, "resid"), "resid")
-        out = resid if out is None else out
-        gate = _vec(gate, "gemm_fp8_blocked gate", N)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
-    if out.dim() == 3:
-        nb, nbs, ldy = _blocks3d(_bf16(out, "out"), "out")
-        if nb * out.shape[0] != N or out.shape[1] != M:
-            raise X2VError(f"gemm_fp8_blocked: out blocks {tuple(out.shape)} do not make [{M}, {N}]")
-    else:
-        o2 = _row2d(_bf16(out, "out"), "out")
-        nb, nbs, ldy = 0, 0, o2.stride(0)
-        if tuple(o2.shape) != (M, N):
-            raise X2VError(f"gemm_fp8_blocked: out is {tuple(o2.shape)}, expected {(M, N)}")
-    sw, sx = _vec(sw, "gemm_fp8_blocked weight scales", N, torch.float32), _vec(sx, "gemm_fp8_blocked activation scales", M, torch.float32)
-    bias = _vec(bias, "gemm_fp8_blocked bias", N)
-    init()
-    if M == 0:
-        return out
-    _check(
-        _lib.x2v_gemm_fp8_blocked(_p(xq), ldx, kb, kbs, _p(sx), _p(wq_nk), wq_nk.stride(0), _p(sw), _p(bias), _p(out), ldy, nb, nbs, M, N, K, epilogue, _p(r2),
-                                  0 if r2 is None else r2.stride(0), _p(gate) if epilogue == EPI_RESIDUAL else None, _stream()),
-        "gemm_fp8_blocked",
-    )
-    return out
+    return _gemm8_blocked(_FP8, xq, sx, wq_nk, sw, bias, epilogue, out, resid, gate)
+
+
+def gemm_int8_blocked(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, out=None, resid=None, gate=None):
+    """gemm_fp8_blocked on int8 codes (x2v_gemm_int8_blocked)."""
+    return _gemm8_blocked(_INT8, xq, sx, wq_nk, sw, bias, epilogue, out, resid, gate)
 
 
 def sinusoid_embed(t, dim):

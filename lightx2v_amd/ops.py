@@ -4,7 +4,7 @@ Every class honours the reference's duck-typed protocol — ctor signature, `set
 `apply(...)`, `to_cuda/to_cpu`, `state_dict`, `clear`, `_calculate_size` — and is registered under new keys,
 so an unchanged LightX2V config selects them by string:
 
-    mm_config.mm_type      = "Hip-bf16" | "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip"
+    mm_config.mm_type      = "Hip-bf16" | "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip" | "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip"
     self_attn_1_type / cross_attn_1_type / attention_type = "hip_flash"
     RMS / LN registries    : key "hip"   (also aliased as "Default"/"sgl-kernel" inside this package, since the
                              reference's weight classes hard-code those keys: transformer_weights.py:127,159,167)
@@ -146,14 +146,16 @@ class MMWeightFp8Hip(_Movable):
         """LayerNorm (+affine, +modulate) and `quantize_input` of its output in one kernel (bit-identical to the two in sequence)."""
         return lib.layernorm_quant_fp8(x, weight, bias, scale, shift, eps)
 
+    _gemm, _gemm_blocked = staticmethod(lib.gemm_fp8), staticmethod(lib.gemm_fp8_blocked)  # the kernels of the code type (MMWeightInt8Hip: int8)
+
     def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None, quantized=None, resid_period=0):
         xq, sx = self.quantize_input(input_tensor) if quantized is None else quantized
         w, sw, b = self.weight, self.weight_scale, self.bias
         if row_slice is not None:
             w, sw, b = w[row_slice], sw[row_slice], (None if b is None else b[row_slice])
         if out is not None and out.dim() == 3:  # N-blocked y: a seq->head send buffer [N, S/N, (H/N) d]
-            return lib.gemm_fp8_blocked(xq, sx, w, sw, b, epilogue=epilogue, out=out)
-        return lib.gemm_fp8(xq, sx, w, sw, b, epilogue=epilogue, resid=resid, gate=gate, out=out, resid_period=resid_period)
+            return self._gemm_blocked(xq, sx, w, sw, b, epilogue=epilogue, out=out)
+        return self._gemm(xq, sx, w, sw, b, epilogue=epilogue, resid=resid, gate=gate, out=out, resid_period=resid_period)
 
     def state_dict(self, destination=None):
         destination = {} if destination is None else destination
@@ -162,6 +164,37 @@ class MMWeightFp8Hip(_Movable):
         if self.bias is not None:
             destination[self.bias_name] = self.bias.cpu().detach().clone()
         return destination
+
+
+@MM_WEIGHT_REGISTER("W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip")
+class MMWeightInt8Hip(MMWeightFp8Hip):
+    """reference: mm_weight.py:111-284 (template) + :322-354 (Vllm) / :592-... (Sgl-ActVllm): int8 weight [N,K] with fp32 per-out-channel scale
+    `<name>.weight_scale` [N,1] (what tools/convert_ckpt.py --linear_dtype torch.int8 writes) or `weight_auto_quant` from bf16 (:185-201);
+    per-token dynamic symmetric activation quant (:247-249); scaled GEMM with an exact int32 accumulator.  MMWeightFp8Hip's protocol — the fused
+    drivers dispatch on the same attributes — over the int8 kernels."""
+
+    def load(self, weight_dict):
+        w = weight_dict[self.weight_name]
+        if self.config.get("weight_auto_quant", False) or w.dtype != torch.int8:
+            wf = w.to(torch.float32)
+            # quant_utils.py:93-113, IntegerQuantizer(8, True, "per_channel").  A tensor divisor for MMWeightFp8Hip.load's reason
+            scale = wf.abs().amax(dim=1, keepdim=True).clamp(min=1e-5) / torch.tensor(127.0, dtype=torch.float32, device=wf.device)
+            self.weight = torch.round(wf / scale).clamp(-128, 127).to(torch.int8).contiguous()
+            self.weight_scale = scale.to(torch.float32)
+        else:
+            self.weight = w.contiguous()
+            self.weight_scale = weight_dict[self.weight_scale_name].float()
+        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
+
+    def quantize_input(self, input_tensor):
+        """Per-token dynamic int8 quantisation of an activation (mm_weight.py:247-249): (codes, fp32 scales)."""
+        return lib.quant_int8_rowwise(input_tensor)
+
+    @staticmethod
+    def layernorm_quantize(x, weight=None, bias=None, scale=None, shift=None, eps=1e-6):
+        return lib.layernorm_quant_int8(x, weight, bias, scale, shift, eps)
+
+    _gemm, _gemm_blocked = staticmethod(lib.gemm_int8), staticmethod(lib.gemm_int8_blocked)
 
 
 # ------------------------------------------------------------------------------------------------ norms

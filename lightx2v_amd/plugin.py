@@ -7,7 +7,7 @@
     x2v.use_hip_clip_encoder()             # optional: WanRunner.load_image_encoder builds the HIP CLIP image tower (i2v)
 
 After that an unchanged LightX2V config selects the HIP path by string:
-    "mm_config": {"mm_type": "Hip-bf16"}   (or "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip")
+    "mm_config": {"mm_type": "Hip-bf16"}   (or "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip" / "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip")
     "self_attn_1_type": "hip_flash", "cross_attn_1_type": "hip_flash", "attention_type": "hip_flash"
 """
 from . import hunyuan, ops, wan
@@ -22,6 +22,7 @@ def register_into_reference():
     for reg, key, cls in (
         (rf.MM_WEIGHT_REGISTER, "Hip-bf16", ops.MMWeightHip),
         (rf.MM_WEIGHT_REGISTER, "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip", ops.MMWeightFp8Hip),
+        (rf.MM_WEIGHT_REGISTER, "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip", ops.MMWeightInt8Hip),
         (rf.MM_WEIGHT_REGISTER, "W-mxfp8-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp8Hip),
         (rf.ATTN_WEIGHT_REGISTER, "hip_flash", ops.HipFlashAttnWeight),
         (rf.RMS_WEIGHT_REGISTER, "hip", ops.RMSWeightHip),

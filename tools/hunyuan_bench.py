@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times one HunyuanVideo-13B denoise step (HIP path) on a synthetic 720p x 129-frame latent (BASELINE config #5 on
 one GPU: 118 800 image + 256 text tokens, 20 double + 40 single blocks) with seeded random weights.
-    python tools/hunyuan_bench.py [--workload hunyuan13b_720px129f] [--steps 1] [--warmup 1]
+    python tools/hunyuan_bench.py [--workload hunyuan13b_720px129f] [--steps 1] [--warmup 1] [--int8]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/hunyuan_bench.py --gpus N
         (config #5 as specified: Ulysses over RCCL, latent grid split along h or w, 24 heads -> N in {1, 2, 3, 4, 6, 8})"""
 import argparse
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--int8", action="store_true", help="linear layers as w8a8 int8 (the reference's configs/quantization/hunyuan_i2v.json operator), weights quantised at load; not yet run on a GPU")
     a = ap.parse_args()
     from lightx2v_amd import launch
 
@@ -47,7 +48,8 @@ def main():
     lib.init(local_rank)
     wl = synth.HUNYUAN_WORKLOADS[a.workload]
     dims = synth.HUNYUAN_DIMS[wl["model"]]
-    cfg = hy.default_config(dims, infer_steps=50)
+    extra = {"mm_config": {"mm_type": "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip", "weight_auto_quant": True}} if a.int8 else {}
+    cfg = hy.default_config(dims, infer_steps=50, **extra)
     wd = synth.synth_hunyuan_weights(dims, seed=0, device="cuda", gen_device="cuda")
     model = hy.HunyuanModel(cfg, wd)
     del wd
@@ -105,7 +107,8 @@ def main():
     n_img = t * (h // 2) * (w // 2)
     fl = step_flops(dims, n_img, dims["text_len"])
     if rank == 0:
-        print(json.dumps({"workload": a.workload, "n_gpus": world, "parallelism": f"ulysses-sp{world}" if world > 1 else "single", "tokens": n_img + dims["text_len"],
+        print(json.dumps({"workload": a.workload, "n_gpus": world, "parallelism": f"ulysses-sp{world}" if world > 1 else "single", "gemm_dtype": "int8" if a.int8 else "bf16",
+                          "tokens": n_img + dims["text_len"],
                           "ms_per_step": dt * 1e3, "step_tflop": fl / 1e12, "tflops_per_s": fl / dt / 1e12, "tflops_per_s_per_gpu": fl / dt / 1e12 / world,
                           "frac_of_bf16_peak": fl / dt / 1e12 / world / 2500.0, "frames_per_s_50_steps": wl["frames"] / (50 * dt),
                           "hbm_gb": torch.cuda.max_memory_allocated() / 1e9, "comm": comm}))

@@ -2,7 +2,7 @@
 // milliseconds on a fresh box).  Test infrastructure — not part of the product path.
 //
 //   x2v_check probe            hardware-semantics probes (MFMA layouts, ds_read_b64_tr_b16, LDS-DMA)
-//   x2v_check norm|gemm|attn|fp8|conv|misc     numerics vs straightforward CPU references
+//   x2v_check norm|gemm|attn|fp8|int8|conv|misc     numerics vs straightforward CPU references
 //   x2v_check bench            GEMM / attention / norm throughput at the BASELINE shapes
 //
 // CPU references here are plain fp32/fp64 loops over the same bf16 inputs (the torch oracle lives in
@@ -809,6 +809,66 @@ static void run_fp8() {
   }
 }
 
+// ---------------------------------------------------------------- int8
+static void run_int8() {
+  Rng rng(19);
+  const int64_t M = 200;
+  const int K = 512, N = 264;
+  auto x = rand_bf((size_t)M * K, rng, 1.5f);
+  for (int k = 0; k < K; ++k) x[3 * K + k] = 0;  // an all-zero token: codes 0, scale 0
+  DevBuf<uint16_t> dx(x);
+  DevBuf<uint8_t> dq((size_t)M * K);
+  DevBuf<float> ds(M);
+  X2V_OKAY(x2v_quant_int8_rowwise(dx.p, K, dq.p, K, ds.p, M, K, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  auto hq = dq.host();
+  auto hs = ds.host();
+  // the quantiser's contract (x2v.h), every step one fp32 operation: equality
+  std::vector<float> qgot((size_t)M * K), qref((size_t)M * K), sref(M);
+  for (int64_t m = 0; m < M; ++m) {
+    float amax = 0;
+    for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(bf2f(x[m * K + k])));
+    sref[m] = amax / 127.0f;
+    const float inv = amax > 0 ? 127.0f / amax : 0.f;
+    for (int k = 0; k < K; ++k) {
+      qgot[m * K + k] = (float)(int8_t)hq[m * K + k];
+      qref[m * K + k] = std::min(std::max(nearbyintf(bf2f(x[m * K + k]) * inv), -128.f), 127.f);
+    }
+  }
+  report("quant_int8 per-token scale == amax / 127", compare(hs, sref, 0, 0));
+  report("quant_int8 codes == clamp(rint(x * (127 / amax)))", compare(qgot, qref, 0, 0));
+  // int8 gemm: exact integer sum, one rounding to fp32, then the fp32 epilogue
+  std::vector<uint8_t> wq((size_t)N * K);
+  std::vector<float> sw(N);
+  for (int n = 0; n < N; ++n) {
+    sw[n] = 0.001f + 0.002f * rng.uni();
+    for (int k = 0; k < K; ++k) wq[(size_t)n * K + k] = (uint8_t)(rng.next() & 0xff);  // full range, -128 included
+  }
+  auto bias = rand_bf(N, rng, 0.2f);
+  DevBuf<uint8_t> dwq(wq);
+  DevBuf<float> dsw(sw);
+  DevBuf<uint16_t> db(bias), dy((size_t)M * N);
+  std::vector<float> yref((size_t)M * N);
+  for (int64_t m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n) {
+      int64_t acc = 0;
+      for (int k = 0; k < K; ++k) acc += (int64_t)(int8_t)hq[m * K + k] * (int8_t)wq[(size_t)n * K + k];
+      yref[m * N + n] = rbf((float)acc * hs[m] * sw[n] + bf2f(bias[n]));
+    }
+  X2V_OKAY(x2v_gemm_int8_variant(dq.p, K, ds.p, dwq.p, K, dsw.p, db.p, dy.p, N, M, N, K, X2V_EPI_NONE, nullptr, 0, nullptr, 1, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  report("gemm_int8 v1 (v_mfma_i32_32x32x32_i8) vs exact integer sum", compare(to_f(dy.host()), yref, 2e-3, 0.0079), 0.002);
+  // the continuous 256x256 kernel (variant 5) on the first 256 channels: 4 K tiles, one output tile with an M tail
+  const int N5 = 256;
+  DevBuf<uint16_t> dy5((size_t)M * N5);
+  std::vector<float> yref5((size_t)M * N5);
+  for (int64_t m = 0; m < M; ++m)
+    for (int n = 0; n < N5; ++n) yref5[m * N5 + n] = yref[m * N + n];
+  X2V_OKAY(x2v_gemm_int8_variant(dq.p, K, ds.p, dwq.p, K, dsw.p, db.p, dy5.p, N5, M, N5, K, X2V_EPI_NONE, nullptr, 0, nullptr, 5, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  report("gemm_int8 v5 (continuous 256x256) vs exact integer sum", compare(to_f(dy5.host()), yref5, 2e-3, 0.0079), 0.002);
+}
+
 // ---------------------------------------------------------------- conv
 static void run_conv() {
   Rng rng(17);
@@ -1223,6 +1283,7 @@ int main(int argc, char** argv) {
   if (mode == "attn" || mode == "all") run_attn();
   if (mode == "dattn") run_dattn();
   if (mode == "fp8" || mode == "all") run_fp8();
+  if (mode == "int8" || mode == "all") run_int8();
   if (mode == "conv" || mode == "all") run_conv();
   if (mode == "hbm") run_hbm();
   if (mode == "bench") run_bench(false);
