@@ -91,6 +91,7 @@ def test_rope_golden(lib, golden_ops):
 
 
 def test_attention_golden(lib, golden_ops):
+    """The golden fixture at the oracle's tolerance; the tight criterion for these kernels is tests/test_gpu_attn_fp64.py (float64, every dispatch edge)."""
     g = golden_ops
     for variant in (0, 4, 5, 6):  # default and the three lazy-rescale thresholds (x2v.h)
         o = lib.attention(dev(g["attn_q"]), dev(g["attn_k"]), dev(g["attn_v"]), 2, variant=variant)
@@ -101,7 +102,8 @@ def test_attention_golden(lib, golden_ops):
 
 def test_attention_fast_variants(lib, golden_ops):
     """The ping-pong kernel folds scale*log2(e) into q (one more bf16 rounding of q, relative 2^-9) — compared with the golden
-    outputs at twice the default tolerance; it runs on the pre-transposed V (transposition checked exactly).  Both kernel bodies."""
+    outputs at twice the default tolerance; it runs on the pre-transposed V (transposition checked exactly).  Both kernel bodies.
+    The tight criterion for these kernels is tests/test_gpu_attn_fp64.py (float64, every dispatch edge)."""
     from oracle import wan_oracle as O
 
     g = golden_ops
