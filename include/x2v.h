@@ -312,7 +312,7 @@ int x2v_gemm_int8(const void* xq, int64_t ldx, const float* sx, const void* wq, 
                   int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
 
 /* Same, selecting the kernel.  variant & 0xff: 0 = by shape, 1 = the 128x128 kernel (gemm.hip's structure on v_mfma_i32_32x32x32_i8; every legal
- * shape), 5 = the continuous 256x256 kernel (gemm256ci8.hip: gemm256c8's pipeline and shape conditions — K a multiple of 256 and >= 512, N a multiple
+ * shape), 5 = the continuous 256x256 kernel (gemm256c8.hip's int8 form: the fp8 kernel's pipeline and shape conditions — K a multiple of 256 and >= 512, N a multiple
  * of 256, y blocks that are multiples of 128 columns, resid with y's row stride, a residual row period that is a multiple of 8 and >= 256 — else
  * X2V_E_SHAPE; bit-equal with variant 1).  Variant 0 takes it where x2v_gemm_fp8's rule takes a 256x256 kernel and these conditions hold.  There is
  * no int8 ping-pong kernel: 2, 3 and 4 return X2V_E_ARG.  Bits 8..15 = m-tiles per scheduling group of the 256x256 kernel (0 = default). */

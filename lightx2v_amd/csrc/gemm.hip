@@ -401,7 +401,7 @@ static int dispatch_epi(int epilogue, const void* x, int64_t ldxb, const void* w
   });
 }
 
-// The argument checks of the four public bf16 / fp8 entries.  `row`: elements of an x row that are contiguous (K, or x's K block); `N`: columns of y
+// The argument checks of the public bf16 and w8a8 (fp8 = true: e4m3 or int8 codes) entries.  `row`: elements of an x row that are contiguous (K, or x's K block); `N`: columns of y
 // that are (N, or y's N block); `blocked`: the wording of the _blocked entries.
 static int check_operands(const char* who, bool fp8, bool blocked, const void* x, int64_t ldx, int row, const float* sx, const void* w, int64_t ldw, const float* sw,
                           const void* y, int64_t ldy, int64_t M, int N, int K, const void* bias, int epilogue, const void* resid, int64_t ldr, const void* gate) {
@@ -460,19 +460,6 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16_blocked(cons
   return dispatch_epi<false>(epilogue, x, ldx * 2, w, ldw * 2, bias, y, ldy, M, N, K / GB_K, resid, ldr, gate, nullptr, nullptr, 0, (hipStream_t)stream, gb);
 }
 
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq,
-                                                                           int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock,
-                                                                           int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr,
-                                                                           const void* gate, void* stream) {
-  int rc = check_operands("gemm_fp8_blocked", true, true, xq, ldx, (x_kblock > 0 ? x_kblock : K), sx, wq, ldw, sw, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
-  if (rc != X2V_OK) return rc;
-  GemmBlocking gb;
-  rc = check_blocking("gemm_fp8_blocked", K, x_kblock, x_kblock_stride, N, y_nblock, y_nblock_stride, epilogue, &gb);
-  if (rc != X2V_OK) return rc;
-  if (M == 0) return X2V_OK;
-  return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
-}
-
 // The residual row period of the _resid_period entries: resid holds `period` rows, output row r combines with row r mod period.  y is written while
 // other workgroups still read resid, so the two may not overlap (the plain epilogue's y == resid is row r onto row r; here it is not).
 static int check_resid_period(const char* who, const void* y, int64_t ldy, int64_t M, int N, const void* resid, int64_t ldr, int64_t period, GemmBlocking* gb) {
@@ -496,38 +483,13 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16_resid_period
   return dispatch_epi<false>(X2V_EPI_RESIDUAL, x, ldx * 2, w, ldw * 2, bias, y, ldy, M, N, K / GB_K, resid, ldr, gate, nullptr, nullptr, variant, (hipStream_t)stream, gb);
 }
 
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias,
-                                                                                void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period,
-                                                                                const void* gate, int variant, void* stream) {
-  int rc = check_operands("gemm_fp8_resid_period", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
-  if (rc != X2V_OK) return rc;
-  GemmBlocking gb;
-  rc = check_resid_period("gemm_fp8_resid_period", y, ldy, M, N, resid, ldr, resid_period, &gb);
-  if (rc != X2V_OK) return rc;
-  if (M == 0) return X2V_OK;
-  return dispatch_epi<true>(X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
-}
-
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K,
                              int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
   return x2v_gemm_bf16_variant(x, ldx, w, ldw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
-                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
-  int rc = check_operands("gemm_fp8", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
-  if (rc != X2V_OK) return rc;
-  if (M == 0) return X2V_OK;
-  return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
-}
-
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
-                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
-  return x2v_gemm_fp8_variant(xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
-}
-
 // ---- w8a8 int8 (the reference's W-int8-channel-sym-A-int8-channel-sym-dynamic presets): the fp8 entries' signatures and argument checks, int8 codes,
-//      an exact int32 accumulator.  Two kernels: the 128x128 one (variant 1, every legal shape) and the continuous 256x256 one (gemm256ci8.hip, variant 5,
+//      an exact int32 accumulator.  Two kernels: the 128x128 one (variant 1, every legal shape) and the continuous 256x256 one (gemm256c8.hip's I8 form, variant 5,
 //      gemm256c8's shapes); variant 0 chooses with choose_kernel's rule; there is no int8 ping-pong kernel (2, 3, 4: X2V_E_ARG).  K <= 65536 keeps
 //      |acc| <= K * 2^14 below 2^31.  The rule is set from profiles/int8_gemm_bench.json: at the six shapes of the w8a8 step (M = 75 600; K, N in
 //      {5120, 13824}; plain, GELU, gated residual) the continuous kernel takes 0.68-0.73 of the 128x128 kernel's time (1.08-1.11x gemm256c8's), so it
@@ -552,46 +514,86 @@ static int dispatch_int8(const char* who, int epilogue, const void* x, int64_t l
   });
 }
 
-extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
-                                                                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant,
-                                                                            void* stream) {
-  int rc = check_operands("gemm_int8", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
-  if (rc == X2V_OK) rc = check_int8_k("gemm_int8", K);
+// ---- the public w8a8 entries: fp8 and int8 of each form (variant, resid_period, blocked) go through one helper.  The bf16 entries' checks in their
+//      fp8 mode, int8's K limit behind them, then each format's own dispatcher (the kernel sets differ: fp8 has a ping-pong kernel and an
+//      environment switch, int8 has neither).
+static int gemm_w8a8_variant(bool i8, const char* who, const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                             int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
+  int rc = check_operands(who, true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, epilogue, resid, ldr, gate);
+  if (rc == X2V_OK && i8) rc = check_int8_k(who, K);
   if (rc != X2V_OK) return rc;
   if (M == 0) return X2V_OK;
-  return dispatch_int8("gemm_int8", epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
+  if (i8) return dispatch_int8(who, epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
+  return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream);
+}
+
+static int gemm_w8a8_resid_period(bool i8, const char* who, const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                                  int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant, void* stream) {
+  int rc = check_operands(who, true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
+  if (rc == X2V_OK && i8) rc = check_int8_k(who, K);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_resid_period(who, y, ldy, M, N, resid, ldr, resid_period, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  if (i8) return dispatch_int8(who, X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
+  return dispatch_epi<true>(X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
+}
+
+static int gemm_w8a8_blocked(bool i8, const char* who, const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq, int64_t ldw,
+                             const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue,
+                             const void* resid, int64_t ldr, const void* gate, void* stream) {
+  int rc = check_operands(who, true, true, xq, ldx, (x_kblock > 0 ? x_kblock : K), sx, wq, ldw, sw, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
+  if (rc == X2V_OK && i8) rc = check_int8_k(who, K);
+  if (rc != X2V_OK) return rc;
+  GemmBlocking gb;
+  rc = check_blocking(who, K, x_kblock, x_kblock_stride, N, y_nblock, y_nblock_stride, epilogue, &gb);
+  if (rc != X2V_OK) return rc;
+  if (M == 0) return X2V_OK;
+  if (i8) return dispatch_int8(who, epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
+  return dispatch_epi<true>(epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
+  return gemm_w8a8_variant(false, "gemm_fp8", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, variant, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return gemm_w8a8_variant(false, "gemm_fp8", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias,
+                            void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant, void* stream) {
+  return gemm_w8a8_resid_period(false, "gemm_fp8_resid_period", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, resid, ldr, resid_period, gate, variant, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_fp8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq,
+                            int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue,
+                            const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return gemm_w8a8_blocked(false, "gemm_fp8_blocked", xq, ldx, x_kblock, x_kblock_stride, sx, wq, ldw, sw, bias, y, ldy, y_nblock, y_nblock_stride, M, N, K, epilogue, resid, ldr, gate, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_variant(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
+                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, int variant, void* stream) {
+  return gemm_w8a8_variant(true, "gemm_int8", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, variant, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias, void* y,
-                                                                    int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
-  return x2v_gemm_int8_variant(xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
+                            int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return gemm_w8a8_variant(true, "gemm_int8", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, epilogue, resid, ldr, gate, 0, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_resid_period(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, const void* bias,
-                                                                                 void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period,
-                                                                                 const void* gate, int variant, void* stream) {
-  int rc = check_operands("gemm_int8_resid_period", true, false, xq, ldx, K, sx, wq, ldw, sw, y, ldy, M, N, K, bias, X2V_EPI_RESIDUAL, resid, ldr, gate);
-  if (rc == X2V_OK) rc = check_int8_k("gemm_int8_resid_period", K);
-  if (rc != X2V_OK) return rc;
-  GemmBlocking gb;
-  rc = check_resid_period("gemm_int8_resid_period", y, ldy, M, N, resid, ldr, resid_period, &gb);
-  if (rc != X2V_OK) return rc;
-  if (M == 0) return X2V_OK;
-  return dispatch_int8("gemm_int8_resid_period", X2V_EPI_RESIDUAL, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, variant, (hipStream_t)stream, gb);
+                            void* y, int64_t ldy, int64_t M, int N, int K, const void* resid, int64_t ldr, int64_t resid_period, const void* gate, int variant, void* stream) {
+  return gemm_w8a8_resid_period(true, "gemm_int8_resid_period", xq, ldx, sx, wq, ldw, sw, bias, y, ldy, M, N, K, resid, ldr, resid_period, gate, variant, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_int8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kblock_stride, const float* sx, const void* wq,
-                                                                            int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock,
-                                                                            int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr,
-                                                                            const void* gate, void* stream) {
-  int rc = check_operands("gemm_int8_blocked", true, true, xq, ldx, (x_kblock > 0 ? x_kblock : K), sx, wq, ldw, sw, y, ldy, M, (y_nblock > 0 ? y_nblock : N), K, bias, epilogue, resid, ldr, gate);
-  if (rc == X2V_OK) rc = check_int8_k("gemm_int8_blocked", K);
-  if (rc != X2V_OK) return rc;
-  GemmBlocking gb;
-  rc = check_blocking("gemm_int8_blocked", K, x_kblock, x_kblock_stride, N, y_nblock, y_nblock_stride, epilogue, &gb);
-  if (rc != X2V_OK) return rc;
-  if (M == 0) return X2V_OK;
-  return dispatch_int8("gemm_int8_blocked", epilogue, xq, ldx, wq, ldw, bias, y, ldy, M, N, K / 128, resid, ldr, gate, sx, sw, 0, (hipStream_t)stream, gb);
+                            int64_t ldw, const float* sw, const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue,
+                            const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return gemm_w8a8_blocked(true, "gemm_int8_blocked", xq, ldx, x_kblock, x_kblock_stride, sx, wq, ldw, sw, bias, y, ldy, y_nblock, y_nblock_stride, M, N, K, epilogue, resid, ldr, gate, stream);
 }
 
 // the int8 twin of x2v_gemm_kernel_choice: low byte = tile family (1: the 128x128 kernel, 2: the 256x256 one), bit 8 = its continuous form — the only

@@ -1,5 +1,5 @@
 // What the GEMM sources share: host side the dispatch entries, the epilogue switch and the persistent grid rule (gemm.hip, gemm256.hip and the
-// three files below); device side the single-stream pipeline of gemm256s.hip (one output tile per workgroup), gemm256c.hip (continuous, bf16) and gemm256c8.hip (continuous, e4m3):
+// three files below); device side the single-stream pipeline of gemm256s.hip (one output tile per workgroup), gemm256c.hip (continuous, bf16) and gemm256c8.hip (continuous, e4m3 and int8):
 // accumulator-register access, the slot plan of a K tile, the LDS images, the tile schedule, the LDS-DMA pieces, the bf16 fragments, and the K-tile
 // slot stream + output-tile loop of the two continuous kernels.  A change to the plan is made HERE, once; the kernels keep what really differs
 // (matrix instruction, fragments, epilogue).
@@ -26,8 +26,7 @@ int gemm256c_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, 
 // gemm256c8.hip: the same continuous pipeline for the w8a8 operator (e4m3 operands, per-token / per-channel scales)
 int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
-
-// gemm256ci8.hip: the same continuous pipeline for the w8a8 int8 operator (v_mfma_i32_32x32x32_i8, int32 accumulators)
+// gemm256c8.hip, I8 form: the same kernel for the w8a8 int8 operator (v_mfma_i32_32x32x32_i8, int32 accumulators)
 int gemm256ci8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                         const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
 
@@ -280,7 +279,7 @@ struct Cursor {
 //      cursors simply run on into the next output tile with that tile's descriptors, so after the first output tile there is no prologue — when an
 //      output tile's last K tile retires, K tile 0 of the next one has landed in LDS and K tile 1 is in flight.  Needs an even number of K tiles >= 4
 //      (every output tile then starts in LDS stage 0).  Parameterised by what differs between bf16 and e4m3:
-//        MFMA_(n, FIRST)        what slot n multiplies (bf16: an MFMA in every slot; e4m3: in every fourth); FIRST: C = 0
+//        MFMA_(n, FIRST)        what slot n multiplies (bf16: an MFMA in every slot; e4m3: in every fourth; int8: in every second); FIRST: C = 0
 //        READ_(R, STAGE, KS)    fragment read R in 0..15 of k-step KS
 //      and by the kernel's own NXLOAD, xload(integral_constant<j>) (epilogue-operand load j, riding in the LAST K tile's slots),
 //      epilogue_setup(tm, tn) (an output tile becomes current) and epilogue() (behind its last K tile).

@@ -1,5 +1,6 @@
-// y[M,N] = epi((xq[M,K] . Wq[N,K]^T) * sx[m] * sw[n] + bias), e4m3 operands with per-token / per-channel fp32 scales (w8a8) — gemm256c.hip's CONTINUOUS
-// single-stream pipeline for the fp8 operator.  Same contract, operand layouts, epilogues, rounding points, MFMA (v_mfma_scale_f32_32x32x64_f8f6f4 with
+// y[M,N] = epi((xq[M,K] . Wq[N,K]^T) * sx[m] * sw[n] + bias), e4m3 or int8 operands with per-token / per-channel fp32 scales (w8a8) — gemm256c.hip's
+// CONTINUOUS single-stream pipeline for the two w8a8 operators: ONE kernel, gemm256c8_kernel<EPI, I8> (the name follows gemm_kernel<FP8, EPI, I8>).
+// The text below describes the e4m3 form (I8 = false); "What int8 changes" lists the three places where I8 = true differs.  Same contract, operand layouts, epilogues, rounding points, MFMA (v_mfma_scale_f32_32x32x64_f8f6f4 with
 // unit block scales) and k order as the fp8 instantiation of gemm256.hip: bit-equal results (tools/gemm_fp8_continuous_check.py,
 // tests/test_gpu_bench_shapes.py::test_gemm_fp8_continuous_pipeline_equals_ping_pong).
 // Replaces the cutlass_scaled_mm / fp8_scaled_mm call of common/ops/mm/mm_weight.py:287-319 at the large shapes, behind x2v_gemm_fp8[_variant|_blocked].
@@ -25,8 +26,26 @@
 // stays on gemm256.hip.  First contact on MI355X (profiles/r04_call16_*): 84 / 84 equality cases bit-equal, +2..5 % plain, +1.5..2.5 % GELU, +4..10 %
 // residual at the w8a8 step's shapes (2.55-2.87 PFLOP/s).  The dispatcher's default for row-major operands; block-strided operands (Ulysses buffers) keep
 // the ping-pong kernel until that path has met a GPU (X2V_GEMM_FP8_CONTINUOUS=2; =0: never).  Variant 5 of x2v_gemm_fp8_variant forces this kernel.
+//
+// What int8 changes (I8 = true: the reference's W-int8-channel-sym-A-int8-channel-sym-dynamic-* classes, mm_weight.py:322-354).  An int8 K tile is the
+// same 128-byte line per operand row as an e4m3 one, so the fragment reads, the epilogue's addressing, operand loads, statements and walk, the constants
+// below and the launch are the e4m3 form's own text.  What differs:
+//   * the matrix instruction: v_mfma_i32_32x32x32_i8, 16 operand bytes per lane.  Each e4m3 MFMA (32 operand bytes per lane = the two ds_read_b128
+//     halves e = 0, 1 of a fragment) becomes TWO int8 MFMAs, one per half, in the slots 4 m and 4 m + 2 of the plan: 64 MFMAs per K tile, one in
+//     every even slot, 32 fragment reads as before.  Both operands take the same half, i.e. the same (lane half, byte) -> k map, which is all the
+//     instruction requires; the order in which the k values are summed is free because the int32 sum is exact (K <= 65536: |acc| < 2^31).
+//     Every fragment is consumed in the slot window in which the e4m3 form consumes it, so the plan's read-before-use and stage-free points hold as
+//     they are.  The two MFMAs of a pair accumulate into the same tile back to back: an accumulate chain (D taken whole as C) needs no wait states.
+//   * the epilogue reads the accumulators as int32 and converts (v_cvt_f32_i32, round to nearest even) in front of the dequantisation (acc_value).
+//     The wait behind the last MFMA: the instruction is TAKEN to be 8-pass (the cycles of the bf16 32x32x16 form, half the block-scaled e4m3 one's;
+//     not measured in isolation here), whose result needs 12 states before another reader.  The 24 that the 16-pass e4m3 instruction needs are
+//     kept, so the reads are safe under either pass count (once per 256 x 256 output tile).  The slot plan's arithmetic (64 MFMAs in a K tile's
+//     time) rests on the same assumption; measured, int8 takes 1.08-1.11x the e4m3 form's time at the w8a8 step's shapes.
+//   Bit-equal with the 128x128 int8 kernel (gemm.hip, I8): same exact sum, same conversion, same epilogue statements (tests/test_gpu_int8.py).
+//   Variant 5 of x2v_gemm_int8_variant forces this kernel; its shapes are the e4m3 form's (a residual row period: a multiple of 8 and >= 256).
 // AUDIT after every edit (the accumulator half is invisible to the compiler): `hipcc -S` must show .vgpr_spill_count 0,
-// .private_segment_fixed_size 0 and no v_accvgpr_* / a[..] operand outside ;;#ASMSTART / ;;#ASMEND.
+// .private_segment_fixed_size 0 and no v_accvgpr_* / a[..] operand outside ;;#ASMSTART / ;;#ASMEND (tools/isa_diff.py reports it).  Both formats'
+// instruction streams are those of the two per-format files this one replaced (profiles/w8a8_one_kernel_isa.txt).
 #include "gemm256_pipe.h"
 
 namespace x2v {
@@ -39,8 +58,6 @@ constexpr int C8_LDS_TOTAL = LDS_BYTES + 4 * C8_STRIP_BYTES;
 constexpr int C8_NX_PLAIN = 4 + 8 + 8, C8_NX_RES = C8_NX_PLAIN + 1 + 4;
 static_assert(xload_slots() >= C8_NX_RES, "the LAST K tile has a position for every epilogue-operand load");
 static_assert(NEWER + C8_NX_RES <= 63, "vmcnt immediate");
-
-typedef float c8_f32x4_t __attribute__((ext_vector_type(4)));
 
 // accumulator tile I (= x block * 4 + W block, 32 x 32) is a[16 I : 16 I + 15].  The UNSCALED encoding v_mfma_f32_32x32x64_f8f6f4 (8 bytes; both
 // operands e4m3 by its default cbsz / blgp): per-channel w8a8 has no block scales, and the scaled encoding with unit e8m0 scales (16 bytes + a
@@ -55,7 +72,28 @@ __device__ __forceinline__ void c8_mfma_first(const i32x8_t& wf, const i32x8_t& 
   asm volatile("v_mfma_f32_32x32x64_f8f6f4 a[%c2:%c3], %0, %1, 0" ::"v"(wf), "v"(xf), "i"(16 * I), "i"(16 * I + 15) : X2V_AGPRS);
 }
 
-template <int EPI>
+// int8: the same tile as 32 x 32 int32; one MFMA per fragment half
+template <int I>
+__device__ __forceinline__ void ci8_mfma(const i32x4_t& wf, const i32x4_t& xf) {
+  asm volatile("v_mfma_i32_32x32x32_i8 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(wf), "v"(xf), "i"(16 * I), "i"(16 * I + 15) : X2V_AGPRS);
+}
+template <int I>
+__device__ __forceinline__ void ci8_mfma_first(const i32x4_t& wf, const i32x4_t& xf) {  // first MFMA of an output tile into tile I: C = 0
+  asm volatile("v_mfma_i32_32x32x32_i8 a[%c2:%c3], %0, %1, 0" ::"v"(wf), "v"(xf), "i"(16 * I), "i"(16 * I + 15) : X2V_AGPRS);
+}
+// accumulator register R as the float the epilogue dequantises: the e4m3 sum itself, the int32 sum converted
+template <bool I8, int R>
+__device__ __forceinline__ float acc_value() {
+  if constexpr (I8) {
+    int x;
+    asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(R) : X2V_AGPRS);
+    return (float)x;
+  } else {
+    return acc_read<R>();
+  }
+}
+
+template <int EPI, bool I8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm256c8_kernel(
     const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes, const unsigned short* __restrict__ bias, unsigned short* Y,
     int64_t ldy, int64_t M, int N, int nk, const unsigned short* resid, int64_t ldr, const unsigned short* __restrict__ gate, const float* __restrict__ sx,
@@ -73,7 +111,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   X2V_PIPE_OPERANDS()
   X2V_PIPE_DMA_OFFSETS()
 
-  // ---- fragment addresses (32x32x64: row fl of a 32-row block; half e of k-step s = 16-byte chunk 4 s + 2 e + fh), block offsets travel as immediates
+  // ---- fragment addresses (32x32x64: row fl of a 32-row block; half e of k-step s = 16-byte chunk 4 s + 2 e + fh; int8: the 32 k values of its k-step
+  //      2 s + e, 16 of them in lane half fh), block offsets travel as immediates
   int rd_x[2][2], rd_w[2][2];
   {
     const int swz = (fl >> 1) & 7;
@@ -86,7 +125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         rd_w[s][e] = o + wc * 16384;
       }
   }
-  // fragment halves: fx[ks][xb][e], fw[ks][wb][e]; an MFMA operand is the 8-register pair (e = 0, 1)
+  // fragment halves: fx[ks][xb][e], fw[ks][wb][e]; an e4m3 MFMA operand is the 8-register pair (e = 0, 1), an int8 one a single half
   i32x4_t fx[2][4][2], fw[2][4][2];
   // read R_ in 0..15 of k-step KS_ of the tile in stage STAGE_: fragment R_ / 2 (order x0, W0..W3, x1..x3: the first MFMA of a k-step needs x0, W0), half R_ % 2
 #define C8_READ(R_, STAGE_, KS_)                                                                                                                \
@@ -96,14 +135,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     else if constexpr (f_ <= 4) fw[KS_][f_ - 1][e_] = *reinterpret_cast<const i32x4_t*>(smem + (STAGE_) * STAGE_BYTES + (f_ - 1) * 4096 + rd_w[KS_][e_]); \
     else fx[KS_][f_ - 4][e_] = *reinterpret_cast<const i32x4_t*>(smem + (STAGE_) * STAGE_BYTES + (f_ - 4) * 4096 + rd_x[KS_][e_]);              \
   }
-  // what position n of a K tile multiplies: MFMA n / 4 sits at n % 4 == 0 (one bf16 MFMA slot = a quarter of an fp8 one)
+  // what position n of a K tile multiplies: e4m3 MFMA m = n / 4 sits at n % 4 == 0 (one bf16 MFMA slot = a quarter of an fp8 one); int8 has an MFMA in
+  // every even slot: slots 4 m and 4 m + 2 hold the halves e = 0, 1 of MFMA m
 #define C8_MFMA(N_, FIRST_)                                                                                   \
-  if constexpr (((N_) & 3) == 0) {                                                                            \
-    constexpr int m = (N_) >> 2, ks = m >> 4, xb = (m >> 2) & 3, wb = m & 3;                                  \
-    const i32x8_t wf = __builtin_shufflevector(fw[ks][wb][0], fw[ks][wb][1], 0, 1, 2, 3, 4, 5, 6, 7);         \
-    const i32x8_t xf = __builtin_shufflevector(fx[ks][xb][0], fx[ks][xb][1], 0, 1, 2, 3, 4, 5, 6, 7);         \
-    if constexpr ((FIRST_) && ks == 0) c8_mfma_first<xb * 4 + wb>(wf, xf);                                    \
-    else c8_mfma<xb * 4 + wb>(wf, xf);                                                                        \
+  if constexpr (((N_) & (I8 ? 1 : 3)) == 0) {                                                                 \
+    constexpr int m = (N_) >> 2, e = ((N_) >> 1) & 1, ks = m >> 4, xb = (m >> 2) & 3, wb = m & 3;             \
+    if constexpr (I8) {                                                                                       \
+      if constexpr ((FIRST_) && ks == 0 && e == 0) ci8_mfma_first<xb * 4 + wb>(fw[ks][wb][e], fx[ks][xb][e]); \
+      else ci8_mfma<xb * 4 + wb>(fw[ks][wb][e], fx[ks][xb][e]);                                               \
+    } else {                                                                                                  \
+      const i32x8_t wf = __builtin_shufflevector(fw[ks][wb][0], fw[ks][wb][1], 0, 1, 2, 3, 4, 5, 6, 7);       \
+      const i32x8_t xf = __builtin_shufflevector(fx[ks][xb][0], fx[ks][xb][1], 0, 1, 2, 3, 4, 5, 6, 7);       \
+      if constexpr ((FIRST_) && ks == 0) c8_mfma_first<xb * 4 + wb>(wf, xf);                                  \
+      else c8_mfma<xb * 4 + wb>(wf, xf);                                                                      \
+    }                                                                                                         \
   }
 
   // ---- epilogue of the CURRENT output tile (see the header).  Half-block (ch, xb) = rows [32 xb, 32 xb + 32) x columns [64 ch, 64 ch + 64) of the
@@ -116,7 +161,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   //      overwrite the strip right behind phase B's reads.
   //      Addressing as gemm256c.hip: vector offset = lane part or the "row does not exist" mark 0x80000000, scalar offset = column base + rows.
   u32x2_t e_bias[2][8];  // [column half][j]
-  c8_f32x4_t e_sw[2][8];
+  f32x4_t e_sw[2][8];
   float e_sx[4];
   u32x4_t e_gate4[2], e_res[2][4];
   __amdgpu_buffer_rsrc_t r_y, r_res, r_bias, r_gate, r_sw, r_sx;
@@ -174,7 +219,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // per-column operands of column half ch: scales and bias in phase-A layout (tile wb = 2 ch + (j >> 2), g = j & 3: columns 32 wb + 8 g + 4 fh ..+3)
   auto sw_load = [&](auto chc, auto jc) {
     constexpr int ch = decltype(chc)::value, j = decltype(jc)::value;
-    e_sw[ch][j] = __builtin_bit_cast(c8_f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_sw, (unsigned)(16 * fh), 2u * s_bias + (unsigned)((ch * 64 + j * 8) * 4), 0));
+    e_sw[ch][j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r_sw, (unsigned)(16 * fh), 2u * s_bias + (unsigned)((ch * 64 + j * 8) * 4), 0));
   };
   auto bias_load = [&](auto chc, auto jc) {
     constexpr int ch = decltype(chc)::value, j = decltype(jc)::value;
@@ -205,7 +250,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int I = decltype(ic)::value, xb = I >> 2, wb = I & 3, ch = wb >> 1;
     static_for<0, 4>([&](auto gc) {
       constexpr int g = decltype(gc)::value, j = (wb & 1) * 4 + g;
-      float vv[4] = {acc_read<16 * I + 4 * g + 0>(), acc_read<16 * I + 4 * g + 1>(), acc_read<16 * I + 4 * g + 2>(), acc_read<16 * I + 4 * g + 3>()};
+      float vv[4] = {acc_value<I8, 16 * I + 4 * g + 0>(), acc_value<I8, 16 * I + 4 * g + 1>(), acc_value<I8, 16 * I + 4 * g + 2>(), acc_value<I8, 16 * I + 4 * g + 3>()};
       // gemm256.hip's statements, in its order
       vv[0] = vv[0] * e_sx[xb] * e_sw[ch][j].x;
       vv[1] = vv[1] * e_sx[xb] * e_sw[ch][j].y;
@@ -291,26 +336,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #endif
 }
 
-template <int EPI>
+template <int EPI, bool I8>
 int launch_gemm256c8(const void* x, int64_t ldx_bytes, const void* w, int64_t ldw_bytes, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                      const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
   if (gm_tiles <= 0) gm_tiles = 4;
   const int ntm = (int)((M + TILE - 1) / TILE), ntn = (N + TILE - 1) / TILE;
-  int rc = ensure_dynamic_lds((const void*)gemm256c8_kernel<EPI>, C8_LDS_TOTAL, "gemm256c8 attr");
+  int rc = ensure_dynamic_lds((const void*)gemm256c8_kernel<EPI, I8>, C8_LDS_TOTAL, I8 ? "gemm256ci8 attr" : "gemm256c8 attr");
   if (rc != X2V_OK) return rc;
-  hipLaunchKernelGGL((gemm256c8_kernel<EPI>), dim3(persistent_grid((unsigned)ntm * (unsigned)ntn)), dim3(256), C8_LDS_TOTAL, st, (const char*)x, ldx_bytes, (const char*)w, ldw_bytes, (const unsigned short*)bias,
+  hipLaunchKernelGGL((gemm256c8_kernel<EPI, I8>), dim3(persistent_grid((unsigned)ntm * (unsigned)ntn)), dim3(256), C8_LDS_TOTAL, st, (const char*)x, ldx_bytes, (const char*)w, ldw_bytes, (const unsigned short*)bias,
                      (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)resid, ldr, (const unsigned short*)gate, sx, sw, ntm, ntn, gm_tiles, gb);
-  X2V_LAUNCH_CHECK("gemm256c8 launch");
+  X2V_LAUNCH_CHECK(I8 ? "gemm256ci8 launch" : "gemm256c8 launch");
   return X2V_OK;
 }
 
 }  // namespace
 
-// Called by gemm.hip's dispatcher, which also decides which shapes take this kernel (continuous_ok there).
+// Called by gemm.hip's dispatchers (dispatch_epi<true>, dispatch_int8), which also decide which shapes take this kernel (continuous_ok there).
 int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
   return with_epilogue("gemm_fp8", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
-    return launch_gemm256c8<decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, gb);
+    return launch_gemm256c8<decltype(epi)::value, false>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, gb);
+  });
+}
+int gemm256ci8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
+                        const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb) {
+  return with_epilogue("gemm_int8", epilogue, resid, ldr, gate, gb, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256c8<decltype(epi)::value, true>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, gb);
   });
 }
 

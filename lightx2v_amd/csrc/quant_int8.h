@@ -1,4 +1,4 @@
-// The per-token symmetric int8 quantiser's arithmetic, shared by quant_int8.hip and norm.hip's fused LayerNorm form so that the two give the same
+// The per-token symmetric int8 quantiser's arithmetic, shared by quant8.hip and norm.hip's fused LayerNorm form so that the two give the same
 // bits.  Restated from vLLM's dynamic `scaled_int8_quant(x, scale=None, azp=None, symmetric=True)` (reference call site mm_weight.py:247-249);
 // every operation is one correctly rounded fp32 operation:
 //   scale = amax / 127,  inv = 127 / amax,  q = clamp(rint(x * inv), -128, 127)  (round half to even)

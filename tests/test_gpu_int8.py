@@ -5,7 +5,7 @@ integer sum is exact, its conversion to fp32 one rounding, and with no bias and 
 rounding — nothing a compiler may contract.  With a bias or an activation an FMA contraction may move one rounding: those cases take the project's
 fp8 criterion (tests/test_gpu_ops.py::test_fp8_path_vs_oracle): assert_bf16_close(ulps=1, atol=4e-3, bad_frac=2e-3).
 
-Both kernels run every GEMM case: the 128x128 one (variant 1) and the continuous 256x256 one (variant 5, gemm256ci8.hip), each at its own shape."""
+Both kernels run every GEMM case: the 128x128 one (variant 1) and the continuous 256x256 one (variant 5, gemm256c8.hip's int8 form), each at its own shape."""
 import math
 import os
 

@@ -17,7 +17,7 @@ cat > $out/src/attn_shim.hip <<'EOS'
 extern "C" __attribute__((visibility("default"))) int x2v_attn_vt_launch_plan(int64_t, int64_t, int, int, int) { return X2V_E_ARG; }
 EOS
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -I include -I lightx2v_amd/csrc"
-for s in x2v_api norm gemm gemm256 gemm256s gemm256c quant_fp8 conv3d vae mx sched probe; do
+for s in x2v_api norm gemm gemm256 gemm256s gemm256c quant8 conv3d vae mx sched probe; do
   /opt/rocm/bin/hipcc $FLAGS -c lightx2v_amd/csrc/$s.hip -o $out/obj/$s.o &
 done
 /opt/rocm/bin/hipcc $FLAGS -c $out/src/attn.hip -o $out/obj/attn.o &
