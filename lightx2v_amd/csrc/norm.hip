@@ -5,36 +5,9 @@
 // achievable HBM.  Structure: a row lives entirely in registers between its single 16-byte-vector read
 // and its single write (two-pass statistics cost no extra HBM traffic); NW waves cooperate on one row
 // (NW=4 for the model dim, NW=1 for short rows so a 256-thread block carries 4 rows).
-#include <algorithm>
-#include <type_traits>
-
-#include "quant_int8.h"
-#include "x2v_common.h"
+#include "rowwise.h"
 
 namespace x2v {
-
-// ------------------------------------------------------------------------------------------------
-// Row holder: CH 16-byte chunks per lane, lanes of the row's NW waves interleaved chunk-wise so every
-// wave-instruction reads NW... 64 consecutive chunks (1 KiB) — fully coalesced.
-template <int CH, int NW>
-struct RowRegs {
-  float v[CH][8];
-  bool ok[CH];
-  __device__ __forceinline__ void load(const unsigned short* row, int D, int t) {
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const int e = (c * NW * 64 + t) * 8;
-      ok[c] = e < D;
-      if (ok[c]) {
-        uint4 u = *reinterpret_cast<const uint4*>(row + e);
-        unpack8(u, v[c]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
-      }
-    }
-  }
-};
 
 template <int CH, int NW, int ROUND>
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const unsigned short* __restrict__ x, int64_t ldx, const unsigned short* __restrict__ w,
@@ -47,25 +20,10 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const unsigned short* __re
   RowRegs<CH, NW> r;
   if (live) r.load(x + row * ldx, D, t);
   float ss = 0.f;
-  if (live) {
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float p = r.v[c][j] * r.v[c][j];
-        ss += (ROUND == X2V_ROUND_REF) ? rbf(p) : p;  // torch: x.pow(2) is a bf16 tensor
-      }
-  }
-  ss = (NW == 1) ? wave_sum(ss) : block_sum<4>(ss, red);
+  if (live) ss = rms_sumsq<ROUND>(r.v);
+  ss = row_sum<NW>(ss, red);
   if (!live) return;
-  float rs;
-  if (ROUND == X2V_ROUND_REF) {
-    float mean = rbf(ss / (float)D);  // .mean(-1): fp32 accumulate, bf16 result
-    float tt = rbf(mean + eps);       // + eps   → bf16
-    rs = rbf(1.0f / sqrtf(tt));       // rsqrt   → bf16
-  } else {
-    rs = 1.0f / sqrtf(ss / (float)D + eps);
-  }
+  const float rs = rms_rstd<ROUND>(ss, (float)D, eps);
   unsigned short* yr = y + row * ldy;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -73,15 +31,16 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const unsigned short* __re
     const int e = (c * NW * 64 + t) * 8;
     float wv[8], o[8];
     unpack8(*reinterpret_cast<const uint4*>(w + e), wv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (ROUND == X2V_ROUND_REF)
-        o[j] = rbf(r.v[c][j] * rs) * wv[j];  // (x * rstd) → bf16, then * weight → bf16 (pack8 rounds)
-      else
-        o[j] = r.v[c][j] * rs * wv[j];
-    }
+    rms_norm8<ROUND>(r.v[c], rs, wv, o);
     *reinterpret_cast<uint4*>(yr + e) = pack8(o);
   }
+}
+
+// ln_chunk of the per-row kernels: every operand is read from global memory where ln_chunk uses it.
+__device__ __forceinline__ void ln_chunk_at(const float* v, float mean, float rstd, const unsigned short* w, const unsigned short* b, const unsigned short* scale,
+                                            const unsigned short* shift, int e, float* o) {
+  auto at = [e](const unsigned short* p) { return [p, e] { return *reinterpret_cast<const uint4*>(p + e); }; };
+  ln_chunk(v, mean, rstd, w != nullptr, at(w), b != nullptr, at(b), scale != nullptr, at(scale), at(shift), o);
 }
 
 // LayerNorm (+ optional affine, + optional adaLN modulate), reference rounding chain.
@@ -97,67 +56,26 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const unsigned short* __
   const bool live = row < M;
   RowRegs<CH, NW> r;
   if (live) r.load(x + row * ldx, D, t);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += r.v[c][j];
-  s = (NW == 1) ? wave_sum(s) : block_sum<4>(s, red);
-  const float mean = s / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-    if (r.ok[c]) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float d = r.v[c][j] - mean;
-        q += d * d;
-      }
-    }
-  q = (NW == 1) ? wave_sum(q) : block_sum<4>(q, red);
+  const float mean = ln_mean<CH, NW>(r.v, D, red);
+  const float rstd = ln_rstd<CH, NW>(r.v, r.ok, mean, D, eps, red);
   if (!live) return;
-  const float rstd = 1.0f / sqrtf(q / (float)D + eps);
   unsigned short* yr = y + row * ldy;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     if (!r.ok[c]) continue;
     const int e = (c * NW * 64 + t) * 8;
     float o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (r.v[c][j] - mean) * rstd;
-    if (w != nullptr) {
-      float wv[8];
-      unpack8(*reinterpret_cast<const uint4*>(w + e), wv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] *= wv[j];
-    }
-    if (b != nullptr) {
-      float bv[8];
-      unpack8(*reinterpret_cast<const uint4*>(b + e), bv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += bv[j];
-    }
-    if (scale != nullptr) {  // norm_out.mul_(1 + scale).add_(shift): three bf16 roundings
-      float sc[8], sh[8];
-      unpack8(*reinterpret_cast<const uint4*>(scale + e), sc);
-      unpack8(*reinterpret_cast<const uint4*>(shift + e), sh);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float ln = rbf(o[j]);
-        float m = rbf(ln * rbf(1.0f + sc[j]));
-        o[j] = m + sh[j];
-      }
-    }
+    ln_chunk_at(r.v[c], mean, rstd, w, b, scale, shift, e, o);
     *reinterpret_cast<uint4*>(yr + e) = pack8(o);
   }
 }
 
 // LayerNorm (+affine, +adaLN modulate) fused with the per-token dynamic e4m3 quantisation of its output (w8a8 path): what the reference
 // runs as LNWeight.apply + mul_/add_ + scaled_fp8_quant in front of the q / k / v (or ffn_0) projections (mm_weight.py:236-245) — the
-// bf16 activation never goes to HBM, and the one quantised copy serves every projection that consumes it.  The normalised values are
-// rounded to bf16 exactly where layernorm_kernel rounds them (same expression order), so codes and scales are bit-identical to
-// x2v_layernorm_bf16 followed by x2v_quant_fp8_rowwise.  One block per row.
-// I8: the same in front of the per-token int8 quantiser (quant_int8.h; x2v_layernorm_quant_int8 == x2v_layernorm_bf16 + x2v_quant_int8_rowwise).
+// bf16 activation never goes to HBM, and the one quantised copy serves every projection that consumes it.  The normalised values come
+// from layernorm_kernel's own ln_mean / ln_rstd / ln_chunk and are rounded to bf16 where that kernel's pack8 rounds them, then quantised by
+// quant8.hip's own scale and pack (quant8.h): codes and scales are bit-identical to x2v_layernorm_bf16 followed by x2v_quant_fp8_rowwise.  One block per row.
+// I8: the same in front of the per-token int8 quantiser (x2v_layernorm_quant_int8 == x2v_layernorm_bf16 + x2v_quant_int8_rowwise).
 template <int CH, bool I8>
 __global__ __launch_bounds__(256) void layernorm_quant_kernel(const unsigned short* __restrict__ x, int64_t ldx, const unsigned short* __restrict__ w,
                                                             const unsigned short* __restrict__ b, const unsigned short* __restrict__ scale,
@@ -168,56 +86,15 @@ __global__ __launch_bounds__(256) void layernorm_quant_kernel(const unsigned sho
   const int64_t row = blockIdx.x;
   RowRegs<CH, 4> r;
   r.load(x + row * ldx, D, t);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += r.v[c][j];
-  s = block_sum<4>(s, red);
-  const float mean = s / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-    if (r.ok[c]) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float d = r.v[c][j] - mean;
-        q += d * d;
-      }
-    }
-  q = block_sum<4>(q, red);
-  const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+  const float mean = ln_mean<CH, 4>(r.v, D, red);
+  const float rstd = ln_rstd<CH, 4>(r.v, r.ok, mean, D, eps, red);
   float amax = 0.f;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     if (!r.ok[c]) continue;
     const int e = (c * 256 + t) * 8;
     float o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (r.v[c][j] - mean) * rstd;
-    if (w != nullptr) {
-      float wv[8];
-      unpack8(*reinterpret_cast<const uint4*>(w + e), wv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] *= wv[j];
-    }
-    if (b != nullptr) {
-      float bv[8];
-      unpack8(*reinterpret_cast<const uint4*>(b + e), bv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += bv[j];
-    }
-    if (scale != nullptr) {
-      float sc[8], sh[8];
-      unpack8(*reinterpret_cast<const uint4*>(scale + e), sc);
-      unpack8(*reinterpret_cast<const uint4*>(shift + e), sh);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float ln = rbf(o[j]);
-        float m = rbf(ln * rbf(1.0f + sc[j]));
-        o[j] = m + sh[j];
-      }
-    }
+    ln_chunk_at(r.v[c], mean, rstd, w, b, scale, shift, e, o);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       r.v[c][j] = rbf(o[j]);  // the bf16 tensor the reference quantises
@@ -235,21 +112,13 @@ __global__ __launch_bounds__(256) void layernorm_quant_kernel(const unsigned sho
       *reinterpret_cast<uint2*>(xq + row * ldq + e) = int8_codes8(r.v[c], inv);
     }
   } else {
-    const float qs = fmaxf(amax / 448.0f, 1.0f / (448.0f * 512.0f));  // quant_fp8_rowwise_kernel's scale rule
+    const float qs = e4m3_scale(amax);
     if (t == 0) sx[row] = qs;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       if (!r.ok[c]) continue;
       const int e = (c * 256 + t) * 8;
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = fminf(fmaxf(r.v[c][j] / qs, -448.f), 448.f);
-      unsigned lo = 0, hi = 0;
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-      *reinterpret_cast<uint2*>(xq + row * ldq + e) = make_uint2(lo, hi);
+      *reinterpret_cast<uint2*>(xq + row * ldq + e) = e4m3_codes8(r.v[c], qs);
     }
   }
 }
@@ -268,13 +137,6 @@ struct RopeOut {
   }
 };
 
-// One complex rotation (a + i b) * (co + i si), then the optional output scale — written with explicit fused multiply-adds so every
-// kernel that rotates (per-row and streaming forms) rounds identically whatever the optimiser would contract on its own.
-__device__ __forceinline__ void rope_pair(float a, float bb, float co, float si, float oscale, float& o0, float& o1) {
-  o0 = __builtin_fmaf(a, co, -(bb * si)) * oscale;
-  o1 = __builtin_fmaf(a, si, bb * co) * oscale;
-}
-
 // Fused q/k RMSNorm over the full model dim + 3-axis RoPE.  blockIdx.y selects q (0) or k (1).
 // One block per token row; D = H*128 so every 16-byte chunk holds 4 (re,im) pairs of one head.
 template <int CH, int ROUND>
@@ -291,59 +153,17 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(unsigned short* __res
   RowRegs<CH, 4> r;
   r.load(base, D, t);
   float rs = 1.f;
-  if (w != nullptr) {
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float p = r.v[c][j] * r.v[c][j];
-        ss += (ROUND == X2V_ROUND_REF) ? rbf(p) : p;
-      }
-    ss = block_sum<4>(ss, red);
-    if (ROUND == X2V_ROUND_REF) {
-      float mean = rbf(ss / (float)D);
-      rs = rbf(1.0f / sqrtf(rbf(mean + eps)));
-    } else {
-      rs = 1.0f / sqrtf(ss / (float)D + eps);
-    }
-  }
-  // grid position of this token (global index s0+row); beyond the grid → identity rotation
-  const int64_t g = s0 + row;
-  const bool rot = g < (int64_t)gf * gh * gw;
-  const int pw = (int)(g % gw), ph = (int)((g / gw) % gh), pf = (int)(g / ((int64_t)gw * gh));
+  if (w != nullptr) rs = rms_rstd<ROUND>(block_sum<4>(rms_sumsq<ROUND>(r.v), red), (float)D, eps);
+  bool rot;
+  int pf, ph, pw;
+  rope3d_pos(s0 + row, gf, gh, gw, rot, pf, ph, pw);  // s0 + row: this token's global index
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     if (!r.ok[c]) continue;
     const int e = (c * 256 + t) * 8;
-    float xn[8], o[8];
-    if (w != nullptr) {
-      float wv[8];
-      unpack8(*reinterpret_cast<const uint4*>(w + e), wv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (ROUND == X2V_ROUND_REF)
-          xn[j] = rbf(rbf(r.v[c][j] * rs) * wv[j]);
-        else
-          xn[j] = rbf(r.v[c][j] * rs * wv[j]);  // the norm's bf16 output feeds RoPE in the reference
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xn[j] = r.v[c][j];
-    }
-    const int pair0 = (e & 127) >> 1;  // complex index within the head: 0..63, 4 pairs per chunk
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int ci = pair0 + p;
-      float co = 1.f, si = 0.f;
-      if (rot) {
-        const int pos = ci < 22 ? pf : (ci < 43 ? ph : pw);
-        const float2 f = cs[pos * 64 + ci];
-        co = f.x;
-        si = f.y;
-      }
-      rope_pair(xn[2 * p], xn[2 * p + 1], co, si, oscale, o[2 * p], o[2 * p + 1]);
-    }
+    float o[8];
+    rms_rope_chunk<ROUND>(
+        r.v[c], w != nullptr, rs, [&] { return *reinterpret_cast<const uint4*>(w + e); }, [&](int p) { return rope3d_factor(cs, rot, pf, ph, pw, rope_pair0(e) + p); }, oscale, o);
     *reinterpret_cast<uint4*>(ro.dst(blockIdx.y, row, e, base)) = pack8(o);
   }
 }
@@ -356,17 +176,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(unsigned short* __res
 // chip at once), walks rows blockIdx.x, +gridDim.x, ..., issues the NEXT row's 16-byte loads before the current row's
 // reductions, and keeps the per-channel operands (affine / modulation rows with 1 + scale already rounded, norm weights) in
 // registers and the token's rotation factors in LDS, fetched once per block / per token instead of once per row.  (A deeper
-// prefetch — two rows ahead — measured slower: more registers, fewer resident blocks, and the hoisted operand math gone.)  The arithmetic (order of every sum and rounding) is exactly that of the kernels above: the two forms
-// give bit-identical outputs, which tools/x2v_check and tests/test_gpu_edge.py assert.
-template <int CH>
-__device__ __forceinline__ void load_row_raw(uint4 (&dst)[CH], const unsigned short* row, int D, int t) {
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int e = (c * 256 + t) * 8;
-    if (e < D) dst[c] = *reinterpret_cast<const uint4*>(row + e);
-    else dst[c] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
+// prefetch — two rows ahead — measured slower: more registers, fewer resident blocks, and the hoisted operand math gone.)  The arithmetic
+// is that of the kernels above, the same helpers of rowwise.h on the same values in the same order: the two forms give bit-identical
+// outputs, which tools/x2v_check and tests/test_gpu_edge.py assert.
 template <int CH, bool AFF, bool MOD>
 __global__ __launch_bounds__(256) void layernorm_stream_kernel(const unsigned short* __restrict__ x, int64_t ldx, const unsigned short* __restrict__ w,
                                                                const unsigned short* __restrict__ b, const unsigned short* __restrict__ scale,
@@ -401,57 +213,16 @@ __global__ __launch_bounds__(256) void layernorm_stream_kernel(const unsigned sh
     float v[CH][8];
 #pragma unroll
     for (int c = 0; c < CH; ++c) unpack8(cur[c], v[c]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[c][j];
-    s = block_sum<4>(s, red);
-    const float mean = s / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-      if (ok[c]) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float d = v[c][j] - mean;
-          q += d * d;
-        }
-      }
-    q = block_sum<4>(q, red);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+    const float mean = ln_mean<CH, 4>(v, D, red);
+    const float rstd = ln_rstd<CH, 4>(v, ok, mean, D, eps, red);
     unsigned short* yr = y + row * ldy;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       if (!ok[c]) continue;
       const int e = (c * 256 + t) * 8;
       float o[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (v[c][j] - mean) * rstd;
-      if constexpr (AFF) {
-        float wf[8], bf[8];
-        unpack8(wv[c], wf);
-        unpack8(bv[c], bf);
-        if (w != nullptr) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] *= wf[j];
-        }
-        if (b != nullptr) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] += bf[j];
-        }
-      }
-      if constexpr (MOD) {  // norm_out.mul_(1 + scale).add_(shift): three bf16 roundings
-        float sc[8], sh[8];
-        unpack8(scv[c], sc);
-        unpack8(shv[c], sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float ln = rbf(o[j]);
-          float m = rbf(ln * rbf(1.0f + sc[j]));
-          o[j] = m + sh[j];
-        }
-      }
+      ln_chunk(v[c], mean, rstd, AFF && w != nullptr, [&] { return wv[AFF ? c : 0]; }, AFF && b != nullptr, [&] { return bv[AFF ? c : 0]; }, MOD, [&] { return scv[MOD ? c : 0]; },
+               [&] { return shv[MOD ? c : 0]; }, o);
       *reinterpret_cast<uint4*>(yr + e) = pack8(o);
     }
 #pragma unroll
@@ -480,21 +251,16 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_stream_kernel(unsigned short
     wkv[c] = (ok[c] && has_w) ? *reinterpret_cast<const uint4*>(wk + e) : make_uint4(0u, 0u, 0u, 0u);
   }
   const int64_t stride = gridDim.x;
-  const int64_t ntok = (int64_t)gf * gh * gw;
   int64_t row = blockIdx.x;
   uint4 cur[CH], nxt[CH];
   if (row < S) load_row_raw<CH>(cur, q + row * ldq, D, t);
   int par = 0;
   for (; row < S; row += stride, par ^= 1) {
-    if (t < 64) {  // this token's rotation factors; beyond the grid -> identity rotation
-      const int64_t g = s0 + row;
-      float2 f = make_float2(1.f, 0.f);
-      if (g < ntok) {
-        const int pw = (int)(g % gw), ph = (int)((g / gw) % gh), pf = (int)(g / ((int64_t)gw * gh));
-        const int pos = t < 22 ? pf : (t < 43 ? ph : pw);
-        f = cs[pos * 64 + t];
-      }
-      tab[par][t] = f;
+    if (t < 64) {  // this token's rotation factors
+      bool rot;
+      int pf, ph, pw;
+      rope3d_pos(s0 + row, gf, gh, gw, rot, pf, ph, pw);
+      tab[par][t] = rope3d_factor(cs, rot, pf, ph, pw, t);
     }
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
@@ -507,50 +273,14 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_stream_kernel(unsigned short
 #pragma unroll
       for (int c = 0; c < CH; ++c) unpack8(cur[c], v[c]);
       float rs = 1.f;
-      if (has_w) {
-        float ss = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float p = v[c][j] * v[c][j];
-            ss += (ROUND == X2V_ROUND_REF) ? rbf(p) : p;
-          }
-        ss = block_sum<4>(ss, red);  // its barriers also publish tab[par]
-        if (ROUND == X2V_ROUND_REF) {
-          float mean = rbf(ss / (float)D);
-          rs = rbf(1.0f / sqrtf(rbf(mean + eps)));
-        } else {
-          rs = 1.0f / sqrtf(ss / (float)D + eps);
-        }
-      } else if (which == 0) {
-        __syncthreads();  // publish tab[par]
-      }
+      if (has_w) rs = rms_rstd<ROUND>(block_sum<4>(rms_sumsq<ROUND>(v), red), (float)D, eps);  // block_sum's barriers also publish tab[par]
+      else if (which == 0) __syncthreads();                                                     // publish tab[par]
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         if (!ok[c]) continue;
         const int e = (c * 256 + t) * 8;
-        float xn[8], o[8];
-        if (has_w) {
-          float wf[8];
-          unpack8(which == 0 ? wqv[c] : wkv[c], wf);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (ROUND == X2V_ROUND_REF)
-              xn[j] = rbf(rbf(v[c][j] * rs) * wf[j]);
-            else
-              xn[j] = rbf(v[c][j] * rs * wf[j]);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xn[j] = v[c][j];
-        }
-        const int pair0 = (e & 127) >> 1;
-        const float4 f01 = *reinterpret_cast<const float4*>(&tab[par][pair0]);
-        const float4 f23 = *reinterpret_cast<const float4*>(&tab[par][pair0 + 2]);
-        const float co[4] = {f01.x, f01.z, f23.x, f23.z}, si[4] = {f01.y, f01.w, f23.y, f23.w};
-#pragma unroll
-        for (int p = 0; p < 4; ++p) rope_pair(xn[2 * p], xn[2 * p + 1], co[p], si[p], oscale, o[2 * p], o[2 * p + 1]);
+        float o[8];
+        rms_rope_chunk<ROUND>(v[c], has_w, rs, [&] { return which == 0 ? wqv[c] : wkv[c]; }, [&](int p) { return tab[par][rope_pair0(e) + p]; }, oscale, o);
         *reinterpret_cast<uint4*>(ro.dst(which, row, e, base)) = pack8(o);
       }
 #pragma unroll
@@ -654,27 +384,16 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(unsigned short* __re
   unpack8(*reinterpret_cast<const uint4*>(p), v);
   if (w != nullptr) {
     unpack8(*reinterpret_cast<const uint4*>(w + sub * 8), wv);
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float pw = v[j] * v[j];
-      ss += (ROUND == X2V_ROUND_REF) ? rbf(pw) : pw;
-    }
+    float ss = rms_sumsq<ROUND>(v, 0.f);
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    float rs;
-    if (ROUND == X2V_ROUND_REF) {
-      const float mean = rbf(ss / 128.f);
-      rs = rbf(1.0f / sqrtf(rbf(mean + eps)));
-    } else {
-      rs = 1.0f / sqrtf(ss / 128.f + eps);
-    }
+    const float rs = rms_rstd<ROUND>(ss, 128.f, eps);
     // q_out_scale (attention prescale, FP32 mode only): folded into the value's last rounding — for un-rotated (text)
     // rows that is the norm's rounding, for rotated rows the rotary sum's
     const bool scale_here = ROUND != X2V_ROUND_REF && tok >= l_rope;
+    rms_norm8<ROUND>(v, rs, wv, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = (ROUND == X2V_ROUND_REF) ? rbf(rbf(v[j] * rs) * wv[j]) : (scale_here ? v[j] * rs * wv[j] * oscale : rbf(v[j] * rs * wv[j]));
+    for (int j = 0; j < 8; ++j) v[j] = scale_here ? v[j] * oscale : rbf(v[j]);
   } else if (ROUND != X2V_ROUND_REF && tok >= l_rope) {
     // no norm, no rotation: the store below is the row's one rounding, so the scale goes in front of it (oscale is 1 for k)
 #pragma unroll
@@ -698,39 +417,6 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(unsigned short* __re
 
 using namespace x2v;
 
-namespace {
-int chunks_for(int D, int nw) { return (D / 8 + nw * 64 - 1) / (nw * 64); }
-}  // namespace
-
-// Dispatch a runtime chunk count to a compile-time CH (generic lambda receives std::integral_constant).
-template <typename F>
-static int dispatch_ch(int ch, int D, F&& f) {
-  switch (ch) {
-    case 1: f(std::integral_constant<int, 1>{}); return X2V_OK;
-    case 2: f(std::integral_constant<int, 2>{}); return X2V_OK;
-    case 3: f(std::integral_constant<int, 3>{}); return X2V_OK;
-    case 4: f(std::integral_constant<int, 4>{}); return X2V_OK;
-    case 5: case 6: case 7: case 8: f(std::integral_constant<int, 8>{}); return X2V_OK;
-    default: ::x2v::set_error("row too long: D=%d (max 16384)", D); return X2V_E_SHAPE;
-  }
-}
-
-// Blocks of a 256-thread kernel that are resident on the whole chip at once (occupancy x CUs), queried once per kernel: the grid of
-// the persistent "stream" kernels.  0 = query failed (callers fall back to the one-block-per-row form).
-template <auto KERNEL>
-static int resident_blocks() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0, nb = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)KERNEL, 256, 0) != hipSuccess || nb <= 0)
-      return 0;
-    cached = nb * prop.multiProcessorCount;
-  }
-  return cached;
-}
-
 extern "C" __attribute__((visibility("default"))) int x2v_rmsnorm_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t M, int D, float eps, int round_mode,
                                 void* stream) {
   X2V_REQUIRE(x && w && y, X2V_E_ARG, "rmsnorm: null pointer");
@@ -741,24 +427,18 @@ extern "C" __attribute__((visibility("default"))) int x2v_rmsnorm_bf16(const voi
   auto xs = (const unsigned short*)x, ws = (const unsigned short*)w;
   auto ys = (unsigned short*)y;
   hipStream_t st = (hipStream_t)stream;
-  if (D <= 512) {  // one wave per row, 4 rows per block
-    const unsigned grid = (unsigned)((M + 3) / 4);
-    if (round_mode == X2V_ROUND_REF)
-      hipLaunchKernelGGL((rmsnorm_kernel<1, 1, X2V_ROUND_REF>), dim3(grid), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
-    else
-      hipLaunchKernelGGL((rmsnorm_kernel<1, 1, X2V_ROUND_FP32>), dim3(grid), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
-  } else {
-    const int ch = chunks_for(D, 4);
-    const unsigned grid = (unsigned)M;
-    int rc = dispatch_ch(ch, D, [&](auto chc) {
-      constexpr int CH = decltype(chc)::value;
-      if (round_mode == X2V_ROUND_REF)
-        hipLaunchKernelGGL((rmsnorm_kernel<CH, 4, X2V_ROUND_REF>), dim3(grid), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
-      else
-        hipLaunchKernelGGL((rmsnorm_kernel<CH, 4, X2V_ROUND_FP32>), dim3(grid), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
-    });
-    if (rc != X2V_OK) return rc;
-  }
+  int rc = X2V_OK;
+  dispatch_value<X2V_ROUND_REF, X2V_ROUND_FP32>(round_mode, [&](auto rm) {
+    constexpr int ROUND = decltype(rm)::value;
+    if (D <= 512) {  // one wave per row, 4 rows per block
+      hipLaunchKernelGGL((rmsnorm_kernel<1, 1, ROUND>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
+    } else {
+      rc = dispatch_ch(chunks_for(D, 4), D, [&](auto chc) {
+        hipLaunchKernelGGL((rmsnorm_kernel<decltype(chc)::value, 4, ROUND>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, ws, ys, ldy, M, D, eps);
+      });
+    }
+  });
+  if (rc != X2V_OK) return rc;
   X2V_LAUNCH_CHECK("rmsnorm launch");
   return X2V_OK;
 }
@@ -789,15 +469,13 @@ extern "C" __attribute__((visibility("default"))) int x2v_layernorm_bf16_variant
       constexpr int CH = decltype(chc)::value;
       if constexpr (CH <= 4) {
         // persistent form for long inputs (bit-identical results; see layernorm_stream_kernel)
-        auto go = [&](auto kern, int resident) {
-          if (variant == 1 || resident <= 0 || (variant == 0 && M < 2 * (int64_t)resident)) return;
-          hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(M, resident)), dim3(256), 0, st, xs, ldx, ws, bs, scs, shs, ys, ldy, M, D, eps);
-          streamed = true;
+        auto go = [&](auto affc, auto modc) {
+          streamed = launch_persistent<layernorm_stream_kernel<CH, decltype(affc)::value, decltype(modc)::value>>(variant, M, st, xs, ldx, ws, bs, scs, shs, ys, ldy, M, D, eps);
         };
-        if (aff && mod) go(layernorm_stream_kernel<CH, true, true>, resident_blocks<layernorm_stream_kernel<CH, true, true>>());
-        else if (aff) go(layernorm_stream_kernel<CH, true, false>, resident_blocks<layernorm_stream_kernel<CH, true, false>>());
-        else if (mod) go(layernorm_stream_kernel<CH, false, true>, resident_blocks<layernorm_stream_kernel<CH, false, true>>());
-        else go(layernorm_stream_kernel<CH, false, false>, resident_blocks<layernorm_stream_kernel<CH, false, false>>());
+        if (aff && mod) go(std::true_type{}, std::true_type{});
+        else if (aff) go(std::true_type{}, std::false_type{});
+        else if (mod) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
       }
       if (!streamed) hipLaunchKernelGGL((layernorm_kernel<CH, 4>), dim3(grid), dim3(256), 0, st, xs, ldx, ws, bs, scs, shs, ys, ldy, M, D, eps);
     });
@@ -870,21 +548,12 @@ static int rmsnorm_rope_impl(void* q, int64_t ldq, void* k, int64_t ldk, const v
   bool streamed = false;
   int rc = dispatch_ch(ch, D, [&](auto chc) {
     constexpr int CH = decltype(chc)::value;
-    if constexpr (CH <= 4) {
+    dispatch_value<X2V_ROUND_REF, X2V_ROUND_FP32>(round_mode, [&](auto rm) {
+      constexpr int ROUND = decltype(rm)::value;
       // persistent form for long inputs (bit-identical results; see rmsnorm_rope_stream_kernel)
-      auto go = [&](auto kern, int resident) {
-        if (variant == 1 || resident <= 0 || (variant == 0 && S < 2 * (int64_t)resident)) return;
-        hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(S, resident)), dim3(256), 0, st, qs, ldq, ks, ldk, wqs, wks, cs, S, D, s0, gf, gh, gw, eps, q_out_scale, ro);
-        streamed = true;
-      };
-      if (round_mode == X2V_ROUND_REF) go(rmsnorm_rope_stream_kernel<CH, X2V_ROUND_REF>, resident_blocks<rmsnorm_rope_stream_kernel<CH, X2V_ROUND_REF>>());
-      else go(rmsnorm_rope_stream_kernel<CH, X2V_ROUND_FP32>, resident_blocks<rmsnorm_rope_stream_kernel<CH, X2V_ROUND_FP32>>());
-    }
-    if (streamed) return;
-    if (round_mode == X2V_ROUND_REF)
-      hipLaunchKernelGGL((rmsnorm_rope_kernel<CH, X2V_ROUND_REF>), grid, dim3(256), 0, st, qs, ldq, ks, ldk, wqs, wks, cs, S, D, s0, gf, gh, gw, eps, q_out_scale, ro);
-    else
-      hipLaunchKernelGGL((rmsnorm_rope_kernel<CH, X2V_ROUND_FP32>), grid, dim3(256), 0, st, qs, ldq, ks, ldk, wqs, wks, cs, S, D, s0, gf, gh, gw, eps, q_out_scale, ro);
+      if constexpr (CH <= 4) streamed = launch_persistent<rmsnorm_rope_stream_kernel<CH, ROUND>>(variant, S, st, qs, ldq, ks, ldk, wqs, wks, cs, S, D, s0, gf, gh, gw, eps, q_out_scale, ro);
+      if (!streamed) hipLaunchKernelGGL((rmsnorm_rope_kernel<CH, ROUND>), grid, dim3(256), 0, st, qs, ldq, ks, ldk, wqs, wks, cs, S, D, s0, gf, gh, gw, eps, q_out_scale, ro);
+    });
   });
   if (rc != X2V_OK) return rc;
   X2V_REQUIRE(variant != 2 || streamed, X2V_E_SHAPE, "rmsnorm_rope: the streaming kernel covers D <= 8192 (D=%d)", D);
@@ -941,12 +610,9 @@ extern "C" __attribute__((visibility("default"))) int x2v_activation_bf16(const 
   if (n <= 0) return X2V_OK;
   const int64_t nv = n / 8;
   const unsigned grid = (unsigned)((nv + 255) / 256 < 8192 ? ((nv + 255) / 256 > 0 ? (nv + 255) / 256 : 1) : 8192);
-  if (act == X2V_EPI_GELU_TANH)
-    hipLaunchKernelGGL((activation_kernel<X2V_EPI_GELU_TANH>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, n);
-  else if (act == X2V_ACT_GELU_ERF)
-    hipLaunchKernelGGL((activation_kernel<X2V_ACT_GELU_ERF>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, n);
-  else
-    hipLaunchKernelGGL((activation_kernel<X2V_EPI_SILU>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, n);
+  dispatch_value<X2V_EPI_GELU_TANH, X2V_ACT_GELU_ERF, X2V_EPI_SILU>(act, [&](auto a) {
+    hipLaunchKernelGGL((activation_kernel<decltype(a)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned short*)y, n);
+  });
   X2V_LAUNCH_CHECK("activation launch");
   return X2V_OK;
 }
@@ -974,14 +640,11 @@ static int headnorm_rope_impl(void* q, int64_t ldq, void* k, int64_t ldk, const 
   const int64_t rows = L * H;
   X2V_REQUIRE((rows + 15) / 16 < (1ll << 31), X2V_E_SHAPE, "headnorm_rope: too many rows");
   dim3 grid((unsigned)((rows + 15) / 16), 2);
-  if (round_mode == X2V_ROUND_REF)
-    hipLaunchKernelGGL((headnorm_rope_kernel<X2V_ROUND_REF>), grid, dim3(256), 0, (hipStream_t)stream, (unsigned short*)q, ldq, (unsigned short*)k, ldk,
+  dispatch_value<X2V_ROUND_REF, X2V_ROUND_FP32>(round_mode, [&](auto rm) {
+    hipLaunchKernelGGL((headnorm_rope_kernel<decltype(rm)::value>), grid, dim3(256), 0, (hipStream_t)stream, (unsigned short*)q, ldq, (unsigned short*)k, ldk,
                        (const unsigned short*)wq, (const unsigned short*)wk, (const unsigned short*)cos_tab, (const unsigned short*)sin_tab, L, H, l_rope, eps, q_out_scale, hpb,
                        cbs);
-  else
-    hipLaunchKernelGGL((headnorm_rope_kernel<X2V_ROUND_FP32>), grid, dim3(256), 0, (hipStream_t)stream, (unsigned short*)q, ldq, (unsigned short*)k, ldk,
-                       (const unsigned short*)wq, (const unsigned short*)wk, (const unsigned short*)cos_tab, (const unsigned short*)sin_tab, L, H, l_rope, eps, q_out_scale, hpb,
-                       cbs);
+  });
   X2V_LAUNCH_CHECK("headnorm_rope launch");
   return X2V_OK;
 }

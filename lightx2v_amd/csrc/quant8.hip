@@ -1,8 +1,8 @@
 // Per-token dynamic quantisation of activations for the two w8a8 paths: e4m3fn (BASELINE config #4) and symmetric int8 (the reference's published
 // int8 presets).  One kernel, quant8_rowwise_kernel<CH, I8>: the loads, the amax reduction and the store are shared, the scale and the 8-value pack
-// are each format's own (int8's in quant_int8.h, which norm.hip's fused LayerNorm form shares).
+// are each format's own (quant8.h, which norm.hip's fused LayerNorm form shares).
 // HBM-bound: reads M*K bf16, writes M*K bytes + M floats.  One workgroup per row, row held in registers.
-#include "quant_int8.h"
+#include "rowwise.h"
 
 namespace x2v {
 
@@ -29,10 +29,9 @@ __global__ __launch_bounds__(256) void quant8_rowwise_kernel(const unsigned shor
     }
   }
   amax = block_max<4>(amax, red);
-  // e4m3: reference mm_weight.py:236-245 → vllm dynamic per-token quant: scale = max(amax / 448, 1 / (448 * 512)), a division per element.
-  // int8: scale = amax / 127, a multiplication by 127 / amax per element (quant_int8.h).  Each format uses its own of s and inv; inv behind the scale's
-  // store is the order the instruction scheduler was handed before the two kernels became one (profiles/w8a8_one_kernel_isa.txt)
-  const float s = I8 ? 0.f : fmaxf(amax / 448.0f, 1.0f / (448.0f * 512.0f));
+  // Each format uses its own of s and inv; inv behind the scale's store is the order the instruction scheduler was handed before the two
+  // kernels became one (profiles/w8a8_one_kernel_isa.txt)
+  const float s = I8 ? 0.f : e4m3_scale(amax);
   if (t == 0) scale[row] = I8 ? int8_scale(amax) : s;
   const float inv = I8 ? int8_inv_scale(amax) : 0.f;
 #pragma unroll
@@ -40,20 +39,8 @@ __global__ __launch_bounds__(256) void quant8_rowwise_kernel(const unsigned shor
     if (!ok[c]) continue;
     const int e = (c * 256 + t) * 8;
     uint2 o;
-    if constexpr (I8) {
-      o = int8_codes8(v[c], inv);
-    } else {
-      float q[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] = fminf(fmaxf(v[c][j] / s, -448.f), 448.f);
-      unsigned lo = 0, hi = 0;
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], lo, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], lo, true);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], hi, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], hi, true);
-      o.x = lo;
-      o.y = hi;
-    }
+    if constexpr (I8) o = int8_codes8(v[c], inv);
+    else o = e4m3_codes8(v[c], s);
     *reinterpret_cast<uint2*>(xq + row * ldq + e) = o;
   }
 }
@@ -71,17 +58,11 @@ static int quant8_rowwise(const char* who, const void* x, int64_t ldx, int kbloc
   X2V_REQUIRE(kblock == 0 || (kblock > 0 && kblock % 8 == 0 && K % kblock == 0 && kblock_stride % 8 == 0 && ldx >= kblock), X2V_E_SHAPE,
               "%s: x K-block of %d elements must be a multiple of 8 dividing K=%d, block stride a multiple of 8", who, kblock, K);
   if (M <= 0) return X2V_OK;
-  const int ch = (K / 8 + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
-  auto xs = (const unsigned short*)x;
-  auto qs = (unsigned char*)xq;
-  switch (ch) {
-    case 1: hipLaunchKernelGGL((quant8_rowwise_kernel<1, I8>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, qs, ldq, scale, K, kblock, kblock_stride); break;
-    case 2: hipLaunchKernelGGL((quant8_rowwise_kernel<2, I8>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, qs, ldq, scale, K, kblock, kblock_stride); break;
-    case 3: hipLaunchKernelGGL((quant8_rowwise_kernel<3, I8>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, qs, ldq, scale, K, kblock, kblock_stride); break;
-    case 4: hipLaunchKernelGGL((quant8_rowwise_kernel<4, I8>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, qs, ldq, scale, K, kblock, kblock_stride); break;
-    default: hipLaunchKernelGGL((quant8_rowwise_kernel<8, I8>), dim3((unsigned)M), dim3(256), 0, st, xs, ldx, qs, ldq, scale, K, kblock, kblock_stride); break;
-  }
+  int rc = dispatch_ch(chunks_for(K, 4), K, [&](auto chc) {
+    hipLaunchKernelGGL((quant8_rowwise_kernel<decltype(chc)::value, I8>), dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, (unsigned char*)xq, ldq,
+                       scale, K, kblock, kblock_stride);
+  });
+  if (rc != X2V_OK) return rc;
   X2V_LAUNCH_CHECK(I8 ? "quant_int8 launch" : "quant_fp8 launch");
   return X2V_OK;
 }

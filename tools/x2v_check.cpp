@@ -1142,6 +1142,32 @@ static void run_hbm() {
     printf("BENCH rmsnorm M=%lld D=%d            %9.3f ms  %8.1f GB/s (%.1f%%)\n", (long long)M, D, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 62.9);
     ms = time_ms(10, [&] { X2V_OKAY(x2v_gate_residual_bf16(y1.p, D, x.p, D, sc.p, M, D, nullptr)); });
     printf("BENCH gate_residual M=%lld D=%d       %9.3f ms  %8.1f GB/s (%.1f%%; 3 streams)\n", (long long)M, D, ms, 1.5 * bytes / ms / 1e6, 1.5 * bytes / ms / 1e6 / 62.9);
+    // the w8a8 quantisers: one bf16 read, one 8-bit write + a scale per row (codes into y2, M*D bytes of its 2*M*D)
+    DevBuf<float> sx((size_t)M);
+    const double qbytes = 3.0 * M * D + 4.0 * M;
+    ms = time_ms(10, [&] { X2V_OKAY(x2v_layernorm_quant_fp8(x.p, D, nullptr, nullptr, sc.p, shf.p, y2.p, D, sx.p, M, D, 1e-6f, nullptr)); });
+    printf("BENCH layernorm_quant_fp8 modulate M=%lld D=%d  %9.3f ms  %8.1f GB/s (%.1f%%)\n", (long long)M, D, ms, qbytes / ms / 1e6, qbytes / ms / 1e6 / 62.9);
+    ms = time_ms(10, [&] { X2V_OKAY(x2v_layernorm_quant_int8(x.p, D, nullptr, nullptr, sc.p, shf.p, y2.p, D, sx.p, M, D, 1e-6f, nullptr)); });
+    printf("BENCH layernorm_quant_int8 modulate M=%lld D=%d %9.3f ms  %8.1f GB/s (%.1f%%)\n", (long long)M, D, ms, qbytes / ms / 1e6, qbytes / ms / 1e6 / 62.9);
+    ms = time_ms(10, [&] { X2V_OKAY(x2v_quant_fp8_rowwise(x.p, D, y2.p, D, sx.p, M, D, nullptr)); });
+    printf("BENCH quant_fp8_rowwise M=%lld D=%d   %9.3f ms  %8.1f GB/s (%.1f%%)\n", (long long)M, D, ms, qbytes / ms / 1e6, qbytes / ms / 1e6 / 62.9);
+    ms = time_ms(10, [&] { X2V_OKAY(x2v_quant_int8_rowwise(x.p, D, y2.p, D, sx.p, M, D, nullptr)); });
+    printf("BENCH quant_int8_rowwise M=%lld D=%d  %9.3f ms  %8.1f GB/s (%.1f%%)\n", (long long)M, D, ms, qbytes / ms / 1e6, qbytes / ms / 1e6 / 62.9);
+  }
+  // per-head RMSNorm + RoPE at the HunyuanVideo-13B block shape of tools/hunyuan_bench.py (720p x 129 frames): 33 x 45 x 80 image + 256 text tokens, 24 heads, q and k the
+  // first two column blocks of the fused [L, 3 * 3072] qkv buffer, image tokens rotated; in place, so q and k are each read and written once
+  {
+    const int64_t L_img = 33 * 45 * 80, L = L_img + 256;
+    const int H = 24, D = H * 128;
+    DevBuf<uint16_t> qkv((size_t)L * 3 * D), wq(128), wk(128), ct((size_t)L_img * 128), st((size_t)L_img * 128);
+    fill_random(qkv, rng, 1.f);
+    fill_random(wq, rng, 1.f);
+    fill_random(wk, rng, 1.f);
+    fill_random(ct, rng, 1.f);
+    fill_random(st, rng, 1.f);
+    const double bytes = 2.0 * 2.0 * L * D * 2;
+    double ms = time_ms(10, [&] { X2V_OKAY(x2v_headnorm_rope_bf16(qkv.p, 3 * D, qkv.p + D, 3 * D, wq.p, wk.p, ct.p, st.p, L, H, L_img, 1e-6f, 0, 0.1275f, nullptr)); });
+    printf("BENCH headnorm+rope (q,k) L=%lld H=%d  %9.3f ms  %8.1f GB/s (%.1f%%; + the cos / sin tables)\n", (long long)L, H, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 62.9);
   }
 }
 
