@@ -16,6 +16,7 @@ Tolerances are those of test_gpu_ops.py / test_gpu_model.py (bf16: 1 ulp = 2^-7 
 GEMM <= 1 ulp + atol on all but <= 2e-3 of the elements; attention at >= 8192 keys: the reference's own acceptance
 allclose(rtol=1e-3, atol=1e-3) (attentions/distributed/ring/tests/test.py:97) for every kernel variant, plus the triangle bound against
 fp32 attention (our error <= 1.5x the reference CPU kernel's own); block outputs relative L2 <= 1e-2.
+The GEMM bodies at small edge shapes against float64 (bit for bit on integer inputs, a bound on every element otherwise): tests/test_gpu_gemm_fp64.py.
 """
 import math
 

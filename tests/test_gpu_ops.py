@@ -135,6 +135,8 @@ def test_attention_fast_variants(lib, golden_ops):
 # ---------------------------------------------------------------------------- oracle on seeded inputs
 @pytest.mark.parametrize("M,K,N", [(1280, 1536, 1536), (1280, 1536, 8960), (333, 8960, 1536), (1, 256, 1536), (512, 4096, 1536), (700, 1536, 64)])
 def test_gemm_vs_oracle(lib, M, K, N):
+    """Against the oracle's bf16 addmm, by the dispatcher's own choice (these shapes take the 128x128 kernel).  Every kernel body forced at its
+    edges against float64, with a bound on every element: tests/test_gpu_gemm_fp64.py."""
     from oracle import wan_oracle as O
 
     gen = torch.Generator().manual_seed(M + K + N)
