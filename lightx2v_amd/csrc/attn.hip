@@ -307,10 +307,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const unsigne
 //     (an LDS-DMA issue costs ~60 cycles between bare MFMAs, about half in VALU-only gaps);
 //   * scores leave the MFMA already relative to the running max (C = -m_run, known before QK^T(t) starts because softmax(t-1) is the same wave's
 //     previous half-step), q carries scale*log2(e) (PRESCALED: folded in by the producer), so P = exp2(S') with no per-score FMA; rescale stays
-//     lazy (cold branch, threshold RESCALE_THR in base-2 units); the first MFMA of every score chain is an asm statement with an early-clobber
-//     destination so that hipcc never computes into (and then restores) the -m tuple;
+//     lazy (cold branch, threshold RESCALE_THR in base-2 units), and the search for the tile's row maxima that decides it sits in that cold
+//     branch too, behind a guard on the lane's tile sums of P (A9_SOFTMAX: a sum of non-negative P reaches 2^THR whenever one of them does), so
+//     a softmax half-step is 32 exp2, 28 adds, 16 packs and a 4-instruction guard; the first MFMA of every score chain is an asm statement
+//     with an early-clobber destination so that hipcc never computes into (and then restores) the -m tuple;
 //   * a straight-line loop per role (early / late waves), unrolled x2 so both LDS buffer indices are compile-time and every fragment address is
-//     register + immediate; one score buffer: nothing spills at 2 waves per SIMD (224 VGPRs).
+//     register + immediate; one score buffer: nothing spills at 2 waves per SIMD (216 VGPRs).
 // Register geometry — v_mfma_f32_16x16x32_bf16.  At the board's power limit the 16x16x32 shape delivers more FLOP per joule than 32x32x16
 // (tools/probes/mfma_power_probe: 1582 vs 1529-1540 TFLOP/s with attention's fragment traffic at 32 rows per wave), the same effect that moved
 // the GEMMs (gemm256.hip): the round-2 kernel (same protocol on 32x32x16, 32 MFMAs per tile) ran 4.8 % slower on the same box
@@ -327,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const unsigne
 //     16-lane group reads are kappa(kt, 0..15), whose h values are exactly 0..15 (h(kappa(kt, c)) = c) — conflict-free; (key & 15), v8's
 //     hash, would collide two-fold.  The DMA pieces of a wave are chosen so that h is the same for all of them (one voffset register).
 //   * a query's 64 scores of a tile sit in 4 lanes (the 4 qd of its column): row maxima of both groups cross lanes with 3 swaps
-//     (permlane16_swap, permlane32_swap, permlane16_swap) and 2 max.
+//     (permlane16_swap, permlane32_swap, permlane16_swap) and 2 max — on the tiles whose sum guard fires only.
 template <int NW, int RESCALE_THR, bool PRESCALED, bool ROT>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned short* __restrict__ Q, int64_t ldq,
                                                                    const unsigned short* __restrict__ Kp, int64_t ldk,
@@ -336,10 +338,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
                                                                    unsigned v_bytes, AttnBatch bs) {
 #if defined(__HIP_DEVICE_COMPILE__)
   static_assert(NW == 8, "DMA piece assignment below is written for 4 issuing waves");
+  static_assert(RESCALE_THR >= 1 && RESCALE_THR <= 30, "A9_GUARD_T is (1 << RESCALE_THR) as a float");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // Work mapping.  The launch grid is (query blocks, heads, sequences) and the dispatcher hands workgroup number L = x + gx (y + gy z) to XCD
   // L % 8 (observed placement; a speed assumption only, MI355X_MICROARCH.md "Workgroup dispatch").  Taken as it comes, the 32 workgroups
-  // resident on an XCD (one per CU: 224 VGPRs = two waves per SIMD = the workgroup's eight waves) belong to ~1-2 heads whose K / V^T streams all eight 4 MiB L2s pull through together.  XCD-aware form
+  // resident on an XCD (one per CU: 216 VGPRs = two waves per SIMD = the workgroup's eight waves) belong to ~1-2 heads whose K / V^T streams all eight 4 MiB L2s pull through together.  XCD-aware form
   // (bit 0 of bs.xcd_remap): XCD c owns the contiguous range c of the (sequence, head, query block) list (bijective for any count), so
   // its resident workgroups are consecutive query blocks of ONE head walking the same K / V^T tiles at about the same time.  Measured
   // (profiles/r03_attn_*): L2 hit rate 73-79 % -> 96 %, L2<->fabric traffic 99-123 GB -> 16 GB per Wan-14B 720p launch — and the launch is
@@ -491,6 +494,33 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
     __builtin_amdgcn_s_setprio(0);                                                                                       \
   }
   // vector half-step: softmax of the tile in sc -> packed bf16 P in pw.  Register r of sc[kt][g] is key 32 (kt >> 1) + 8 qd + 4 (kt & 1) + r.
+  // The hot path goes straight to the 32 exp2 and never looks for the row maxima: the rescale decision "some row's max exceeds the reference by
+  // more than THR" is guarded by the tile-local row sums ts, which are computed anyway.  Scores arrive as s - m_run, so a P = exp2(sc) of a
+  // score with sc > THR is at least 2^THR (1 - 2^-22) (v_exp_f32 is good to about an ulp); every P is >= 0 (never NaN: sc is finite or the
+  // mask's -1e30), and a round-to-nearest fp32 sum of non-negative addends is never below its largest addend (rounding is monotone: a + b >= a
+  // exactly, so RN(a + b) >= RN(a) = a).  The lane that owns such a key therefore holds, for that query group, a tile sum ts[g][0] + ts[g][1]
+  // >= 2^THR (1 - 2^-22) > A9_GUARD_T = 2^THR (1 - 2^-10): whenever the exact condition holds the guard fires (a P of +inf, from a score 128
+  // or more orders above the reference, fires it too).  It may also fire when no single score crossed (eight keys of a lane at 2^5 each,
+  // sixteen at 2^4): the cold branch then finds the exact condition false and shifts nothing.  Behind the exact condition everything is as before — m_run, lsum, oacc, negm and sc shifted in that
+  // order.  The cold branch ends by computing the tile's P, sums and pw again from sc, shifted or not (an unshifted sc gives the same bits;
+  // keeping the hot path's values alive across the max tree instead costs 12 registers and ten copies per loop trip: 228 VGPRs against 216).
+  // The m_run sequence and the bits of every P and oacc are those of the max-on-every-tile form; only the row sums associate differently
+  // (tile sums are added to lsum instead of each P).  The sum chains are sched-barriered every eight exp2 so that hipcc packs each P pair
+  // before it starts the next ones (sc stays live, so the exp2 results need registers of their own).  The adds are the compiler's own
+  // instructions, never inline asm: an asm statement that reads a v_exp_f32 result hides the use from hipcc's hazard recognizer, which then
+  // leaves out the wait state gfx950 needs between a transcendental and a VALU instruction that reads it, and the add sees the old register.
+#define A9_GUARD_T ((float)(1u << RESCALE_THR) * (1.0f - 0x1p-10f))
+#define A9_EXP_TILE() /* P = exp2(sc): two sum chains per query group (ts, started from the first P) and the packed bf16 operand */ \
+  _Pragma("unroll") for (int g = 0; g < 2; ++g) _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) {                       \
+    _Pragma("unroll") for (int e = 0; e < 4; e += 2) {                                                                   \
+      const float p0 = __builtin_amdgcn_exp2f(sc[kt][g][e]), p1 = __builtin_amdgcn_exp2f(sc[kt][g][e + 1]);             \
+      ts[g][0] = (kt | e) ? ts[g][0] + p0 : p0;                                                                          \
+      ts[g][1] = (kt | e) ? ts[g][1] + p1 : p1;                                                                          \
+      asm("" : "+v"(ts[g][0]), "+v"(ts[g][1])); /* scalar chains: packed into v_pk_add_f32 they cost more issue time beside the partner's MFMAs */ \
+      pw[kt >> 1][g][2 * (kt & 1) + (e >> 1)] = pack_bf2(p0, p1);                                                        \
+    }                                                                                                                    \
+    if (kt & 1) A9_SB();                                                                                                 \
+  }
 #define A9_SOFTMAX(LAST_)                                                                                                \
   {                                                                                                                      \
     if ((LAST_) && (int64_t)(t + 1) * AT_KV > Sk) {                                                                      \
@@ -498,42 +528,45 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
       _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) _Pragma("unroll") for (int r = 0; r < 4; ++r)                     \
         if (32 * (kt >> 1) + 8 * qd + 4 * (kt & 1) + r >= left) { sc[kt][0][r] = -1e30f; sc[kt][1][r] = -1e30f; }        \
     }                                                                                                                    \
-    float mg[2];                                                                                                         \
-    _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                      \
-      const float a_ = vmax3(sc[0][g][0], sc[0][g][1], sc[0][g][2]), b_ = vmax3(sc[0][g][3], sc[1][g][0], sc[1][g][1]);   \
-      const float c_ = vmax3(sc[1][g][2], sc[1][g][3], sc[2][g][0]), d_ = vmax3(sc[2][g][1], sc[2][g][2], sc[2][g][3]);   \
-      const float e_ = vmax3(sc[3][g][0], sc[3][g][1], sc[3][g][2]);                                                     \
-      mg[g] = vmax3(vmax3(a_, b_, c_), vmax3(d_, e_, sc[3][g][3]), -3.0e38f);                                            \
-    }                                                                                                                    \
-    { /* across the four lanes (qd) of a query column, both groups at once: rows {A01, B01, A23, B23} -> {A, B, A, B} -> A | B */ \
-      auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(mg[0]), __float_as_uint(mg[1]), false, false);         \
-      const float c1 = vmax2(__uint_as_float(s1[0]), __uint_as_float(s1[1]));                                            \
-      auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c1), __float_as_uint(c1), false, false);               \
-      const float c2 = vmax2(__uint_as_float(s2[0]), __uint_as_float(s2[1]));                                            \
-      auto s3 = __builtin_amdgcn_permlane16_swap(__float_as_uint(c2), __float_as_uint(c2), false, false);               \
-      mg[0] = __uint_as_float(s3[0]);                                                                                    \
-      mg[1] = __uint_as_float(s3[1]);                                                                                    \
-    }                                                                                                                    \
-    if (force || __any(vmax2(mg[0], mg[1]) > (float)RESCALE_THR)) { /* cold: some row's max grew by more than THR (or first tile) */ \
+    float ts[2][2];                                                                                                      \
+    A9_EXP_TILE()                                                                                                        \
+    if (force || __any(vmax2(ts[0][0] + ts[0][1], ts[1][0] + ts[1][1]) >= A9_GUARD_T)) { /* cold: first tile, or some P may exceed 2^THR */ \
+      float mg[2];                                                                                                       \
       _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                    \
-        const float d = force ? mg[g] : fmaxf(mg[g], 0.f);                                                               \
-        m_run[g] += d;                                                                                                   \
-        if (!force) {                                                                                                    \
-          const float al = __builtin_amdgcn_exp2f(-d);                                                                   \
-          lsum[g][0] *= al;                                                                                              \
-          lsum[g][1] *= al;                                                                                              \
-          _Pragma("unroll") for (int T = 0; T < 8; ++T) _Pragma("unroll") for (int e = 0; e < 4; ++e) oacc[T][g][e] *= al; \
-        }                                                                                                                \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) negm[g][e] = -m_run[g];                                            \
-        _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) _Pragma("unroll") for (int e = 0; e < 4; ++e) sc[kt][g][e] -= d; \
+        const float a_ = vmax3(sc[0][g][0], sc[0][g][1], sc[0][g][2]), b_ = vmax3(sc[0][g][3], sc[1][g][0], sc[1][g][1]); \
+        const float c_ = vmax3(sc[1][g][2], sc[1][g][3], sc[2][g][0]), d_ = vmax3(sc[2][g][1], sc[2][g][2], sc[2][g][3]); \
+        const float e_ = vmax3(sc[3][g][0], sc[3][g][1], sc[3][g][2]);                                                   \
+        mg[g] = vmax3(vmax3(a_, b_, c_), vmax3(d_, e_, sc[3][g][3]), -3.0e38f);                                          \
       }                                                                                                                  \
-      force = false;                                                                                                     \
+      { /* across the four lanes (qd) of a query column, both groups at once: rows {A01, B01, A23, B23} -> {A, B, A, B} -> A | B */ \
+        auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(mg[0]), __float_as_uint(mg[1]), false, false);       \
+        const float c1 = vmax2(__uint_as_float(s1[0]), __uint_as_float(s1[1]));                                          \
+        auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c1), __float_as_uint(c1), false, false);             \
+        const float c2 = vmax2(__uint_as_float(s2[0]), __uint_as_float(s2[1]));                                          \
+        auto s3 = __builtin_amdgcn_permlane16_swap(__float_as_uint(c2), __float_as_uint(c2), false, false);             \
+        mg[0] = __uint_as_float(s3[0]);                                                                                  \
+        mg[1] = __uint_as_float(s3[1]);                                                                                  \
+      }                                                                                                                  \
+      if (force || __any(vmax2(mg[0], mg[1]) > (float)RESCALE_THR)) { /* some row's max grew by more than THR (or first tile) */ \
+        _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                  \
+          const float d = force ? mg[g] : fmaxf(mg[g], 0.f);                                                             \
+          m_run[g] += d;                                                                                                 \
+          if (!force) {                                                                                                  \
+            const float al = __builtin_amdgcn_exp2f(-d);                                                                 \
+            lsum[g][0] *= al;                                                                                            \
+            lsum[g][1] *= al;                                                                                            \
+            _Pragma("unroll") for (int T = 0; T < 8; ++T) _Pragma("unroll") for (int e = 0; e < 4; ++e) oacc[T][g][e] *= al; \
+          }                                                                                                              \
+          _Pragma("unroll") for (int e = 0; e < 4; ++e) negm[g][e] = -m_run[g];                                          \
+          _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) _Pragma("unroll") for (int e = 0; e < 4; ++e) sc[kt][g][e] -= d; \
+        }                                                                                                                \
+        force = false;                                                                                                   \
+      }                                                                                                                  \
+      A9_EXP_TILE()                                                                                                      \
     }                                                                                                                    \
-    _Pragma("unroll") for (int g = 0; g < 2; ++g) _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) _Pragma("unroll") for (int e = 0; e < 4; e += 2) { \
-      const float p0 = __builtin_amdgcn_exp2f(sc[kt][g][e]), p1 = __builtin_amdgcn_exp2f(sc[kt][g][e + 1]);             \
-      lsum[g][0] += p0;                                                                                                  \
-      lsum[g][1] += p1;                                                                                                  \
-      pw[kt >> 1][g][2 * (kt & 1) + (e >> 1)] = pack_bf2(p0, p1);                                                        \
+    _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                      \
+      lsum[g][0] += ts[g][0];                                                                                            \
+      lsum[g][1] += ts[g][1];                                                                                            \
     }                                                                                                                    \
     { /* the row sums belong to THIS half-step */                                                                        \
       asm volatile("" : "+v"(lsum[0][0]), "+v"(lsum[0][1]), "+v"(lsum[1][0]), "+v"(lsum[1][1]));                         \
@@ -621,7 +654,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
 #undef A9_BAR_EVEN
 #undef A9_BARRIER
 #undef A9_BAR_ODD
-  // (A9_SOFTMAX, A9_MATRIX, A9_FRAG, A9_SB, A9_DMA_K, A9_DMA_V stay defined for the persistent form below)
+  // (A9_SOFTMAX with A9_EXP_TILE and A9_GUARD_T, A9_MATRIX, A9_FRAG, A9_SB, A9_DMA_K, A9_DMA_V stay defined for the persistent form below)
 
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
@@ -1011,6 +1044,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_p9_kernel(const unsigned shor
 #endif
 }
 #undef A9_SOFTMAX
+#undef A9_EXP_TILE
+#undef A9_GUARD_T
 #undef A9_MATRIX
 #undef A9_FRAG
 #undef A9_SB
