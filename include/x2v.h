@@ -515,11 +515,16 @@ int x2v_blend_axis_f32(const float* a, float* b, int64_t outer, int na, int nb, 
 #define X2V_EPI16_NONE 0     /* y = fp16(acc + bias) */
 #define X2V_EPI16_GELU_ERF 1 /* y = fp16(gelu_erf(acc + bias))                       (nn.GELU() of AttentionBlock.mlp, xlm_roberta/model.py:150-153) */
 #define X2V_EPI16_RESIDUAL 2 /* y = fp16(resid + fp16(acc + bias)); y may alias resid (x + self.attn(...) / x + self.mlp(...), model.py:162-163) */
+#define X2V_EPI16_QUICK_GELU 3 /* y = fp16(v * sigmoid(1.702 v)), v = acc + bias in fp32; bias must be given (transformers' QuickGELUActivation after CLIPMLP.fc1) */
+#define X2V_EPI16_SWIGLU 4     /* W is [2N, K], row 2n = gate_proj row n, row 2n + 1 = up_proj row n: y[M, N] = fp16(silu(fp16(acc_gate)) * fp16(acc_up)), the SiLU
+                                * and the product in fp32 on the two fp16 Linear outputs (transformers' LlamaMLP); bias must be NULL, N even */
 
 /* y[M,N] = epi(x[M,K] . W[N,K]^T + bias) in fp16 with fp32 accumulation, for M of a few hundred rows (257 tokens per image) — replaces the nn.Linear calls
  * of SelfAttention.to_qkv / proj (model.py:82,89), AttentionBlock.mlp (:150-153) and, on the patch-major operand of x2v_clip_preprocess_f16 with
  * bias = NULL, VisionTransformer.patch_embedding (:253,278).  K % 32 == 0 (pad both operands with zero columns), N % 4 == 0; bias may be NULL.
- * Each output value is reduced in k order whatever M: rows of a batch equal the rows computed alone, bit for bit. */
+ * Each output value is reduced in k order whatever M: rows of a batch equal the rows computed alone, bit for bit.  Every M from 0 (nothing launched) to
+ * 4 194 240 (the grid's limit at the smallest tile) is admitted; the form streams W once per 64 or 128 rows and is meant for M up to a few thousand.
+ * With X2V_EPI16_SWIGLU N counts y's columns, W has 2N rows and the tile is the one x2v_gemm_f16_tile_choice gives for (M, 2N). */
 int x2v_gemm_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K, int epilogue,
                  const void* resid, int64_t ldr, void* stream);
 
@@ -577,6 +582,28 @@ int x2v_gemm_rows_bf16_tile_choice(int64_t M, int N, int epilogue);
  * rounding of the output. */
 int x2v_attn_bf16_d64_relbias(const void* qkv, int64_t ld, const float* bias, void* out, int64_t ldo, const int* cu_seqlens, int batch, int num_heads,
                               float scale, void* stream);
+
+/* ---- HunyuanVideo's text towers (fp16): the producers of text_encoder_output["text_encoder_1_text_states"] / ["text_encoder_2_text_states"]
+ * (runners/hunyuan/hunyuan_runner.py:58-67) — transformers' LlamaModel behind input_encoders/hf/llama/model.py and CLIPTextModel behind
+ * input_encoders/hf/clip/model.py.  Their Linears are x2v_gemm_f16 (X2V_EPI16_SWIGLU / X2V_EPI16_QUICK_GELU), CLIP's LayerNorm is x2v_layernorm_f16. ---- */
+
+/* out[r0_b + i, h*d : h*d + d] = softmax_{j <= i}(scale * q_i . k_j) v_j over the keys 0..i of sequence b only: causal, grouped-query attention in fp16,
+ * d = head_dim in {64, 128} — replaces apply_rotary_pos_emb, repeat_kv and the causal softmax attention of transformers' LlamaAttention.forward, and (with
+ * the tables NULL, num_kv_heads = num_heads) CLIPAttention.forward under CLIPTextTransformer's causal mask.  `batch` <= 8 sequences of 1..512 tokens are
+ * packed row after row, sequence b being rows cu_seqlens[b] .. cu_seqlens[b+1] - 1 (r0_b = cu_seqlens[b]); cu_seqlens is a HOST array of batch + 1
+ * increasing ints, passed on to the kernel by value.  qkv is the fused projection output read in place: a row of stride ld holds q at column 0
+ * (num_heads * d), k at num_heads * d (num_kv_heads * d) and v at (num_heads + num_kv_heads) * d; query head h reads key/value head
+ * h / (num_heads / num_kv_heads); rows outside every sequence are neither read nor written.  rope_cos / rope_sin: device fp32 tables [>= 512][d / 2],
+ * entry [p][i] = cos / sin(p * theta^(-2i/d)), or both NULL; given (head_dim 128 only, else X2V_E_ARG), q and k are rotated in fp32 at p = index within
+ * the sequence, t * cos + cat(-t[d/2:], t[:d/2]) * sin with the table row repeated over both halves, and rounded once to fp16 as the matrix operands.
+ * scale = 0 means d^-1/2.  fp32 scores, maximum, exp and sum (online over 64-key tiles); P rounded to fp16 for the PV product, fp32 accumulation, one
+ * rounding of the output. */
+int x2v_attn_f16_causal(const void* qkv, int64_t ld, void* out, int64_t ldo, const int* cu_seqlens, int batch, int num_heads, int num_kv_heads, int head_dim,
+                        const float* rope_cos, const float* rope_sin, float scale, void* stream);
+
+/* y[M,D] = fp16(w * x * rsqrt(mean(x^2) + eps)) with fp32 statistics and one rounding; x, w, y fp16 — replaces transformers' LlamaRMSNorm.forward, which
+ * rounds x * rsqrt(...) to fp16 before the weight multiply and the product again.  D % 8 == 0, D <= 8192. */
+int x2v_rmsnorm_f16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t M, int D, float eps, void* stream);
 
 /* Box calibration (measurement plumbing; no reference counterpart): runs bare v_mfma_f32_16x16x32_bf16 loops (operands in registers,
  * 8 waves per CU, every CU) for `milliseconds` on `stream` and returns in *tflops what the board sustained over the second half of that time.

@@ -227,8 +227,14 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_f16_tile_choice(i
 extern "C" __attribute__((visibility("default"))) int x2v_gemm_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M,
                                                                    int N, int K, int epilogue, const void* resid, int64_t ldr, void* stream) {
   X2V_REQUIRE(x && w && y, X2V_E_ARG, "gemm_f16: null pointer");
-  X2V_REQUIRE(epilogue == X2V_EPI16_NONE || epilogue == X2V_EPI16_GELU_ERF || epilogue == X2V_EPI16_RESIDUAL, X2V_E_ARG, "gemm_f16: unknown epilogue %d", epilogue);
-  return gemm_rows_launch<_Float16>("gemm_f16", x, ldx, w, ldw, bias, y, ldy, M, N, K, epilogue, resid, ldr, stream);
+  X2V_REQUIRE(epilogue >= X2V_EPI16_NONE && epilogue <= X2V_EPI16_SWIGLU, X2V_E_ARG, "gemm_f16: unknown epilogue %d", epilogue);
+  X2V_REQUIRE(epilogue != X2V_EPI16_QUICK_GELU || bias != nullptr, X2V_E_ARG, "gemm_f16: the quick-GELU epilogue needs a bias (CLIPMLP.fc1 has one)");
+  if (epilogue == X2V_EPI16_SWIGLU) {  // W holds 2N rows (gate_proj and up_proj interleaved), y has N columns
+    X2V_REQUIRE(bias == nullptr, X2V_E_ARG, "gemm_f16: the SwiGLU epilogue takes no bias");
+    X2V_REQUIRE(N > 0 && N % 2 == 0 && N < (1 << 30), X2V_E_SHAPE, "gemm_f16: N=%d must be even with the SwiGLU epilogue", N);
+    return gemm_rows_launch<_Float16>("gemm_f16", x, ldx, w, ldw, nullptr, y, ldy, M, 2 * N, K, ROWS_EPI_SWIGLU, resid, ldr, stream);
+  }
+  return gemm_rows_launch<_Float16>("gemm_f16", x, ldx, w, ldw, bias, y, ldy, M, N, K, epilogue == X2V_EPI16_QUICK_GELU ? ROWS_EPI_QUICK_GELU : epilogue, resid, ldr, stream);
 }
 
 extern "C" __attribute__((visibility("default"))) int x2v_attn_f16_d80(const void* qkv, int64_t ld, void* out, int64_t ldo, int batch, int S, int num_heads, float scale,

@@ -7,8 +7,9 @@
 //   contiguous bytes of one row.  A 4-deep register ring of k-steps keeps 4 x (MT + NT) 16-byte loads per lane in flight.  The launcher takes the largest tile
 //   of {128x64, 64x64, 64x32, 64x16} that still yields >= 192 workgroups.  Every output value is reduced in k order by one lane whatever the tile and whatever
 //   M: batching rows is bit-identical.
-// Epilogues (ROWS_EPI_*; each entry admits its own subset): plain, exact GELU (fp16), residual, and GEGLU (bf16): W holds the rows of two Linears interleaved
-//   (row 2n of one, row 2n + 1 of its gate), so a lane's 4 columns are two (value, gate) pairs and it stores 2 output columns of y[M, N / 2].
+// Epilogues (ROWS_EPI_*; each entry admits its own subset): plain, exact GELU (fp16), quick-GELU (fp16), residual, and the two gated ones, GEGLU (bf16) and
+//   SwiGLU (fp16): W holds the rows of two Linears interleaved (row 2n of one, row 2n + 1 of the other), so a lane's 4 columns are two pairs and it stores
+//   2 output columns of y[M, N / 2].  GEGLU: (value, gate) = fc1 * gelu_tanh(gate.0); SwiGLU: (gate, up) = silu(gate_proj) * up_proj.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -26,6 +27,10 @@ __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f +
 
 constexpr int GF_RING = 4;
 constexpr int ROWS_EPI_NONE = 0, ROWS_EPI_GELU_ERF = 1, ROWS_EPI_RESIDUAL = 2, ROWS_EPI_GEGLU = 3;  // NONE / GELU_ERF / RESIDUAL are X2V_EPI16_*'s values
+constexpr int ROWS_EPI_QUICK_GELU = 4, ROWS_EPI_SWIGLU = 5;                                           // fp16 only (X2V_EPI16_QUICK_GELU / _SWIGLU, mapped by the entry)
+constexpr bool rows_epi_gated(int epi) { return epi == ROWS_EPI_GEGLU || epi == ROWS_EPI_SWIGLU; }
+
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 template <typename T>
 struct RowsElem;
@@ -106,14 +111,18 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const T* __restrict__ x,
       const int n = n0 + 16 * j + 4 * g4;
       if (n >= N) continue;
       float v[4] = {acc[j][i][0], acc[j][i][1], acc[j][i][2], acc[j][i][3]};
-      if constexpr (std::is_same<T, __bf16>::value) {
-        if (epi == ROWS_EPI_GEGLU) {  // torch: fc1(h) * gelu(gate(h)) on two bf16 Linear outputs; the GELU itself in fp32
-          typename RowsElem<T>::v2 o2;
+      // the gated epilogues: torch multiplies two 16-bit Linear outputs, the activation of one of them evaluated in fp32.  GEGLU (bf16): fc1(h) *
+      // gelu(gate(h)); SwiGLU (fp16): silu(gate_proj(h)) * up_proj(h)
+      if (epi == (std::is_same<T, __bf16>::value ? ROWS_EPI_GEGLU : ROWS_EPI_SWIGLU)) {
+        typename RowsElem<T>::v2 o2;
 #pragma unroll
-          for (int e = 0; e < 2; ++e) o2[e] = (T)((float)(T)v[2 * e] * gelu_tanh_f((float)(T)v[2 * e + 1]));
-          *reinterpret_cast<typename RowsElem<T>::v2*>(y + (int64_t)m * ldy + n / 2) = o2;
-          continue;
+        for (int e = 0; e < 2; ++e) {
+          const float a = (float)(T)v[2 * e], g = (float)(T)v[2 * e + 1];
+          if constexpr (std::is_same<T, __bf16>::value) o2[e] = (T)(a * gelu_tanh_f(g));
+          else o2[e] = (T)(a * sigmoid_f(a) * g);
         }
+        *reinterpret_cast<typename RowsElem<T>::v2*>(y + (int64_t)m * ldy + n / 2) = o2;
+        continue;
       }
       if (bias != nullptr) {
         const v4 bv = *reinterpret_cast<const v4*>(bias + n);
@@ -123,6 +132,9 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const T* __restrict__ x,
       if (std::is_same<T, _Float16>::value && epi == ROWS_EPI_GELU_ERF) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = gelu_erf_f(v[e]);
+      } else if (std::is_same<T, _Float16>::value && epi == ROWS_EPI_QUICK_GELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] * sigmoid_f(1.702f * v[e]);
       } else if (epi == ROWS_EPI_RESIDUAL) {  // torch: x + linear(...) on two 16-bit tensors
         const v4 rv = *reinterpret_cast<const v4*>(resid + (int64_t)m * ldr + n);
 #pragma unroll
@@ -149,7 +161,7 @@ static inline int gemm_rows_tile_choice(int64_t M, int N) {
 }
 
 // Checks and launch shared by the two entries (`who` starts every error text; the entry has checked its own epilogue set).  N counts W's rows: with
-// ROWS_EPI_GEGLU y has N / 2 columns.
+// a gated epilogue y has N / 2 columns.
 template <typename T>
 static int gemm_rows_launch(const char* who, const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K, int epilogue,
                             const void* resid, int64_t ldr, void* stream) {
@@ -158,7 +170,7 @@ static int gemm_rows_launch(const char* who, const void* x, int64_t ldx, const v
   X2V_REQUIRE(M >= 0 && M < (1ll << 31) && N > 0 && K > 0, X2V_E_SHAPE, "%s: bad shape M=%lld N=%d K=%d", who, (long long)M, N, K);
   X2V_REQUIRE(K % 32 == 0, X2V_E_SHAPE, "%s: K=%d must be a multiple of 32 (pad the operands with zero columns)", who, K);
   X2V_REQUIRE(N % 4 == 0, X2V_E_SHAPE, "%s: N=%d must be a multiple of 4", who, N);
-  const int ny = epilogue == ROWS_EPI_GEGLU ? N / 2 : N;
+  const int ny = rows_epi_gated(epilogue) ? N / 2 : N;
   X2V_REQUIRE(ldx >= K && ldw >= K && ldy >= ny && ldx % 8 == 0 && ldw % 8 == 0 && ldy % 4 == 0 && (resid == nullptr || (ldr >= N && ldr % 4 == 0)), X2V_E_ALIGN,
               "%s: leading dimensions must cover the rows (ldx, ldw multiples of 8, ldy, ldr of 4 %s)", who, RowsElem<T>::unit());
   X2V_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(bias) && aligned16(resid), X2V_E_ALIGN, "%s: pointers must be 16-byte aligned", who);

@@ -100,6 +100,8 @@ PROTOTYPES = {
     "x2v_gemm_rows_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
     "x2v_gemm_rows_bf16_tile_choice": [_i64, _i32, _i32],
     "x2v_attn_bf16_d64_relbias": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, ctypes.POINTER(_i32), _i32, _i32, _f32, _c_void_p],
+    "x2v_attn_f16_causal": [_c_void_p, _i64, _c_void_p, _i64, ctypes.POINTER(_i32), _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p],
+    "x2v_rmsnorm_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _f32, _c_void_p],
     "x2v_vae_replicate_border_f32": [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
@@ -1118,7 +1120,7 @@ def distill_step(cond, uncond, guide, latents, noise, sigma, one_minus_next, sig
 
 
 # ---- CLIP image tower (fp16; csrc/clip.hip) ---------------------------------------------------------------------------------------------------------
-EPI16_NONE, EPI16_GELU_ERF, EPI16_RESIDUAL = 0, 1, 2
+EPI16_NONE, EPI16_GELU_ERF, EPI16_RESIDUAL, EPI16_QUICK_GELU, EPI16_SWIGLU = 0, 1, 2, 3, 4
 
 
 def _f16rows(t, name):
@@ -1128,10 +1130,13 @@ def _f16rows(t, name):
 
 
 def gemm_f16(x, weight_nk, bias=None, epilogue=EPI16_NONE, resid=None, out=None):
-    """x2v_gemm_f16: y[M, N] = epi(x[M, K] . W[N, K]^T + bias) in fp16 (fp32 accumulation); K % 32 == 0, N % 4 == 0."""
+    """x2v_gemm_f16: y[M, N] = epi(x[M, K] . W[N, K]^T + bias) in fp16 (fp32 accumulation); K % 32 == 0, N % 4 == 0.  With EPI16_SWIGLU W is [2N, K]
+    (rows of gate_proj and up_proj interleaved) and there is no bias."""
     x, w = _f16rows(x, "gemm_f16 x"), _f16rows(weight_nk, "gemm_f16 weight")
     M, K = x.shape
-    N = w.shape[0]
+    if epilogue == EPI16_SWIGLU and w.shape[0] % 2:
+        raise X2VError(f"gemm_f16: the SwiGLU epilogue needs an even number of weight rows, got {w.shape[0]}")
+    N = w.shape[0] // 2 if epilogue == EPI16_SWIGLU else w.shape[0]
     if w.shape[1] != K:
         raise X2VError(f"gemm_f16: x {tuple(x.shape)} and weight {tuple(w.shape)} disagree on K")
     bias = _vec(bias, "gemm_f16 bias", N, dtype=torch.float16)
@@ -1283,4 +1288,46 @@ def attention_bf16_d64_relbias(qkv, bias, cu_seqlens, num_heads, out=None, scale
         raise X2VError(f"{who}: out must be [{qkv.shape[0]}, {D}]")
     init()
     _check(_lib.x2v_attn_bf16_d64_relbias(_p(qkv), qkv.stride(0), _p(bias), _p(out), out.stride(0), cu, batch, num_heads, float(scale), _stream()), who)
+    return out
+
+
+# ---- HunyuanVideo's text towers (fp16; csrc/txt_enc.hip) ------------------------------------------------------------------------------------------------
+ATTN_CAUSAL_MAX_BATCH, ATTN_CAUSAL_MAX_LEN = 8, 512
+
+
+def attention_f16_causal(qkv, cu_seqlens, num_heads, num_kv_heads, head_dim, rope=None, out=None, scale=0.0):
+    """x2v_attn_f16_causal on the fused q | k | v GEMM output qkv [rows, (num_heads + 2 num_kv_heads) * head_dim] fp16 (read in place; a row stride beyond
+    its columns is fine) -> [rows, num_heads * head_dim] fp16.  cu_seqlens: host ints, sequence b = rows cu[b] .. cu[b + 1] - 1.  rope: None or the
+    (cos, sin) fp32 device tables [>= 512, head_dim / 2] (head_dim 128).  Rows outside every sequence are not written."""
+    who = "attention_f16_causal"
+    qkv = _f16rows(qkv, who + " qkv")
+    D = num_heads * head_dim
+    if qkv.shape[1] != (num_heads + 2 * num_kv_heads) * head_dim:
+        raise X2VError(f"{who}: qkv {tuple(qkv.shape)} is not [rows, ({num_heads} + 2 * {num_kv_heads}) * {head_dim}] (q | k | v side by side; pass the whole rows)")
+    cos = sin = None
+    if rope is not None:
+        cos, sin = (_vec(t, who + " rope table", None, dtype=torch.float32) for t in rope)
+        if cos.numel() != sin.numel() or cos.numel() < ATTN_CAUSAL_MAX_LEN * (head_dim // 2):
+            raise X2VError(f"{who}: the rope tables must both hold at least [{ATTN_CAUSAL_MAX_LEN}, {head_dim // 2}] fp32 values")
+    cu, batch = _cu_seqlens(cu_seqlens, qkv.shape[0], who)
+    out = torch.empty((qkv.shape[0], D), dtype=torch.float16, device=qkv.device) if out is None else _f16rows(out, who + " out")
+    if out.shape != (qkv.shape[0], D):
+        raise X2VError(f"{who}: out must be [{qkv.shape[0]}, {D}]")
+    init()
+    _check(_lib.x2v_attn_f16_causal(_p(qkv), qkv.stride(0), _p(out), out.stride(0), cu, batch, num_heads, num_kv_heads, head_dim, _p(cos), _p(sin), float(scale), _stream()), who)
+    return out
+
+
+def rmsnorm_f16(x, weight, eps=1e-5, out=None):
+    """x2v_rmsnorm_f16: fp16 rows and weight, fp32 statistics, one rounding."""
+    x = _f16rows(x, "rmsnorm_f16 x")
+    D = x.shape[1]
+    weight = _vec(weight, "rmsnorm_f16 weight", D, dtype=torch.float16)
+    if weight is None:
+        raise X2VError("rmsnorm_f16: weight is required")
+    out = torch.empty_like(x) if out is None else _f16rows(out, "rmsnorm_f16 out")
+    if out.shape != x.shape:
+        raise X2VError(f"rmsnorm_f16: out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    init()
+    _check(_lib.x2v_rmsnorm_f16(_p(x), x.stride(0), _p(weight), _p(out), out.stride(0), x.shape[0], D, eps, _stream()), "rmsnorm_f16")
     return out

@@ -5,6 +5,7 @@
     x2v.use_fused_wan_block()              # optional: WanModel picks the fused HIP block driver
     x2v.use_fused_hunyuan_block()          # optional: HunyuanModel picks the fused HIP double / single block driver
     x2v.use_hip_clip_encoder()             # optional: WanRunner.load_image_encoder builds the HIP CLIP image tower (i2v)
+    x2v.use_hip_hunyuan_text_encoders()    # optional: HunyuanRunner.load_text_encoder builds the HIP Llama and CLIP-L text towers (t2v)
 
 After that an unchanged LightX2V config selects the HIP path by string:
     "mm_config": {"mm_type": "Hip-bf16"}   (or "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip" / "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip")
@@ -73,6 +74,19 @@ def use_hip_clip_encoder():
     from . import clip
 
     wan_runner.CLIPModel = clip.CLIPModel
+
+
+def use_hip_hunyuan_text_encoders():
+    """Make HunyuanRunner.load_text_encoder (runners/hunyuan/hunyuan_runner.py:30-37) build this package's two text towers: the runner module binds
+    TextEncoderHFLlamaModel and TextEncoderHFClipModel by name (:8-10) and calls them with (model directory, device); run_text_encoder (:58-67) only calls
+    `.infer(text, config)`.  `task: "i2v"` keeps the reference's LLaVA class as encoder 1 (not built here); `cpu_offload: true` raises NotImplementedError
+    in `infer`."""
+    from lightx2v.models.runners.hunyuan import hunyuan_runner
+
+    from . import clip_text, llama
+
+    hunyuan_runner.TextEncoderHFLlamaModel = llama.TextEncoderHFLlamaModel
+    hunyuan_runner.TextEncoderHFClipModel = clip_text.TextEncoderHFClipModel
 
 
 def use_fused_hunyuan_block():

@@ -224,6 +224,80 @@ def synth_t5_weights(dims, seed=0, device="cpu"):
     return wd
 
 
+# HunyuanVideo's text towers: the released text_encoder (Llama-3-8B decoder stack) and text_encoder_2 (CLIP-L text model) configs, and tiny ones of the
+# same head dims (128 with 2 query heads per key/value head; 64)
+LLAMA_DIMS = {
+    "llama3-8b": dict(vocab=128256, dim=4096, heads=32, kv_heads=8, head_dim=128, ffn=14336, layers=32, rope_theta=500000.0, eps=1e-5),
+    "llama-tiny": dict(vocab=384, dim=512, heads=4, kv_heads=2, head_dim=128, ffn=448, layers=4, rope_theta=500000.0, eps=1e-5),
+}
+CLIP_TEXT_DIMS = {
+    "clip-l": dict(vocab=49408, dim=768, heads=12, head_dim=64, ffn=3072, layers=12, positions=77, eps=1e-5, eos_token_id=2),
+    # wide and deep enough that the tiny fixture tells quick-GELU from the exact GELU beyond 1e-2 (tests/test_hunyuan_text_host.py)
+    "clip-text-tiny": dict(vocab=512, dim=256, heads=4, head_dim=64, ffn=2048, layers=4, positions=77, eps=1e-5, eos_token_id=2),
+}
+
+
+def synth_llama_weights(dims, seed=0, device="cpu"):
+    """transformers' LlamaModel.state_dict() names and shapes at `dims`, fp16, drawn on `device`: Linears N(0, 0.05^2), norm weights 1 + 0.1 N(0, 1),
+    the embedding N(0, 1)."""
+    D, H, Hkv, d, F = dims["dim"], dims["heads"], dims["kv_heads"], dims["head_dim"], dims["ffn"]
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev if dev.type != "cpu" else "cpu").manual_seed(seed + 811)
+    wd = {}
+
+    def rn(shape, std=0.05):
+        return _randn(shape, std, gen, dev, torch.float16)
+
+    def norm():
+        return (1.0 + _randn((D,), 0.1, gen, dev, torch.float32)).to(torch.float16)
+
+    wd["embed_tokens.weight"] = rn((dims["vocab"], D), 1.0)
+    for i in range(dims["layers"]):
+        p = f"layers.{i}"
+        wd[f"{p}.input_layernorm.weight"] = norm()
+        wd[f"{p}.self_attn.q_proj.weight"] = rn((H * d, D))
+        wd[f"{p}.self_attn.k_proj.weight"] = rn((Hkv * d, D))
+        wd[f"{p}.self_attn.v_proj.weight"] = rn((Hkv * d, D))
+        wd[f"{p}.self_attn.o_proj.weight"] = rn((D, H * d))
+        wd[f"{p}.post_attention_layernorm.weight"] = norm()
+        wd[f"{p}.mlp.gate_proj.weight"] = rn((F, D))
+        wd[f"{p}.mlp.up_proj.weight"] = rn((F, D))
+        wd[f"{p}.mlp.down_proj.weight"] = rn((D, F))
+    wd["norm.weight"] = norm()
+    return wd
+
+
+def synth_clip_text_weights(dims, seed=0, device="cpu"):
+    """transformers' CLIPTextModel names (under `text_model.`, as the released checkpoint has them) and shapes at `dims`, fp16: Linears N(0, 0.05^2) with
+    biases N(0, 0.02^2), norm weights 1 + 0.1 N(0, 1) with biases N(0, 0.02^2), both embeddings N(0, 1)."""
+    D, F = dims["dim"], dims["ffn"]
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev if dev.type != "cpu" else "cpu").manual_seed(seed + 907)
+    wd = {}
+
+    def rn(shape, std=0.05):
+        return _randn(shape, std, gen, dev, torch.float16)
+
+    def linear(name, n, k):
+        wd[f"{name}.weight"], wd[f"{name}.bias"] = rn((n, k)), rn((n,), 0.02)
+
+    def norm(name):
+        wd[f"{name}.weight"], wd[f"{name}.bias"] = (1.0 + _randn((D,), 0.1, gen, dev, torch.float32)).to(torch.float16), rn((D,), 0.02)
+
+    wd["text_model.embeddings.token_embedding.weight"] = rn((dims["vocab"], D), 1.0)
+    wd["text_model.embeddings.position_embedding.weight"] = rn((dims["positions"], D), 1.0)
+    for i in range(dims["layers"]):
+        p = f"text_model.encoder.layers.{i}"
+        norm(f"{p}.layer_norm1")
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            linear(f"{p}.self_attn.{n}", D, D)
+        norm(f"{p}.layer_norm2")
+        linear(f"{p}.mlp.fc1", F, D)
+        linear(f"{p}.mlp.fc2", D, F)
+    norm("text_model.final_layer_norm")
+    return wd
+
+
 def synth_inputs(dims, target_shape, seed=42, device="cpu"):
     """Latents exactly as the reference seeds them (wan/scheduler.py:25-28,54-63: randn(target_shape),
     fp32, seed 42) but always drawn from the CPU stream so CPU oracle and GPU path see identical noise
