@@ -309,7 +309,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const unsigne
 //     previous half-step), q carries scale*log2(e) (PRESCALED: folded in by the producer), so P = exp2(S') with no per-score FMA; rescale stays
 //     lazy (cold branch, threshold RESCALE_THR in base-2 units), and the search for the tile's row maxima that decides it sits in that cold
 //     branch too, behind a guard on the lane's tile sums of P (A9_SOFTMAX: a sum of non-negative P reaches 2^THR whenever one of them does), so
-//     a softmax half-step is 32 exp2, 28 adds, 16 packs and a 4-instruction guard; the first MFMA of every score chain is an asm statement
+//     a softmax half-step is 32 exp2, 28 adds, 16 packs and a 4-instruction guard, with no register copy; the first MFMA of every score chain is an asm statement
 //     with an early-clobber destination so that hipcc never computes into (and then restores) the -m tuple;
 //   * a straight-line loop per role (early / late waves), unrolled x2 so both LDS buffer indices are compile-time and every fragment address is
 //     register + immediate; one score buffer: nothing spills at 2 waves per SIMD (216 VGPRs).
@@ -506,17 +506,28 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
   // keeping the hot path's values alive across the max tree instead costs 12 registers and ten copies per loop trip: 228 VGPRs against 216).
   // The m_run sequence and the bits of every P and oacc are those of the max-on-every-tile form; only the row sums associate differently
   // (tile sums are added to lsum instead of each P).  The sum chains are sched-barriered every eight exp2 so that hipcc packs each P pair
-  // before it starts the next ones (sc stays live, so the exp2 results need registers of their own).  The adds are the compiler's own
+  // before it starts the next ones (sc stays live, so the exp2 results need registers of their own).  On the hot path a chain starts as its
+  // first P under no asm operand: an operand that nominally modifies it while pack_bf2 still reads the P costs a v_mov_b32 per chain.  The
+  // cold branch's copy of the tile keeps that operand on purpose: written alike, hipcc gives the two copies' first sums one virtual register
+  // and a copy in front of the hot path's first asm survives register coalescing (4 v_mov_b32 again, one VGPR more).  The guard stays the sum
+  // of a group's two chains: the largest of the four chain sums is a sound witness too and one instruction shorter (v_max3, v_max, compare),
+  // but its two dependent asm statements, each padded with a wait state, measured 1.6 % slower per launch.  The adds are the compiler's own
   // instructions, never inline asm: an asm statement that reads a v_exp_f32 result hides the use from hipcc's hazard recognizer, which then
   // leaves out the wait state gfx950 needs between a transcendental and a VALU instruction that reads it, and the add sees the old register.
 #define A9_GUARD_T ((float)(1u << RESCALE_THR) * (1.0f - 0x1p-10f))
-#define A9_EXP_TILE() /* P = exp2(sc): two sum chains per query group (ts, started from the first P) and the packed bf16 operand */ \
+#define A9_EXP_TILE(COLD_) /* P = exp2(sc): two sum chains per query group (ts, started from the first P) and the packed bf16 operand */   \
   _Pragma("unroll") for (int g = 0; g < 2; ++g) _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) {                       \
     _Pragma("unroll") for (int e = 0; e < 4; e += 2) {                                                                   \
       const float p0 = __builtin_amdgcn_exp2f(sc[kt][g][e]), p1 = __builtin_amdgcn_exp2f(sc[kt][g][e + 1]);             \
-      ts[g][0] = (kt | e) ? ts[g][0] + p0 : p0;                                                                          \
-      ts[g][1] = (kt | e) ? ts[g][1] + p1 : p1;                                                                          \
-      asm("" : "+v"(ts[g][0]), "+v"(ts[g][1])); /* scalar chains: packed into v_pk_add_f32 they cost more issue time beside the partner's MFMAs */ \
+      if (kt | e) {                                                                                                      \
+        ts[g][0] += p0;                                                                                                  \
+        ts[g][1] += p1;                                                                                                  \
+        asm("" : "+v"(ts[g][0]), "+v"(ts[g][1])); /* scalar chains: packed into v_pk_add_f32 they cost more issue time beside the partner's MFMAs */ \
+      } else { /* chain start: the first P itself; an asm operand here only in the cold copy (see above) */               \
+        ts[g][0] = p0;                                                                                                   \
+        ts[g][1] = p1;                                                                                                   \
+        if (COLD_) asm("" : "+v"(ts[g][0]), "+v"(ts[g][1]));                                                             \
+      }                                                                                                                  \
       pw[kt >> 1][g][2 * (kt & 1) + (e >> 1)] = pack_bf2(p0, p1);                                                        \
     }                                                                                                                    \
     if (kt & 1) A9_SB();                                                                                                 \
@@ -529,7 +540,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
         if (32 * (kt >> 1) + 8 * qd + 4 * (kt & 1) + r >= left) { sc[kt][0][r] = -1e30f; sc[kt][1][r] = -1e30f; }        \
     }                                                                                                                    \
     float ts[2][2];                                                                                                      \
-    A9_EXP_TILE()                                                                                                        \
+    A9_EXP_TILE(false)                                                                                                   \
     if (force || __any(vmax2(ts[0][0] + ts[0][1], ts[1][0] + ts[1][1]) >= A9_GUARD_T)) { /* cold: first tile, or some P may exceed 2^THR */ \
       float mg[2];                                                                                                       \
       _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                    \
@@ -562,7 +573,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
         }                                                                                                                \
         force = false;                                                                                                   \
       }                                                                                                                  \
-      A9_EXP_TILE()                                                                                                      \
+      A9_EXP_TILE(true)                                                                                                  \
     }                                                                                                                    \
     _Pragma("unroll") for (int g = 0; g < 2; ++g) {                                                                      \
       lsum[g][0] += ts[g][0];                                                                                            \
