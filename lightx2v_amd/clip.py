@@ -14,6 +14,7 @@ import math
 import torch
 
 from . import lib, synth
+from .packed import run_plan
 
 HEAD_DIM = 80  # x2v_attn_f16_d80
 
@@ -124,10 +125,7 @@ class CLIPModel:
         return plan
 
     def _run_plan(self, B):
-        for fn, args in self._plan(B, lib._stream()):
-            rc = fn(*args)
-            if rc != 0:
-                lib._check(rc, fn.__name__)
+        run_plan(self._plan(B, lib._stream()))
 
     def preprocess(self, videos):
         """CLIPModel.visual's resize + normalise (model.py:440-442), written as the patch GEMM's operand: → (B, workspace)."""

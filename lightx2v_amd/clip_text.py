@@ -10,15 +10,13 @@ token + position add is torch glue.  fp16 activations and weights, fp32 accumula
 the reference's fp16 model: q is not scaled before the product (the softmax scale is applied to the fp32 scores), scores and probabilities stay fp32 up to
 the PV operand, the quick-GELU is evaluated in fp32 on the fp32 accumulator + bias and rounded once.  cpu_offload is not built.
 """
-from collections import OrderedDict
-
 import torch
 
 from . import lib
 from .llama import load_hf_dir, strip_prefix
+from .packed import MAX_PLANS, PackedTower  # noqa: F401
 
 HEAD_DIM = 64
-MAX_PLANS = 16
 
 
 def eos_position(ids, eos_token_id):
@@ -41,7 +39,7 @@ def dims_from_config(cfg):
                 eos_token_id=int(cfg.get("eos_token_id", 2)))
 
 
-class TextEncoderHFClipModel:
+class TextEncoderHFClipModel(PackedTower):
     """Same constructor, attributes, `infer`, `to_cuda` and `to_cpu` as the reference's TextEncoderHFClipModel; `model_path` may also be a
     (name → tensor dict, dims dict) pair (dims: the keys of synth.CLIP_TEXT_DIMS)."""
 
@@ -91,9 +89,9 @@ class TextEncoderHFClipModel:
                 o=w(a + "out_proj.weight", (D, D)), o_b=w(a + "out_proj.bias", (D,)),
                 fc1=w(p + "mlp.fc1.weight", (F, D)), fc1_b=w(p + "mlp.fc1.bias", (F,)), fc2=w(p + "mlp.fc2.weight", (D, F)), fc2_b=w(p + "mlp.fc2.bias", (D,))))
         self.final_ln = ln("final_layer_norm")
-        self._bufs, self._rows, self._plans, self._tokenizer = {}, 0, OrderedDict(), None
+        self._init_plumbing()
 
-    # ---- plumbing ------------------------------------------------------------------------------------------------------
+    # ---- plumbing (packed.PackedTower: one workspace, the plan cache) --------------------------------------------------
     def weight_bytes(self):
         """Bytes of Linear weights one forward streams (the launch floor of the tower)."""
         return sum(b[k].numel() * 2 for b in self.blocks for k in ("qkv", "o", "fc1", "fc2"))
@@ -101,32 +99,12 @@ class TextEncoderHFClipModel:
     def launches(self):
         return 7 * self.num_layers + 1
 
-    def _workspace(self, M):
-        if M > self._rows:
+    def _buffers(self):
+        return dict(x=self.dim, h=self.dim, qkv=3 * self.dim, att=self.dim, f=self.dim_ffn, pooled=(self.dim, 1))
 
-            def buf(c, rows=M):
-                return torch.empty((rows, c), dtype=torch.float16, device=self.device)
-
-            self._plans.clear()
-            self._bufs = dict(x=buf(self.dim), h=buf(self.dim), qkv=buf(3 * self.dim), att=buf(self.dim), f=buf(self.dim_ffn), pooled=buf(self.dim, 1))
-            self._rows = M
-        return {k: (v if k == "pooled" else v[:M]) for k, v in self._bufs.items()}
-
-    def _plan(self, lens, stream):
-        """The tower as a list of (C entry, raw arguments) per (lengths, stream); the final norm reads the last row of the single sequence."""
-        key = (lens, stream)
-        plan = self._plans.get(key)
-        if plan is not None:
-            self._plans.move_to_end(key)
-            return plan
-        L, M = lib._lib, sum(lens)
-        ws = self._workspace(M)
-        D, F, eps = self.dim, self.dim_ffn, self.norm_eps
-        p = {k: v.data_ptr() for k, v in ws.items()}
-        cu = [0]
-        for n in lens:
-            cu.append(cu[-1] + n)
-        cu_arr = (lib._i32 * len(cu))(*cu)
+    def _launches(self, p, M, cu_arr, batch, stream):
+        """The final norm reads the last row of the single sequence."""
+        L, D, F, eps = lib._lib, self.dim, self.dim_ffn, self.norm_eps
         plan = []
 
         def norm(wb):
@@ -138,23 +116,17 @@ class TextEncoderHFClipModel:
         for b in self.blocks:
             norm(b["ln1"])
             gemm("h", b["qkv"], b["qkv_b"], "qkv", 3 * D, D, lib.EPI16_NONE)
-            plan.append((L.x2v_attn_f16_causal, (p["qkv"], 3 * D, p["att"], D, cu_arr, len(lens), self.num_heads, self.num_heads, HEAD_DIM, None, None, 0.0, stream)))
+            plan.append((L.x2v_attn_f16_causal, (p["qkv"], 3 * D, p["att"], D, cu_arr, batch, self.num_heads, self.num_heads, HEAD_DIM, None, None, 0.0, stream)))
             gemm("att", b["o"], b["o_b"], "x", D, D, lib.EPI16_RESIDUAL, "x")
             norm(b["ln2"])
             gemm("h", b["fc1"], b["fc1_b"], "f", F, D, lib.EPI16_QUICK_GELU)
             gemm("f", b["fc2"], b["fc2_b"], "x", D, F, lib.EPI16_RESIDUAL, "x")
         plan.append((L.x2v_layernorm_f16, (p["x"] + (M - 1) * D * 2, D, self.final_ln[0].data_ptr(), self.final_ln[1].data_ptr(), p["pooled"], D, 1, D, eps, stream)))
-        self._plans[key] = plan
-        while len(self._plans) > MAX_PLANS:
-            self._plans.popitem(last=False)
         return plan
 
     def forward_packed(self, lens):
         """Layers + the final norm of the last row on the workspace (`x` holds token + position embeddings of one sequence): → pooled [1, dim] (the workspace)."""
-        for fn, args in self._plan(tuple(lens), lib._stream()):
-            rc = fn(*args)
-            if rc != 0:
-                lib._check(rc, fn.__name__)
+        self._run_packed(lens)
         return self._bufs["pooled"]
 
     # ---- the reference's interface -------------------------------------------------------------------------------------

@@ -4,10 +4,9 @@
 //
 // gemm_rows_kernel<_Float16> (gemm_rows.h, shared with the bf16 text encoder) — y[M,N] = epi(x[M,K] . W[N,K]^T + b), the weight-streaming small-M GEMM.
 // attn_f16_d80_kernel — non-causal attention, head dim 80, <= 272 keys, q/k/v read in place from the QKV GEMM's output rows.  Workgroup = (64 query rows, one
-//   head of one image); the head's K [272][80] and V^T [80][288] live in LDS (93 KiB), zero-filled beyond the last key.  S^T = K . Q^T (three k-steps over d:
-//   32 + 32 + 16, the last half zero in both operands) leaves a query's 272 scores in 17 accumulator tiles of the 4 lanes that share its column: the softmax
-//   is done in registers (fp32), keys >= S masked to -inf.  O^T = V^T . P^T takes those accumulators as the B operand without lane movement: k-step kk joins
-//   key tiles 2kk and 2kk + 1, element j of lane group g being key 32kk + 4g + j (j < 4) or 32kk + 16 + 4g + j - 4, and the V^T fragment reads the same keys.
+//   head of one image); the head's K [272][80] and V^T [80][288] live in LDS (93 KiB).  Built from enc_attn.h's steps (the staging, lane and fragment
+//   convention is described there): three k-steps over d, 32 + 32 + 16, the last half zero in both operands; a query's 272 scores sit in 17 accumulator
+//   tiles, the softmax is done in registers (fp32), keys >= S masked to -inf; an 18th all-zero tile fills the second half of the 9th PV k-step.
 // ln_f16_kernel — LayerNorm of an fp16 row in registers: fp32 two-pass statistics, fp32 affine, one rounding.  EMBED: the row is built first as
 //   fp16(cls | patch token + pos_embedding) (VisionTransformer.forward :278-287).
 // clip_preprocess_kernel — bicubic resample (A = -0.75, align_corners=False, border-clamped taps: F.interpolate(mode="bicubic")), (x * 0.5 + 0.5 - mean) / std,
@@ -16,6 +15,7 @@
 
 #include <algorithm>
 
+#include "enc_attn.h"
 #include "gemm_rows.h"
 #include "x2v_common.h"
 
@@ -35,57 +35,37 @@ __global__ __launch_bounds__(256) void attn_f16_d80_kernel(const _Float16* __res
   extern __shared__ __attribute__((aligned(16))) char smem[];
   _Float16* Ks = reinterpret_cast<_Float16*>(smem);
   _Float16* Vt = Ks + AT_KROWS * AT_KP;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int c16 = lane & 15, g4 = lane >> 4;
+  const EncLanes L = enc_lanes();
   const int b = blockIdx.y / H, h = blockIdx.y % H;
   const int64_t D = (int64_t)H * AT_D;
   const _Float16* base = qkv + (int64_t)b * S * ld + h * AT_D;
 
-  for (int i = tid; i < AT_KROWS * (AT_D / 8); i += 256) {
-    const int key = i / (AT_D / 8), ch = i % (AT_D / 8);
-    half8_t v = {};
-    if (key < S) v = *reinterpret_cast<const half8_t*>(base + (int64_t)key * ld + D + ch * 8);
-    *reinterpret_cast<half8_t*>(Ks + key * AT_KP + ch * 8) = v;
-  }
-  for (int i = tid; i < AT_VKEYS * (AT_D / 8); i += 256) {
-    const int ch = i / AT_VKEYS, key = i % AT_VKEYS;  // consecutive lanes: consecutive keys of one V^T row group
-    half8_t v = {};
-    if (key < S) v = *reinterpret_cast<const half8_t*>(base + (int64_t)key * ld + 2 * D + ch * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * AT_VP + key] = v[e];
-  }
+  stage_k<_Float16, AT_D, AT_KROWS, AT_KP>(Ks, base + D, ld, 0, S, L.tid);
+  stage_vt<_Float16, AT_D, AT_VKEYS, AT_VP>(Vt, base + 2 * D, ld, 0, S, L.tid);
 
-  const int q = blockIdx.x * 64 + wid * 16 + c16;
-  const _Float16* qp = base + (int64_t)min(q, S - 1) * ld + g4 * 8;
+  const int q = enc_query(L, blockIdx.x);
+  const _Float16* qp = base + (int64_t)enc_read_row(q, S) * ld;
   half8_t qf[3];
-  qf[0] = *reinterpret_cast<const half8_t*>(qp);
-  qf[1] = *reinterpret_cast<const half8_t*>(qp + 32);
+  load_q<_Float16, 2>(qp, L.g4, qf);
   qf[2] = half8_t{};
-  if (g4 < 2) qf[2] = *reinterpret_cast<const half8_t*>(qp + 64);
+  if (L.g4 < 2) qf[2] = *reinterpret_cast<const half8_t*>(qp + 64 + 8 * L.g4);
   __syncthreads();
 
-  // scores: sc[t][e] = q . k[16 t + 4 g4 + e]
+  // scores: sc[t][e] = q . k[16 t + 4 g4 + e]   (three k-steps over d: 32 + 32 + 16)
   f32x4_t sc[AT_TILES + 1];
   float mx = -INFINITY;
 #pragma unroll
   for (int t = 0; t < AT_TILES; ++t) {
-    const _Float16* kr = Ks + (16 * t + c16) * AT_KP + g4 * 8;
-    f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const half8_t*>(kr), qf[0], a, 0, 0, 0);
-    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const half8_t*>(kr + 32), qf[1], a, 0, 0, 0);
-    half8_t k2 = {};
-    if (g4 < 2) k2 = *reinterpret_cast<const half8_t*>(kr + 64);
-    a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k2, qf[2], a, 0, 0, 0);
+    f32x4_t a = score_tile<_Float16, 2, AT_KP, true>(Ks, t, L, qf);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      if (16 * t + 4 * g4 + e >= S) a[e] = -INFINITY;
+      if (16 * t + 4 * L.g4 + e >= S) a[e] = -INFINITY;
       mx = fmaxf(mx, a[e]);
     }
     sc[t] = a;
   }
   sc[AT_TILES] = f32x4_t{0.f, 0.f, 0.f, 0.f};  // the second half of the last k-step: no keys
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: key 0 is never masked
+  mx = quad_max(mx);                          // finite: key 0 is never masked
   float sum = 0.f;
 #pragma unroll
   for (int t = 0; t < AT_TILES; ++t)
@@ -95,38 +75,15 @@ __global__ __launch_bounds__(256) void attn_f16_d80_kernel(const _Float16* __res
       sc[t][e] = p;
       sum += p;
     }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
+  sum = quad_sum(sum);
 
   f32x4_t o[AT_D / 16];
 #pragma unroll
   for (int c = 0; c < AT_D / 16; ++c) o[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int kk = 0; kk < AT_VKEYS / 32; ++kk) {
-    half8_t pb;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      pb[e] = (_Float16)sc[2 * kk][e];
-      pb[4 + e] = (_Float16)sc[2 * kk + 1][e];
-    }
-#pragma unroll
-    for (int c = 0; c < AT_D / 16; ++c) {
-      const _Float16* vr = Vt + (16 * c + c16) * AT_VP + 32 * kk + 4 * g4;
-      const half4_t lo = *reinterpret_cast<const half4_t*>(vr), hi = *reinterpret_cast<const half4_t*>(vr + 16);
-      const half8_t vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      o[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb, o[c], 0, 0, 0);
-    }
-  }
+  for (int kk = 0; kk < AT_VKEYS / 32; ++kk) pv_step<_Float16, AT_D / 16, AT_VP>(Vt, kk, sc[2 * kk], sc[2 * kk + 1], L, o);
   if (q >= S) return;
-  const float inv = 1.0f / sum;
-  _Float16* op = out + ((int64_t)b * S + q) * ldo + h * AT_D + 4 * g4;
-#pragma unroll
-  for (int c = 0; c < AT_D / 16; ++c) {
-    half4_t r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (_Float16)(o[c][e] * inv);
-    *reinterpret_cast<half4_t*>(op + 16 * c) = r;
-  }
+  store_out<_Float16, AT_D / 16>(out + ((int64_t)b * S + q) * ldo + h * AT_D, o, 1.0f / sum, L.g4);
 }
 
 // ---- LayerNorm (and the token assembly in front of pre_norm) ------------------------------------------------------------------------------------------

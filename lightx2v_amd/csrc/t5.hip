@@ -6,34 +6,24 @@
 //   residual and the GEGLU epilogue (fc1 and gate.0 interleaved row by row in one weight matrix).
 // attn_d64_relbias_kernel — non-causal attention, head dim 64, with T5's additive relative-position bias, over packed sequences of 1..512 tokens; q | k | v
 //   read in place from the fused QKV GEMM's output rows.  Workgroup = (64 query rows, one head of one sequence).  The sequence bounds arrive by value
-//   (a kernel argument: no device copy, no sync).  The head's K [KR][64] and V^T [64][KR] live in LDS, zero-filled beyond the sequence's last key, next to
-//   the head's bias row [1023] in fp32; KR is the sequence's OWN length rounded up to 64 / 128 / 256 / 512 keys (the body is instantiated per size and
-//   chosen per workgroup), so a 77-token prompt packed with a 300-token one walks 128 keys.  At 512 keys: 4 KB + 72 KB + 65 KB = 141 KB of the CU's 160.
-//   S^T = K . Q^T (two k-steps over d) leaves a query's scores in the accumulator tiles of the 4 lanes that share its column: score * scale + bias, the
-//   row maximum, exp and the sum are fp32 in registers, keys >= length masked to -inf (probability exactly 0: rows of other sequences are never read).
-//   O^T = V^T . P^T takes those accumulators, rounded to bf16, as the B operand without lane movement: k-step kk joins key tiles 2kk and 2kk + 1, element j of
-//   lane group g being key 32kk + 4g + j (j < 4) or 32kk + 16 + 4g + j - 4, and the V^T fragment reads the same keys.  fp32 accumulation, the 1 / sum applied
-//   in fp32, one rounding of the output.
+//   (a kernel argument: no device copy, no sync).  The head's K [KR][64] and V^T [64][KR] live in LDS next to the head's bias row [1023] in fp32; KR is
+//   the sequence's OWN length rounded up to 64 / 128 / 256 / 512 keys (the body is instantiated per size and chosen per workgroup), so a 77-token prompt
+//   packed with a 300-token one walks 128 keys.  At 512 keys: 4 KB + 72 KB + 65 KB = 141 KB of the CU's 160.  Built from enc_attn.h's steps (the staging,
+//   lane and fragment convention is described there): score * scale + bias, the row maximum, exp and the sum are fp32 in registers, keys >= length masked
+//   to -inf (probability exactly 0).
 #include <math.h>
 
-#include <algorithm>
-
+#include "enc_attn.h"
 #include "gemm_rows.h"
 #include "x2v_common.h"
 
 namespace x2v {
 
 constexpr int TA_D = 64;
-constexpr int TA_MAXLEN = 512;
-constexpr int TA_MAXBATCH = 8;
-constexpr int TA_NBIAS = 2 * TA_MAXLEN - 1;  // deltas -511 .. 511
-constexpr int TA_BIAS_BYTES = 4096;          // the bias row's slot at the start of LDS
-constexpr int TA_KP = 72;                    // K row pitch in elements (144 B: 16-byte aligned rows, 8 pad elements never read)
-constexpr int TA_VPAD = 8;                   // V^T row pitch = KR + 8
-
-struct T5Seqs {
-  int cu[TA_MAXBATCH + 1];
-};
+constexpr int TA_NBIAS = 2 * ENC_MAXLEN - 1;  // deltas -511 .. 511
+constexpr int TA_BIAS_BYTES = 4096;           // the bias row's slot at the start of LDS
+constexpr int TA_KP = TA_D + 8;               // K row pitch in elements
+constexpr int TA_VPAD = 8;                    // V^T row pitch = KR + 8
 
 constexpr int ta_lds_bytes(int kr) { return TA_BIAS_BYTES + (kr * TA_KP + TA_D * (kr + TA_VPAD)) * 2; }
 static inline int ta_key_rows(int len) { return len <= 64 ? 64 : len <= 128 ? 128 : len <= 256 ? 256 : 512; }
@@ -46,50 +36,34 @@ __device__ __forceinline__ void attn_d64_body(char* smem, const __bf16* __restri
   float* Bs = reinterpret_cast<float*>(smem);
   __bf16* Ks = reinterpret_cast<__bf16*>(smem + TA_BIAS_BYTES);
   __bf16* Vt = Ks + KR * TA_KP;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int c16 = lane & 15, g4 = lane >> 4;
+  const EncLanes L = enc_lanes();
 
-  for (int i = tid; i < TA_NBIAS; i += 256) Bs[i] = bias_h[i];
-  for (int i = tid; i < KR * (TA_D / 8); i += 256) {
-    const int key = i / (TA_D / 8), ch = i % (TA_D / 8);
-    bf16x8_t v = {};
-    if (key < len) v = *reinterpret_cast<const bf16x8_t*>(base + (int64_t)key * ld + D + ch * 8);
-    *reinterpret_cast<bf16x8_t*>(Ks + key * TA_KP + ch * 8) = v;
-  }
-  for (int i = tid; i < KR * (TA_D / 8); i += 256) {
-    const int ch = i / KR, key = i % KR;  // consecutive lanes: consecutive keys of one V^T row group
-    bf16x8_t v = {};
-    if (key < len) v = *reinterpret_cast<const bf16x8_t*>(base + (int64_t)key * ld + 2 * D + ch * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * VP + key] = v[e];
-  }
+  for (int i = L.tid; i < TA_NBIAS; i += 256) Bs[i] = bias_h[i];
+  stage_k<__bf16, TA_D, KR, TA_KP>(Ks, base + D, ld, 0, len, L.tid);
+  stage_vt<__bf16, TA_D, KR, VP>(Vt, base + 2 * D, ld, 0, len, L.tid);
 
-  const int q = qb * 64 + wid * 16 + c16;
-  const __bf16* qp = base + (int64_t)min(q, len - 1) * ld + g4 * 8;
-  const bf16x8_t qf0 = *reinterpret_cast<const bf16x8_t*>(qp), qf1 = *reinterpret_cast<const bf16x8_t*>(qp + 32);
+  const int q = enc_query(L, qb);
+  bf16x8_t qf[2];
+  load_q<__bf16, 2>(base + (int64_t)enc_read_row(q, len) * ld, L.g4, qf);
   __syncthreads();
-  if (qb * 64 + wid * 16 >= len) return;  // no barrier below: a wave without queries leaves
+  if (qb * 64 + L.wid * 16 >= len) return;  // no barrier below: a wave without queries leaves
 
   // scores: sc[t][e] = scale * q . k[16 t + 4 g4 + e] + bias[key - q + 511]   (q <= 511, key <= 511: the index stays inside the row)
   f32x4_t sc[NT];
   float mx = -INFINITY;
-  const float* bq = Bs + (TA_MAXLEN - 1) - q + 4 * g4;
+  const float* bq = Bs + (ENC_MAXLEN - 1) - q + 4 * L.g4;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    const __bf16* kr = Ks + (16 * t + c16) * TA_KP + g4 * 8;
-    f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(kr), qf0, a, 0, 0, 0);
-    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(kr + 32), qf1, a, 0, 0, 0);
+    f32x4_t a = score_tile<__bf16, TA_D / 32, TA_KP>(Ks, t, L, qf);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       a[e] = a[e] * scale + bq[16 * t + e];
-      if (16 * t + 4 * g4 + e >= len) a[e] = -INFINITY;
+      if (16 * t + 4 * L.g4 + e >= len) a[e] = -INFINITY;
       mx = fmaxf(mx, a[e]);
     }
     sc[t] = a;
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: key 0 is never masked
+  mx = quad_max(mx);  // finite: key 0 is never masked
   float sum = 0.f;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -99,42 +73,19 @@ __device__ __forceinline__ void attn_d64_body(char* smem, const __bf16* __restri
       sc[t][e] = p;
       sum += p;
     }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
+  sum = quad_sum(sum);
 
   f32x4_t o[TA_D / 16];
 #pragma unroll
   for (int c = 0; c < TA_D / 16; ++c) o[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int kk = 0; kk < NT / 2; ++kk) {
-    bf16x8_t pb;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      pb[e] = (__bf16)sc[2 * kk][e];
-      pb[4 + e] = (__bf16)sc[2 * kk + 1][e];
-    }
-#pragma unroll
-    for (int c = 0; c < TA_D / 16; ++c) {
-      const __bf16* vr = Vt + (16 * c + c16) * VP + 32 * kk + 4 * g4;
-      const bf16x4_t lo = *reinterpret_cast<const bf16x4_t*>(vr), hi = *reinterpret_cast<const bf16x4_t*>(vr + 16);
-      const bf16x8_t vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb, o[c], 0, 0, 0);
-    }
-  }
+  for (int kk = 0; kk < NT / 2; ++kk) pv_step<__bf16, TA_D / 16, VP>(Vt, kk, sc[2 * kk], sc[2 * kk + 1], L, o);
   if (q >= len) return;
-  const float inv = 1.0f / sum;
-  __bf16* op = out_rows + (int64_t)q * ldo + 4 * g4;
-#pragma unroll
-  for (int c = 0; c < TA_D / 16; ++c) {
-    bf16x4_t r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (__bf16)(o[c][e] * inv);
-    *reinterpret_cast<bf16x4_t*>(op + 16 * c) = r;
-  }
+  store_out<__bf16, TA_D / 16>(out_rows + (int64_t)q * ldo, o, 1.0f / sum, L.g4);
 }
 
 __global__ __launch_bounds__(256) void attn_d64_relbias_kernel(const __bf16* __restrict__ qkv, int64_t ld, const float* __restrict__ bias, __bf16* __restrict__ out, int64_t ldo,
-                                                               T5Seqs seqs, int H, float scale) {
+                                                               PackedSeqs seqs, int H, float scale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.y / H, h = blockIdx.y % H, qb = blockIdx.x;
   const int row0 = seqs.cu[b], len = seqs.cu[b + 1] - row0;
@@ -180,24 +131,17 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_rows_bf16(const v
 extern "C" __attribute__((visibility("default"))) int x2v_attn_bf16_d64_relbias(const void* qkv, int64_t ld, const float* bias, void* out, int64_t ldo, const int* cu_seqlens,
                                                                                 int batch, int num_heads, float scale, void* stream) {
   X2V_REQUIRE(qkv && bias && out && cu_seqlens, X2V_E_ARG, "attn_bf16_d64_relbias: null pointer");
-  X2V_REQUIRE(batch >= 1 && batch <= TA_MAXBATCH, X2V_E_SHAPE, "attn_bf16_d64_relbias: batch=%d must be 1..%d packed sequences", batch, TA_MAXBATCH);
+  PackedSeqs seqs;
+  int longest;
+  int rc = packed_seqs_check("attn_bf16_d64_relbias", cu_seqlens, batch, ENC_MAXLEN, "keys this kernel holds in LDS", &seqs, &longest);
+  if (rc != X2V_OK) return rc;
   X2V_REQUIRE(num_heads > 0 && (int64_t)batch * num_heads < 65536, X2V_E_SHAPE, "attn_bf16_d64_relbias: bad head count %d", num_heads);
   X2V_REQUIRE(scale == scale && fabsf(scale) <= 3.0e38f, X2V_E_ARG, "attn_bf16_d64_relbias: scale must be finite (T5 passes 1)");
-  T5Seqs seqs{};
-  int longest = 0;
-  X2V_REQUIRE(cu_seqlens[0] >= 0, X2V_E_SHAPE, "attn_bf16_d64_relbias: cu_seqlens[0]=%d is negative", cu_seqlens[0]);
-  for (int b = 0; b <= batch; ++b) seqs.cu[b] = cu_seqlens[b];
-  for (int b = 0; b < batch; ++b) {
-    const int64_t len = (int64_t)seqs.cu[b + 1] - seqs.cu[b];
-    X2V_REQUIRE(len >= 1, X2V_E_SHAPE, "attn_bf16_d64_relbias: cu_seqlens must increase (sequence %d has %lld tokens)", b, (long long)len);
-    X2V_REQUIRE(len <= TA_MAXLEN, X2V_E_SHAPE, "attn_bf16_d64_relbias: sequence %d has %lld tokens, more than the %d keys this kernel holds in LDS", b, (long long)len, TA_MAXLEN);
-    longest = std::max(longest, (int)len);
-  }
   X2V_REQUIRE(ld >= 3ll * num_heads * TA_D && ldo >= (int64_t)num_heads * TA_D && ld % 8 == 0 && ldo % 4 == 0, X2V_E_ALIGN,
               "attn_bf16_d64_relbias: ld must cover [q | k | v] of %d heads x 64 (a multiple of 8 elements), ldo the output row (of 4)", num_heads);
   X2V_REQUIRE(aligned16(qkv) && aligned16(out) && ((uintptr_t)bias & 3) == 0, X2V_E_ALIGN, "attn_bf16_d64_relbias: qkv / out must be 16-byte aligned, bias 4-byte");
   const int lds = ta_lds_bytes(ta_key_rows(longest));
-  int rc = ensure_dynamic_lds((const void*)attn_d64_relbias_kernel, ta_lds_bytes(TA_MAXLEN), "attn_bf16_d64_relbias attr");
+  rc = ensure_dynamic_lds((const void*)attn_d64_relbias_kernel, ta_lds_bytes(ENC_MAXLEN), "attn_bf16_d64_relbias attr");
   if (rc != X2V_OK) return rc;
   hipLaunchKernelGGL(attn_d64_relbias_kernel, dim3((unsigned)((longest + 63) / 64), (unsigned)(batch * num_heads)), dim3(256), lds, (hipStream_t)stream, (const __bf16*)qkv, ld,
                      bias, (__bf16*)out, ldo, seqs, num_heads, scale);

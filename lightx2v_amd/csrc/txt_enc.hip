@@ -6,41 +6,32 @@
 // attn_f16_causal_kernel<D> — causal attention, head dim 64 or 128, grouped-query (query head h reads key/value head h / (H / Hkv)), over packed sequences
 //   of 1..512 tokens; q | k | v read in place from the fused QKV GEMM's output rows.  Workgroup = (64 query rows, one query head of one sequence); the
 //   sequence bounds arrive by value.  It walks the 64-key tiles 0 .. its own diagonal tile: K [64][D] and V^T [D][64] of one tile live in LDS (35 KiB at
-//   D = 128), zero-filled beyond the sequence's last key, so rows of other sequences are never read.  With rope tables given (D = 128), q (in registers) and
-//   k (while it is staged) are rotated in fp32, rotate-half at position = index within the sequence, and rounded once to fp16.  S^T = K . Q^T leaves a
-//   query's 64 scores of the tile in the accumulators of the 4 lanes that share its column: the running maximum, exp and sum are fp32 in registers (online
-//   softmax), the diagonal tile masks key > query to -inf (probability exactly 0).  O^T = V^T . P^T takes those accumulators, rounded to fp16, as the B
-//   operand without lane movement (the key order of attn_f16_d80_kernel's k-steps); fp32 accumulation, 1 / sum applied in fp32, one rounding of the output.
+//   D = 128).  Built from enc_attn.h's steps (the staging, lane and fragment convention is described there).  With rope tables given (D = 128), q (in
+//   registers) and k (while it is staged, in a loop of its own over half rows) are rotated in fp32, rotate-half at position = index within the sequence,
+//   and rounded once to fp16.  The running maximum, exp and sum of a query's row are fp32 in registers (online softmax), the diagonal tile masks
+//   key > query to -inf (probability exactly 0).
 // rmsnorm_f16_kernel — RMSNorm of an fp16 row with an fp16 weight: rowwise.h's statistic and normalise steps (X2V_ROUND_FP32), one rounding.
 #include <math.h>
 
-#include <algorithm>
-
-#include "gemm_rows.h"
+#include "enc_attn.h"
 #include "rowwise.h"
 #include "x2v_common.h"
 
 namespace x2v {
 
-constexpr int CA_MAXLEN = 512;
-constexpr int CA_MAXBATCH = 8;
 constexpr int CA_TILE = 64;           // keys per tile = query rows per workgroup
 constexpr int CA_VP = CA_TILE + 8;    // V^T row pitch in halves (144 B: 8-byte aligned fragments)
 
-struct CausalSeqs {
-  int cu[CA_MAXBATCH + 1];
-};
-
 template <int D>
-__global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __restrict__ qkv, int64_t ld, _Float16* __restrict__ out, int64_t ldo, CausalSeqs seqs, int H,
+__global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __restrict__ qkv, int64_t ld, _Float16* __restrict__ out, int64_t ldo, PackedSeqs seqs, int H,
                                                               int Hkv, const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, float scale_log2e) {
-  constexpr int KP = D + 8;     // K row pitch in halves (16-byte aligned rows, 8 pad halves never read)
+  constexpr int KP = D + 8;     // K row pitch in halves
   constexpr int KS = D / 32;    // k-steps of S^T = K . Q^T
   constexpr int HD = D / 2;     // the rotation's partner distance = the tables' row length
   __shared__ __attribute__((aligned(16))) _Float16 Ks[CA_TILE * KP];
   __shared__ __attribute__((aligned(16))) _Float16 Vt[D * CA_VP];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int c16 = lane & 15, g4 = lane >> 4;
+  const EncLanes L = enc_lanes();
+  const int tid = L.tid, g4 = L.g4;
   const int b = blockIdx.y / H, h = blockIdx.y % H, qb = blockIdx.x;
   const int row0 = seqs.cu[b], len = seqs.cu[b + 1] - row0;
   if (qb * CA_TILE >= len) return;  // the whole workgroup: the grid is sized for the longest sequence
@@ -50,13 +41,11 @@ __global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __
   const _Float16* vbase = kbase + (int64_t)Hkv * D;
   const bool rope = rope_cos != nullptr;
 
-  // this lane's query (column c16 of the wave's 16), k elements 32 ks + 8 g4 .. + 7 of each k-step; rows beyond the sequence read its last row (never stored)
-  const int q = qb * CA_TILE + wid * 16 + c16;
-  const int qr = min(q, len - 1);
-  const bool active = qb * CA_TILE + wid * 16 < len;  // a wave without queries only helps staging
+  const int q = enc_query(L, qb);
+  const int qr = enc_read_row(q, len);
+  const bool active = qb * CA_TILE + L.wid * 16 < len;  // a wave without queries only helps staging
   half8_t qf[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(qbase + (int64_t)qr * ld + 32 * ks + 8 * g4);
+  load_q<_Float16, KS>(qbase + (int64_t)qr * ld, g4, qf);
   if constexpr (D == 128) {
     if (rope) {  // out[i] = t[i] cos[i] - t[i + 64] sin[i] (i < 64), out[i + 64] = t[i + 64] cos[i] + t[i] sin[i]
 #pragma unroll
@@ -102,20 +91,9 @@ __global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __
         *reinterpret_cast<half8_t*>(Ks + key * KP + HD + ch * 8) = hi;
       }
     } else {
-      for (int i = tid; i < CA_TILE * (D / 8); i += 256) {
-        const int key = i / (D / 8), ch = i % (D / 8);
-        half8_t v = {};
-        if (k0 + key < len) v = *reinterpret_cast<const half8_t*>(kbase + (int64_t)(k0 + key) * ld + ch * 8);
-        *reinterpret_cast<half8_t*>(Ks + key * KP + ch * 8) = v;
-      }
+      stage_k<_Float16, D, CA_TILE, KP>(Ks, kbase, ld, k0, len, tid);
     }
-    for (int i = tid; i < CA_TILE * (D / 8); i += 256) {
-      const int ch = i / CA_TILE, key = i % CA_TILE;  // consecutive lanes: consecutive keys of one V^T row group
-      half8_t v = {};
-      if (k0 + key < len) v = *reinterpret_cast<const half8_t*>(vbase + (int64_t)(k0 + key) * ld + ch * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * CA_VP + key] = v[e];
-    }
+    stage_vt<_Float16, D, CA_TILE, CA_VP>(Vt, vbase, ld, k0, len, tid);
     __syncthreads();
     if (!active) continue;
 
@@ -124,10 +102,7 @@ __global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __
     float tmx = -INFINITY;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const _Float16* kr = Ks + (16 * t + c16) * KP + g4 * 8;
-      f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const half8_t*>(kr + 32 * ks), qf[ks], a, 0, 0, 0);
+      f32x4_t a = score_tile<_Float16, KS, KP>(Ks, t, L, qf);
       if (kt == qb) {  // the diagonal tile: keys behind the query (and with them every key beyond the sequence) are masked
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -137,8 +112,7 @@ __global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __
       for (int e = 0; e < 4; ++e) tmx = fmaxf(tmx, a[e]);
       sc[t] = a;
     }
-    tmx = fmaxf(tmx, __shfl_xor(tmx, 16, 64));
-    tmx = fmaxf(tmx, __shfl_xor(tmx, 32, 64));  // finite: the tile's first key is never behind a query of this block
+    tmx = quad_max(tmx);  // finite: the tile's first key is never behind a query of this block
     const float mnew = fmaxf(mx, tmx);
     const float alpha = __builtin_amdgcn_exp2f((mx - mnew) * scale_log2e);  // 0 at the first tile (mx = -inf)
     mx = mnew;
@@ -156,34 +130,11 @@ __global__ __launch_bounds__(256) void attn_f16_causal_kernel(const _Float16* __
         sum += p;
       }
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      half8_t pb;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pb[e] = (_Float16)sc[2 * kk][e];
-        pb[4 + e] = (_Float16)sc[2 * kk + 1][e];
-      }
-#pragma unroll
-      for (int c = 0; c < D / 16; ++c) {
-        const _Float16* vr = Vt + (16 * c + c16) * CA_VP + 32 * kk + 4 * g4;
-        const half4_t lo = *reinterpret_cast<const half4_t*>(vr), hi = *reinterpret_cast<const half4_t*>(vr + 16);
-        const half8_t vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        o[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb, o[c], 0, 0, 0);
-      }
-    }
+    for (int kk = 0; kk < 2; ++kk) pv_step<_Float16, D / 16, CA_VP>(Vt, kk, sc[2 * kk], sc[2 * kk + 1], L, o);
   }
   if (q >= len) return;
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-  _Float16* op = out + (int64_t)(row0 + q) * ldo + h * D + 4 * g4;
-#pragma unroll
-  for (int c = 0; c < D / 16; ++c) {
-    half4_t r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (_Float16)(o[c][e] * inv);
-    *reinterpret_cast<half4_t*>(op + 16 * c) = r;
-  }
+  sum = quad_sum(sum);
+  store_out<_Float16, D / 16>(out + (int64_t)(row0 + q) * ldo + h * D, o, 1.0f / sum, g4);
 }
 
 // ---- RMSNorm ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -239,21 +190,13 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_f16_causal(const 
   X2V_REQUIRE(head_dim == 64 || head_dim == 128, X2V_E_SHAPE, "attn_f16_causal: head_dim=%d must be 64 or 128", head_dim);
   X2V_REQUIRE((rope_cos == nullptr) == (rope_sin == nullptr), X2V_E_ARG, "attn_f16_causal: rope_cos and rope_sin must be given together");
   X2V_REQUIRE(rope_cos == nullptr || head_dim == 128, X2V_E_ARG, "attn_f16_causal: the rotary tables go with head_dim 128 only (got %d)", head_dim);
-  X2V_REQUIRE(batch >= 1 && batch <= CA_MAXBATCH, X2V_E_SHAPE, "attn_f16_causal: batch=%d must be 1..%d packed sequences", batch, CA_MAXBATCH);
+  PackedSeqs seqs;
+  int longest;
+  int rc = packed_seqs_check("attn_f16_causal", cu_seqlens, batch, ENC_MAXLEN, "this kernel (and its rotary tables) takes", &seqs, &longest);
+  if (rc != X2V_OK) return rc;
   X2V_REQUIRE(num_heads > 0 && num_kv_heads > 0 && num_heads % num_kv_heads == 0 && (int64_t)batch * num_heads < 65536, X2V_E_SHAPE,
               "attn_f16_causal: bad head counts %d / %d (query heads must be a multiple of key/value heads)", num_heads, num_kv_heads);
   X2V_REQUIRE(scale == scale && scale >= 0.f && scale <= 3.0e38f, X2V_E_ARG, "attn_f16_causal: scale must be finite and >= 0 (0 = head_dim^-1/2)");
-  CausalSeqs seqs{};
-  int longest = 0;
-  X2V_REQUIRE(cu_seqlens[0] >= 0, X2V_E_SHAPE, "attn_f16_causal: cu_seqlens[0]=%d is negative", cu_seqlens[0]);
-  for (int b = 0; b <= batch; ++b) seqs.cu[b] = cu_seqlens[b];
-  for (int b = 0; b < batch; ++b) {
-    const int64_t len = (int64_t)seqs.cu[b + 1] - seqs.cu[b];
-    X2V_REQUIRE(len >= 1, X2V_E_SHAPE, "attn_f16_causal: cu_seqlens must increase (sequence %d has %lld tokens)", b, (long long)len);
-    X2V_REQUIRE(len <= CA_MAXLEN, X2V_E_SHAPE, "attn_f16_causal: sequence %d has %lld tokens, more than the %d this kernel (and its rotary tables) takes", b, (long long)len,
-                CA_MAXLEN);
-    longest = std::max(longest, (int)len);
-  }
   const int64_t cols = ((int64_t)num_heads + 2 * num_kv_heads) * head_dim;
   X2V_REQUIRE(ld >= cols && ldo >= (int64_t)num_heads * head_dim && ld % 8 == 0 && ldo % 4 == 0, X2V_E_ALIGN,
               "attn_f16_causal: ld must cover [q | k | v] of %d + 2 x %d heads x %d (a multiple of 8 halves), ldo the output row (of 4)", num_heads, num_kv_heads, head_dim);

@@ -18,14 +18,13 @@ cpu_offload are not built.
 """
 import json
 import os
-from collections import OrderedDict
 
 import torch
 
 from . import lib
+from .packed import MAX_PLANS, PackedTower  # noqa: F401
 
 HEAD_DIM = 128  # the rotary form of x2v_attn_f16_causal
-MAX_PLANS = 16
 MAX_LEN = lib.ATTN_CAUSAL_MAX_LEN
 
 
@@ -87,7 +86,7 @@ def dims_from_config(cfg):
                 rope_theta=float(rope.get("rope_theta", cfg.get("rope_theta", 10000.0))), eps=float(cfg.get("rms_norm_eps", 1e-6)))
 
 
-class TextEncoderHFLlamaModel:
+class TextEncoderHFLlamaModel(PackedTower):
     """Same constructor, attributes, `infer`, `to_cuda` and `to_cpu` as the reference's TextEncoderHFLlamaModel; `model_path` may also be a
     (name → tensor dict, dims dict) pair (dims: the keys of synth.LLAMA_DIMS)."""
 
@@ -150,9 +149,9 @@ class TextEncoderHFLlamaModel:
                 swiglu=interleave_rows(w(p + "mlp.gate_proj.weight", (self.dim_ffn, self.dim)), w(p + "mlp.up_proj.weight", (self.dim_ffn, self.dim))),
                 down=w(p + "mlp.down_proj.weight", (self.dim, self.dim_ffn))))
         self.rope = tuple(t.to(self.device) for t in rope_tables(self.rope_theta))
-        self._bufs, self._rows, self._plans, self._tokenizer = {}, 0, OrderedDict(), None
+        self._init_plumbing()
 
-    # ---- plumbing ------------------------------------------------------------------------------------------------------
+    # ---- plumbing (packed.PackedTower: one workspace, the plan cache) --------------------------------------------------
     def weight_bytes(self):
         """Bytes of Linear weights one forward streams (the launch floor of the tower)."""
         return sum(b[k].numel() * 2 for b in self.blocks for k in ("qkv", "o", "swiglu", "down"))
@@ -160,33 +159,11 @@ class TextEncoderHFLlamaModel:
     def launches(self):
         return 7 * self.num_layers
 
-    def _workspace(self, M):
-        """Row views [M, ...] of ONE set of buffers, sized to the largest M seen so far (growing it drops the launch plans, which hold its pointers)."""
-        if M > self._rows:
+    def _buffers(self):
+        return dict(x=self.dim, h=self.dim, qkv=self.dim_qkv, att=self.dim_attn, f=self.dim_ffn)
 
-            def buf(c):
-                return torch.empty((M, c), dtype=torch.float16, device=self.device)
-
-            self._plans.clear()
-            self._bufs = dict(x=buf(self.dim), h=buf(self.dim), qkv=buf(self.dim_qkv), att=buf(self.dim_attn), f=buf(self.dim_ffn))
-            self._rows = M
-        return {k: v[:M] for k, v in self._bufs.items()}
-
-    def _plan(self, lens, stream):
-        """The tower as a list of (C entry, raw arguments): pointers, strides, the sequence bounds and the stream are fixed per (lengths, stream)."""
-        key = (lens, stream)
-        plan = self._plans.get(key)
-        if plan is not None:
-            self._plans.move_to_end(key)
-            return plan
-        L, M = lib._lib, sum(lens)
-        ws = self._workspace(M)
-        D, A, Q, F, eps = self.dim, self.dim_attn, self.dim_qkv, self.dim_ffn, self.norm_eps
-        p = {k: v.data_ptr() for k, v in ws.items()}
-        cu = [0]
-        for n in lens:
-            cu.append(cu[-1] + n)
-        cu_arr = (lib._i32 * len(cu))(*cu)  # a host array, read at launch time: the plan keeps it alive
+    def _launches(self, p, M, cu_arr, batch, stream):
+        L, D, A, Q, F, eps = lib._lib, self.dim, self.dim_attn, self.dim_qkv, self.dim_ffn, self.norm_eps
         cos, sin = (t.data_ptr() for t in self.rope)
         plan = []
 
@@ -199,23 +176,17 @@ class TextEncoderHFLlamaModel:
         for b in self.blocks:
             norm(b["n1"])
             gemm("h", b["qkv"], "qkv", Q, D, lib.EPI16_NONE, Q)
-            plan.append((L.x2v_attn_f16_causal, (p["qkv"], Q, p["att"], A, cu_arr, len(lens), self.num_heads, self.num_kv_heads, HEAD_DIM, cos, sin, 0.0, stream)))
+            plan.append((L.x2v_attn_f16_causal, (p["qkv"], Q, p["att"], A, cu_arr, batch, self.num_heads, self.num_kv_heads, HEAD_DIM, cos, sin, 0.0, stream)))
             gemm("att", b["o"], "x", D, A, lib.EPI16_RESIDUAL, D, "x")
             norm(b["n2"])
             gemm("h", b["swiglu"], "f", F, D, lib.EPI16_SWIGLU, F)
             gemm("f", b["down"], "x", D, F, lib.EPI16_RESIDUAL, D, "x")
-        self._plans[key] = plan
-        while len(self._plans) > MAX_PLANS:
-            self._plans.popitem(last=False)
         return plan
 
     def forward_packed(self, lens):
         """The L - skip layers on the workspace of these lengths (`x` holds the packed token embeddings): → the residual stream [sum(lens), dim] (the workspace)."""
-        for fn, args in self._plan(tuple(lens), lib._stream()):
-            rc = fn(*args)
-            if rc != 0:
-                lib._check(rc, fn.__name__)
-        return self._bufs["x"][: sum(lens)]
+        M = self._run_packed(lens)
+        return self._bufs["x"][:M]
 
     # ---- the reference's interface -------------------------------------------------------------------------------------
     def _valid_length(self, ids, mask):

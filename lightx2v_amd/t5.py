@@ -14,14 +14,13 @@ output (the reference's GELU module rounds every op), the norm rounds once (X2V_
 not built.
 """
 import math
-from collections import OrderedDict
 
 import torch
 
 from . import lib
+from .packed import MAX_PLANS, PackedTower  # noqa: F401
 
 HEAD_DIM = 64  # x2v_attn_bf16_d64_relbias
-MAX_PLANS = 16  # launch plans kept per model (least recently used first out)
 MAX_BATCH, MAX_LEN = lib.ATTN_D64_MAX_BATCH, lib.ATTN_D64_MAX_LEN
 
 
@@ -57,7 +56,7 @@ def _load_state(src):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-class T5EncoderModel:
+class T5EncoderModel(PackedTower):
     """Same constructor keywords, `infer`, `to_cuda` and `to_cpu` as the reference's T5EncoderModel; `checkpoint_path` may also be a name → tensor dict."""
 
     def __init__(self, text_len, dtype=torch.bfloat16, device="cuda", checkpoint_path=None, tokenizer_path=None, shard_fn=None, cpu_offload=False, offload_granularity="model",
@@ -100,41 +99,20 @@ class T5EncoderModel:
                 qkv=torch.cat([w(p + "attn.q.weight"), w(p + "attn.k.weight"), w(p + "attn.v.weight")]).contiguous(), o=w(p + "attn.o.weight"),
                 geglu=torch.stack([fc1, gate], dim=1).reshape(2 * self.dim_ffn, self.dim).contiguous(),  # row 2n = fc1 row n, row 2n + 1 = gate.0 row n
                 fc2=w(p + "ffn.fc2.weight"), bias=bias_table(sd[p + "pos_embedding.embedding.weight"]).to(self.device)))
-        self._bufs, self._rows, self._plans, self._tokenizer = {}, 0, OrderedDict(), None
+        self._init_plumbing()
 
-    # ---- plumbing ------------------------------------------------------------------------------------------------------
+    # ---- plumbing (packed.PackedTower: one workspace, the plan cache) --------------------------------------------------
+    DTYPE = torch.bfloat16
+
     def weight_bytes(self):
         """Bytes of Linear weights one forward streams (the launch floor of the encoder)."""
         return sum(b[k].numel() * 2 for b in self.blocks for k in ("qkv", "o", "geglu", "fc2"))
 
-    def _workspace(self, M):
-        """Row views [M, ...] of ONE set of buffers, sized to the largest M seen so far (growing it drops the launch plans, which hold its pointers):
-        a service encoding prompts of many lengths holds one workspace, not one per length."""
-        if M > self._rows:
+    def _buffers(self):
+        return dict(x=self.dim, h=self.dim, qkv=3 * self.dim_attn, att=self.dim_attn, f=self.dim_ffn, out=self.dim)
 
-            def buf(c):
-                return torch.empty((M, c), dtype=torch.bfloat16, device=self.device)
-
-            self._plans.clear()
-            self._bufs = dict(x=buf(self.dim), h=buf(self.dim), qkv=buf(3 * self.dim_attn), att=buf(self.dim_attn), f=buf(self.dim_ffn), out=buf(self.dim))
-            self._rows = M
-        return {k: v[:M] for k, v in self._bufs.items()}
-
-    def _plan(self, lens, stream):
-        """The encoder as a list of (C entry, raw arguments): pointers, strides, the sequence bounds and the stream are fixed per (lengths, stream)."""
-        key = (lens, stream)
-        plan = self._plans.get(key)
-        if plan is not None:
-            self._plans.move_to_end(key)
-            return plan
-        L, M = lib._lib, sum(lens)
-        ws = self._workspace(M)
-        D, A, F, eps = self.dim, self.dim_attn, self.dim_ffn, self.norm_eps
-        p = {k: v.data_ptr() for k, v in ws.items()}
-        cu = [0]
-        for n in lens:
-            cu.append(cu[-1] + n)
-        cu_arr = (lib._i32 * len(cu))(*cu)  # a host array, read at launch time: the plan keeps it alive
+    def _launches(self, p, M, cu_arr, batch, stream):
+        L, D, A, F, eps = lib._lib, self.dim, self.dim_attn, self.dim_ffn, self.norm_eps
         plan = []
 
         def norm(x, wt, y):
@@ -146,24 +124,18 @@ class T5EncoderModel:
         for b in self.blocks:
             norm("x", b["n1"], "h")
             gemm("h", b["qkv"], "qkv", 3 * A, D, lib.EPIR_NONE)
-            plan.append((L.x2v_attn_bf16_d64_relbias, (p["qkv"], 3 * A, b["bias"].data_ptr(), p["att"], A, cu_arr, len(lens), self.num_heads, 1.0, stream)))
+            plan.append((L.x2v_attn_bf16_d64_relbias, (p["qkv"], 3 * A, b["bias"].data_ptr(), p["att"], A, cu_arr, batch, self.num_heads, 1.0, stream)))
             gemm("att", b["o"], "x", D, A, lib.EPIR_RESIDUAL, "x")
             norm("x", b["n2"], "h")
             gemm("h", b["geglu"], "f", F, D, lib.EPIR_GEGLU)
             gemm("f", b["fc2"], "x", D, F, lib.EPIR_RESIDUAL, "x")
         norm("x", self.norm, "out")
-        self._plans[key] = plan
-        while len(self._plans) > MAX_PLANS:
-            self._plans.popitem(last=False)
         return plan
 
     def forward_packed(self, lens):
         """Blocks + final norm on the workspace of these lengths (`x` holds the packed token embeddings): → out [sum(lens), dim] (the workspace)."""
-        for fn, args in self._plan(tuple(lens), lib._stream()):
-            rc = fn(*args)
-            if rc != 0:
-                lib._check(rc, fn.__name__)
-        return self._bufs["out"][: sum(lens)]
+        M = self._run_packed(lens)
+        return self._bufs["out"][:M]
 
     # ---- the reference's interface -------------------------------------------------------------------------------------
     def infer_ids(self, ids, mask):

@@ -251,6 +251,8 @@ def test_new_entries_validate_arguments_without_a_gpu():
     assert L.x2v_attn_f16_causal(a, 1016, a, 512, cu, 2, 4, 2, 128, None, None, 0.0, None) == -2  # ld does not cover q | k | v
     assert L.x2v_attn_f16_causal(a, 1024, a, 512, (ctypes.c_int * 3)(0, 5, 5), 2, 4, 2, 128, None, None, 0.0, None) == -1  # an empty sequence
     assert L.x2v_attn_f16_causal(a, 1024, a, 512, (ctypes.c_int * 2)(0, 513), 1, 4, 2, 128, None, None, 0.0, None) == -1  # > 512 tokens
+    assert L.x2v_attn_f16_causal(a, 1024, a, 512, (ctypes.c_int * 2)(-1, 8), 1, 4, 2, 128, None, None, 0.0, None) == -1  # negative cu_seqlens[0]
+    assert L.x2v_attn_f16_causal(a, 1024, a, 512, (ctypes.c_int * 3)(0, 8, 5), 2, 4, 2, 128, None, None, 0.0, None) == -1  # decreasing
     assert L.x2v_attn_f16_causal(a, 1024, a, 512, cu, 2, 4, 2, 128, None, None, -1.0, None) == -5  # negative scale
     # x2v_gemm_f16(x, ldx, w, ldw, bias, y, ldy, M, N, K, epilogue, resid, ldr, stream)
     assert L.x2v_gemm_f16(a, 64, a, 64, None, a, 64, 4, 64, 64, 5, None, 0, None) == -5  # unknown epilogue
