@@ -441,6 +441,19 @@ int x2v_vae_conv_s2_f16(const void* xp, int64_t x_frame_stride, int64_t x_row_st
 int x2v_vae_video_prep(const float* video, int64_t c_stride, int64_t t_stride, int64_t row_stride, int T, int H, int W, void* y, int64_t y_frame_stride,
                        int64_t y_row_stride, int64_t y_px_stride, int mode, void* stream);
 
+/* One output tile of WanVAE_.tiled_decode / tiled_encode (vae.py:568-682: blend_v with the tile above, blend_h with the tile to the left, crop to the
+ * stride, cat) from the RAW tiles in one pass.  Tiles are fp32 channels-last: center [T][ch][cw][C], up [T][uh][cw][C], left [T][ch][lw][C], up_left
+ * [T][uh][lw][C]; ev / eh = the vertical / horizontal blend extents min(len_a, len_b, blend) (0 = no neighbour on that axis: its pointer may be NULL;
+ * up_left is read only where both are set).  For y < rh, x < rw the value
+ *   u = up[uh-ev+y][x] (x < eh: up_left[uh-ev+y][lw-eh+x]*(1-x/eh) + u*(x/eh));  v = u*(1-y/ev) + center[y][x]*(y/ev) for y < ev, else center[y][x];
+ *   l = left[y][lw-eh+x] (y < ev: up_left[..]*(1-y/ev) + l*(y/ev));              out = l*(1-x/eh) + v*(x/eh) for x < eh, else v
+ * goes to out[c*out_c_stride + t*out_t_stride + y*out_row_stride + x] (out = the region's first element in a channel-first video), clamped to [-1, 1]
+ * when clamp = 1.  Weights are formed in double and rounded once to fp32, every product and sum is rounded on its own: the bits of the reference's
+ * in-place row-major blending whenever blend <= stride on both axes (a neighbour's rows read here then lie outside its own blend zone). */
+int x2v_vae_tile_compose_f32(const float* center, const float* up, const float* left, const float* up_left, int T, int C, int ch, int cw, int uh, int lw,
+                             int ev, int eh, int rh, int rw, float* out, int64_t out_c_stride, int64_t out_t_stride, int64_t out_row_stride, int clamp,
+                             void* stream);
+
 /* ---- HunyuanVideo VAE decode (video_encoders/hf/autoencoder_kl_causal_3d/), fp32, channels-last ------------------- */
 
 /* Pixel-wise producer: v = x*mul[c] + add[c] (mul/add optional; GroupNorm applied as a per-channel affine), optional SiLU

@@ -506,6 +506,105 @@ __global__ __launch_bounds__(256) void blend_axis_kernel(const float* __restrict
   }
 }
 
+// One output tile of WanVAE_.tiled_decode / tiled_encode (vae.py:568-682) in one pass: the reference cross-fades the tiles in place in row-major
+// order (blend_v with the tile above, blend_h with the tile to the left), crops each to the stride and concatenates.  With blend <= stride on both
+// axes the rows / columns a tile reads from a neighbour lie outside that neighbour's own blend zone on that axis, so every output value is a fixed
+// expression of at most four RAW tiles (centre, up, left, up-left), evaluated here in the reference's order of operations:
+//   u = U[uh - ev + y, x],          x < eh: u = UL[uh - ev + y, lw - eh + x] * (1 - x/eh) + u * (x/eh)      (U was blend_h'ed with UL before C read it)
+//   v = u * (1 - y/ev) + C[y, x] * (y/ev)                                                        for y < ev     (blend_v)
+//   l = L[y, lw - eh + x],          y < ev: l = UL[uh - ev + y, lw - eh + x] * (1 - y/ev) + l * (y/ev)      (L was blend_v'ed with UL)
+//   out = l * (1 - x/eh) + v * (x/eh)                                                            for x < eh     (blend_h)
+// The weights are formed in double and rounded once to fp32 (torch's Python-float scalars), every product and sum is rounded on its own (no FMA
+// contraction: in the ISA the blend is v_mul_f32 / v_add_f32; the only fused fp32 ops left belong to the index divisions): the reference's bits.  Tiles are channels-last [T][h][w][C] (U has C's width, L has C's height, UL has U's height and L's width);
+// the output is channel-first, out[c][t][y][x] through its strides.  A thread owns PX consecutive output pixels of one row: it reads their PX * C
+// contiguous floats from each tile it needs and writes PX contiguous floats into each channel plane, consecutive lanes consecutive segments.  <3, 4>
+// is the decoder's form (48-byte reads, 16-byte writes per lane; tile sizes, extents and the region are multiples of 8 pixels there); <0, 1> takes
+// any channel count and width (the encoder's 16-channel latents, a few MB).  Memory-bound, no LDS, grid-stride.
+// Contraction is switched off for these sums of products: the reference rounds every product and every sum.  Plain operators, not __fmul_rn /
+// __fadd_rn — those are header functions compiled under hipcc's default contract(fast), and a product inside them still fuses into the sum.
+__device__ __forceinline__ float tile_compose_value(float v, float u, float l, float ulv, bool iny, bool inx, float wy1, float wy, float wx1, float wx) {
+#pragma clang fp contract(off)
+  if (iny) {
+    if (inx) u = ulv * wx1 + u * wx;
+    v = u * wy1 + v * wy;
+  }
+  if (inx) {
+    if (iny) l = ulv * wy1 + l * wy;
+    v = l * wx1 + v * wx;
+  }
+  return v;
+}
+
+// (float)(1 - k/n), (float)(k/n) with the quotient and the difference in double
+__device__ __forceinline__ void tile_compose_weights(int k, int n, float& w1, float& w) {
+  const double q = (double)k / (double)n;
+  w1 = (float)(1.0 - q), w = (float)q;
+}
+
+template <int CT, int PX>
+__global__ __launch_bounds__(256) void tile_compose_kernel(const float* __restrict__ ct, const float* __restrict__ ut, const float* __restrict__ lt,
+                                                           const float* __restrict__ ult, int T, int C, int ch, int cw, int uh, int lw, int ev, int eh, int rh,
+                                                           int rw, float* __restrict__ out, int64_t ocs, int64_t ots, int64_t ors, int clamp) {
+  static_assert(PX == 1 || CT > 0, "several pixels per thread need a compile-time channel count");
+  const int Cn = CT ? CT : C;
+  const int rwq = rw / PX;  // the launcher takes PX > 1 only when it divides rw and eh: a thread's pixels are all inside or all outside the blend columns
+  const int64_t total = (int64_t)T * rh * rwq;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int x = (int)(i % rwq) * PX;
+    const int y = (int)((i / rwq) % rh);
+    const int64_t t = i / ((int64_t)rwq * rh);
+    const bool iny = y < ev, inx = x < eh;
+    float wy1 = 0.f, wy = 0.f;
+    if (iny) tile_compose_weights(y, ev, wy1, wy);
+    const int64_t uy = t * uh + (uh - ev + y);  // row of the upper tiles (read only where iny)
+    const float* cp = ct + ((t * ch + y) * cw + x) * Cn;
+    const float* up = iny ? ut + (uy * cw + x) * Cn : cp;  // a pointer that is not needed aliases the centre pixel and is not dereferenced
+    const float* lp = inx ? lt + ((t * ch + y) * lw + (lw - eh + x)) * Cn : cp;
+    const float* ulp = (iny && inx) ? ult + (uy * lw + (lw - eh + x)) * Cn : cp;
+    float* op = out + t * ots + (int64_t)y * ors + x;
+    if constexpr (PX == 1) {
+      float wx1 = 0.f, wx = 0.f;
+      if (inx) tile_compose_weights(x, eh, wx1, wx);
+      for (int c = 0; c < Cn; ++c) {
+        const float v = tile_compose_value(cp[c], iny ? up[c] : 0.f, inx ? lp[c] : 0.f, (iny && inx) ? ulp[c] : 0.f, iny, inx, wy1, wy, wx1, wx);
+        op[c * ocs] = clamp ? fminf(fmaxf(v, -1.f), 1.f) : v;
+      }
+    } else {
+      constexpr int N = PX * (CT ? CT : 1);  // the thread's floats per tile: contiguous in every tile
+      float cv[N], uv[N], lv[N], ulv[N];
+#pragma unroll
+      for (int k = 0; k < N; ++k) cv[k] = cp[k], uv[k] = lv[k] = ulv[k] = 0.f;
+      if (iny) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) uv[k] = up[k];
+      }
+      if (inx) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) lv[k] = lp[k];
+        if (iny) {
+#pragma unroll
+          for (int k = 0; k < N; ++k) ulv[k] = ulp[k];
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < PX; ++p) {
+        float wx1 = 0.f, wx = 0.f;
+        if (inx) tile_compose_weights(x + p, eh, wx1, wx);
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          const int k = p * CT + c;
+          const float v = tile_compose_value(cv[k], uv[k], lv[k], ulv[k], iny, inx, wy1, wy, wx1, wx);
+          cv[k] = clamp ? fminf(fmaxf(v, -1.f), 1.f) : v;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+#pragma unroll
+        for (int p = 0; p < PX; ++p) op[c * ocs + p] = cv[p * CT + c];
+    }
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Halo-tiled form of the 16-bit convolution for 3x3 spatial kernels (kt = 1 or 3), 64 pixels per wave.  What still reaches it: by default the 3x3
@@ -1106,5 +1205,32 @@ extern "C" __attribute__((visibility("default"))) int x2v_blend_axis_f32(const f
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536 * 4);
   hipLaunchKernelGGL(blend_axis_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, outer, na, nb, inner, a_outer_stride, b_outer_stride, extent);
   X2V_LAUNCH_CHECK("blend_axis launch");
+  return X2V_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_vae_tile_compose_f32(const float* center, const float* up, const float* left, const float* up_left, int T, int C,
+                                                                               int ch, int cw, int uh, int lw, int ev, int eh, int rh, int rw, float* out,
+                                                                               int64_t out_c_stride, int64_t out_t_stride, int64_t out_row_stride, int clamp, void* stream) {
+  X2V_REQUIRE(center && out, X2V_E_ARG, "vae_tile_compose: null centre tile or output");
+  X2V_REQUIRE(clamp == 0 || clamp == 1, X2V_E_ARG, "vae_tile_compose: clamp = 0 | 1");
+  X2V_REQUIRE(T > 0 && C > 0 && ch > 0 && cw > 0 && rh > 0 && rw > 0 && rh <= ch && rw <= cw, X2V_E_SHAPE,
+              "vae_tile_compose: bad shape T=%d C=%d tile %dx%d region %dx%d (the region lies inside the centre tile)", T, C, ch, cw, rh, rw);
+  X2V_REQUIRE(ev >= 0 && eh >= 0 && ev <= ch && eh <= cw, X2V_E_SHAPE, "vae_tile_compose: blend extents %d / %d exceed the centre tile %dx%d", ev, eh, ch, cw);
+  X2V_REQUIRE(ev == 0 || (up && uh > 0 && ev <= uh), X2V_E_SHAPE, "vae_tile_compose: vertical extent %d needs an upper tile of at least that height (uh=%d)", ev, uh);
+  X2V_REQUIRE(eh == 0 || (left && lw > 0 && eh <= lw), X2V_E_SHAPE, "vae_tile_compose: horizontal extent %d needs a left tile of at least that width (lw=%d)", eh, lw);
+  X2V_REQUIRE(ev == 0 || eh == 0 || up_left, X2V_E_ARG, "vae_tile_compose: both extents set but no up-left tile");
+  X2V_REQUIRE(out_row_stride >= rw && out_t_stride > 0 && out_c_stride > 0, X2V_E_SHAPE, "vae_tile_compose: output strides must cover the region");
+  X2V_REQUIRE(((uintptr_t)center | (uintptr_t)up | (uintptr_t)left | (uintptr_t)up_left | (uintptr_t)out) % 4 == 0, X2V_E_ALIGN,
+              "vae_tile_compose: pointers must be 4-byte aligned");
+  const bool wide = C == 3 && rw % 4 == 0 && eh % 4 == 0;  // the decoder's tiles: four pixels per thread
+  const int64_t total = (int64_t)T * rh * (wide ? rw / 4 : rw);
+  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 8);  // 8 workgroups per CU, grid-stride behind that
+  if (wide)
+    hipLaunchKernelGGL((tile_compose_kernel<3, 4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, center, up, left, up_left, T, C, ch, cw, uh, lw, ev, eh, rh, rw, out,
+                       out_c_stride, out_t_stride, out_row_stride, clamp);
+  else
+    hipLaunchKernelGGL((tile_compose_kernel<0, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, center, up, left, up_left, T, C, ch, cw, uh, lw, ev, eh, rh, rw, out,
+                       out_c_stride, out_t_stride, out_row_stride, clamp);
+  X2V_LAUNCH_CHECK("vae_tile_compose launch");
   return X2V_OK;
 }

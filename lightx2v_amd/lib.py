@@ -91,6 +91,7 @@ PROTOTYPES = {
     "x2v_vae_prep_ex_f32": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i64, _i64, _c_void_p],
     "x2v_vae_conv_s2_f16": [_c_void_p, _i64, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_vae_video_prep": [_c_void_p, _i64, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
+    "x2v_vae_tile_compose_f32": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_gemm_f16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
     "x2v_gemm_f16_tile_choice": [_i64, _i32],
     "x2v_attn_f16_d80": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
@@ -1012,6 +1013,34 @@ def vae_video_prep(video, y_view, split=False):
     mode = 2 if split else VIDEO_PREP_MODES[y_view.dtype]
     _check(_lib.x2v_vae_video_prep(_p(video), video.stride(0), video.stride(1), video.stride(2), T, H, W, _p(y_view), y_view.stride(0), y_view.stride(1),
                                    y_view.stride(2), mode, _stream()), "vae_video_prep")
+
+
+def vae_tile_compose(center, up, left, up_left, ev, eh, out_region, clamp=False):
+    """x2v_vae_tile_compose_f32: one output tile of the Wan VAE's tiled decode / encode from its raw tiles.  center [T, ch, cw, C], up [T, uh, cw, C],
+    left [T, ch, lw, C], up_left [T, uh, lw, C]: contiguous fp32 channels-last (None where the tile has no such neighbour; ev / eh = 0 then);
+    out_region: the [C, T, rh, rw] view (unit x stride) of the channel-first output that this tile owns, rh <= ch, rw <= cw."""
+    T, ch, cw, C = _f32dense(center, "vae_tile_compose center", 4).shape
+    uh = lw = 0
+    if ev:
+        if up is None or tuple(_f32dense(up, "vae_tile_compose up", 4).shape[::2]) != (T, cw) or up.shape[3] != C:
+            raise X2VError(f"vae_tile_compose: a vertical extent needs an upper tile [T, uh, {cw}, {C}]")
+        uh = up.shape[1]
+    if eh:
+        if left is None or tuple(_f32dense(left, "vae_tile_compose left", 4).shape[:2]) != (T, ch) or left.shape[3] != C:
+            raise X2VError(f"vae_tile_compose: a horizontal extent needs a left tile [{T}, {ch}, lw, {C}]")
+        lw = left.shape[2]
+    if ev and eh and (up_left is None or tuple(_f32dense(up_left, "vae_tile_compose up_left", 4).shape) != (T, uh, lw, C)):
+        raise X2VError(f"vae_tile_compose: both extents need an up-left tile [{T}, {uh}, {lw}, {C}]")
+    _dev_view(out_region, "vae_tile_compose out", (torch.float32,))
+    if out_region.dim() != 4 or out_region.shape[0] != C or out_region.shape[1] != T or out_region.stride(3) != 1:
+        raise X2VError(f"vae_tile_compose: the output region must be a [{C}, {T}, rh, rw] view with unit x stride, got {tuple(out_region.shape)} strides {out_region.stride()}")
+    rh, rw = out_region.shape[2:]
+    if not (0 < rh <= ch and 0 < rw <= cw and 0 <= ev <= min(ch, uh if ev else ch) and 0 <= eh <= min(cw, lw if eh else cw)):
+        raise X2VError(f"vae_tile_compose: region {rh}x{rw} / extents {ev}, {eh} do not fit the tiles (centre {ch}x{cw}, up {uh} rows, left {lw} columns)")
+    init()
+    _check(_lib.x2v_vae_tile_compose_f32(_p(center), _p(up) if ev else None, _p(left) if eh else None, _p(up_left) if ev and eh else None, T, C, ch, cw, uh, lw, ev, eh,
+                                         rh, rw, _p(out_region), out_region.stride(0), out_region.stride(1), out_region.stride(2), int(bool(clamp)), _stream()),
+           "vae_tile_compose")
 
 
 def vae_replicate_border_(buf, lead, pad):

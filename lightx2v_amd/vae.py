@@ -19,6 +19,12 @@ What is laid out differently for the MI355X (288 GB HBM, fp32-input MFMA):
     kernel (1x1 taps), per frame.
 Torch is used for allocation, 2-frame cache moves (copy_), the V transpose and the boundary layout changes
 ([C,T,H,W] ↔ channels-last) — memory plumbing, no arithmetic.
+
+`use_tiling` (the configs' "use_tiling_vae"; WanVAE_.tiled_decode / tiled_encode, vae.py:568-682): `tile_plan` holds the reference's tile loops as data,
+`WanVAE_.tiled_decode` / `vae_enc.tiled_encode` run each tile through the cache-carrying Decoder3d / Encoder3d of its geometry (at most four per image
+size, on shared converted weights), the decoder's head without its fused clamp, and `compose_tiles` turns the raw tiles into the channel-first output —
+one x2v_vae_tile_compose_f32 launch per tile (blend_v + blend_h + crop + cat + clamp + permute in one pass, the reference's bits) when blend <= stride,
+else in-place x2v_blend_axis_f32 blends in the reference's tile order.
 """
 import torch
 
@@ -101,13 +107,23 @@ def _split16(v, cp, split):
 class Decoder3d:
     """reference: vae.py:377-489."""
 
-    def __init__(self, sd, dim, latent_hw, device, conv16=False):
-        self._setup(sd, "decoder.", latent_hw, device, conv16)
+    def __init__(self, sd, dim, latent_hw, device, conv16=False, share=None):
+        """share: a Decoder3d of the same state dict and mode whose converted weights (`w`, `w16`, `w16_tail`) this one uses instead of converting `sd`
+        again — the tiled decode keeps one decoder per tile geometry (buffers and caches are per geometry, weights are not)."""
+        self._setup(sd, "decoder.", latent_hw, device, conv16, share)
         self.dims, self.plan = synth.wan_vae_decoder_plan(dim)
 
-    def _setup(self, sd, prefix, hw, device, conv16):
+    def _setup(self, sd, prefix, hw, device, conv16, share=None):
         """Weights under `prefix` in the kernels' layouts, buffer pools and cache state — shared with the encoder (vae_enc.Encoder3d)."""
         self.device = device
+        if share is not None:
+            if share.conv16 != conv16 or torch.device(share.device) != torch.device(device):
+                raise lib.X2VError("Decoder3d: shared weights must come from an instance of the same conv16 mode and device")
+            self.conv16, self.split = share.conv16, share.split
+            self.w, self.w16, self.w16_tail = share.w, share.w16, share.w16_tail
+            self.h0, self.w0 = hw
+            self._bufs, self._pool, self._rep = {}, {}, {}
+            return
         # conv16: False = fp32 convolutions on the fp32 matrix instruction (the reference's precision); True = fp16 operands (opt-in fast
         # decode, 11 mantissa bits); "split" = hi/lo fp16 split of activations and weights, three 16-bit products per fp32 product
         # accumulated in fp32 (~22 mantissa bits per operand: fp32-grade results at 16-bit matrix speed)
@@ -222,9 +238,10 @@ class Decoder3d:
                 x = self._conv_cached(p + "time", p + "time_conv", x, flags=lib.VCONV_TSPLIT)
         return self._conv_cached(p + "sp", p + "resample.1", x, upsample=True)
 
-    def forward(self, x):
+    def forward(self, x, clamp=True):
         """One chunk: x [T, h, w, z] (output of conv2) → [T', 8h, 8w, 3], clamped (the reference clamps after the
-        concat of all chunks, vae.py:951-955 — elementwise, so per chunk is the same)."""
+        concat of all chunks, vae.py:951-955 — elementwise, so per chunk is the same).  clamp=False: the head's raw output, for the tiled decode, whose
+        tiles the reference blends unclamped and clamps afterwards (vae.py:949)."""
         x = self._conv_cached("conv1", "decoder.conv1", x)
         x = self.residual_block("decoder.middle.0.", x)
         x = self.attention_block("decoder.middle.1.", x)
@@ -232,7 +249,51 @@ class Decoder3d:
         for idx, kind, _, _ in self.plan:
             p = f"decoder.upsamples.{idx}."
             x = self.residual_block(p, x) if kind == "res" else self.resample(p, x, kind)
-        return self._conv_cached("head", "decoder.head.2", x, gamma=self.w["decoder.head.0.gamma"], silu=True, flags=lib.VCONV_CLAMP)
+        return self._conv_cached("head", "decoder.head.2", x, gamma=self.w["decoder.head.0.gamma"], silu=True, flags=lib.VCONV_CLAMP if clamp else 0)
+
+
+def tile_plan(h, w, min_h, min_w, stride_h, stride_w):
+    """The tile loops of WanVAE_.tiled_decode / tiled_encode (vae.py:568-682) as data.  All six arguments are in ONE unit — the latent grid's; the decode
+    blends in pixels and the encode tiles in pixels, both 8x these numbers (the tile attributes, like the reference's 256 / 192, are multiples of 8).
+    Tile starts are range(0, size, stride), a tile is clipped to the image (slivers down to one unit occur), blend = min - stride.  Per tile (row-major,
+    the reference's blending order):
+      i, j         row and column of the tile;          y0, x0   its origin;          th, tw   its clipped size;
+      ev, eh       the blend extents min(len_a, len_b, blend) with the tile above / to the left (0 in the first row / column) — the neighbour is read
+                   at len_a - extent + idx;
+      rh, rw       what survives the crop to the stride and the final crop to the image: the region [y0, y0 + rh) x [x0, x0 + rw) of the output.
+    mode: "fused" when blend <= stride on both axes (min <= 2 stride) — a neighbour's rows read by a tile then lie outside the neighbour's own blend zone,
+    every output value is an expression of at most four raw tiles (x2v_vae_tile_compose_f32); else "sequential" (in-place blends in tile order)."""
+    if min(h, w) < 1 or stride_h < 1 or stride_w < 1 or min_h < stride_h or min_w < stride_w:
+        raise lib.X2VError(f"tile_plan: {h}x{w} with tiles {min_h}x{min_w} at strides {stride_h}x{stride_w}: sizes must be positive and a tile at least one stride long")
+    bh, bw = min_h - stride_h, min_w - stride_w
+    ys, xs = list(range(0, h, stride_h)), list(range(0, w, stride_w))
+    ths, tws = [min(min_h, h - y) for y in ys], [min(min_w, w - x) for x in xs]
+    tiles = []
+    for i, y0 in enumerate(ys):
+        for j, x0 in enumerate(xs):
+            tiles.append(dict(i=i, j=j, y0=y0, x0=x0, th=ths[i], tw=tws[j], ev=min(ths[i - 1], ths[i], bh) if i else 0, eh=min(tws[j - 1], tws[j], bw) if j else 0,
+                              rh=min(ths[i], stride_h), rw=min(tws[j], stride_w)))
+    return dict(mode="fused" if bh <= stride_h and bw <= stride_w else "sequential", rows=len(ys), cols=len(xs), blend=(bh, bw), tiles=tiles)
+
+
+def compose_tiles(plan, raw, out, scale=1, clamp=False):
+    """The blending half of tiled_decode / tiled_encode: `raw` = the tiles of `plan` in its order, fp32 channels-last [T, scale th, scale tw, C] (scale: 8
+    for the decode, whose plan is in latent units and whose tiles are pixels); `out` [C, T, scale h, scale w].  Fused mode: one launch of
+    x2v_vae_tile_compose_f32 per tile on the raw tiles.  Sequential mode (blend > stride): x2v_blend_axis_f32 in place in tile order as the reference does,
+    then the same kernel with no neighbours as the crop + channel-first store (+ clamp) of each blended tile."""
+    cols, s = plan["cols"], scale
+    for k, p in enumerate(plan["tiles"]):
+        up, left = (raw[k - cols] if p["i"] else None), (raw[k - 1] if p["j"] else None)
+        region = out[:, :, s * p["y0"] : s * (p["y0"] + p["rh"]), s * p["x0"] : s * (p["x0"] + p["rw"])]
+        if plan["mode"] == "fused":
+            lib.vae_tile_compose(raw[k], up, left, raw[k - cols - 1] if p["i"] and p["j"] else None, s * p["ev"], s * p["eh"], region, clamp=clamp)
+            continue
+        if up is not None and p["ev"]:
+            lib.blend_axis_(up, raw[k], 1, s * p["ev"])
+        if left is not None and p["eh"]:
+            lib.blend_axis_(left, raw[k], 2, s * p["eh"])
+        lib.vae_tile_compose(raw[k], None, None, None, 0, 0, region, clamp=clamp)
+    return out
 
 
 def chunk_bounds(t, chunk_frames):
@@ -263,6 +324,73 @@ class WanVAE_:
         self.conv2_b = sd["conv2.bias"].to(device=device, dtype=torch.float32).contiguous() if has_dec else None
         self.decoder = None
         self.encoder = None
+        # tiling (vae.py:521-527): the reference's names and defaults, in pixels; settable on the instance (multiples of 8, the spatial compression)
+        self.tile_sample_min_height = 256
+        self.tile_sample_min_width = 256
+        self.tile_sample_stride_height = 192
+        self.tile_sample_stride_width = 192
+        self._tile_decoders = {}  # (latent size, latent tile size) -> Decoder3d; at most four per image size (full, right edge, bottom edge, corner)
+        self._tile_encoders = {}  # (video size, pixel tile size) -> Encoder3d
+
+    def tile_geometry(self):
+        """(min_h, min_w, stride_h, stride_w) in latent units; the pixel attributes must be multiples of 8 (the reference floors them, vae.py:573-576,
+        and then crops to the pixel stride: for other values its tiles and its crop disagree)."""
+        px = (self.tile_sample_min_height, self.tile_sample_min_width, self.tile_sample_stride_height, self.tile_sample_stride_width)
+        if any(int(v) != v or v <= 0 or v % 8 for v in px):
+            raise lib.X2VError(f"tiled VAE: tile sizes and strides must be positive multiples of 8 pixels, got {px}")
+        return tuple(int(v) // 8 for v in px)
+
+    def _tile_module(self, cls, store, first, image_hw, hw):
+        """The cache-carrying Decoder3d / Encoder3d of tile geometry `hw` of an image of `image_hw`: one per geometry, all on the weights converted once
+        (by `first`, the plain path's instance, when there is one).  Another image size drops the old geometries and their buffers."""
+        share = next(iter(store.values()), first)
+        if any(k[0] != image_hw for k in store):
+            store.clear()
+        m = store.get((image_hw, hw))
+        if m is None:
+            m = store[(image_hw, hw)] = cls(self.sd, self.dim, hw, self.device, conv16=self.conv16, share=share)
+        return m
+
+    def tiled_decode(self, z, scale, tile_chunk_frames=None):
+        """reference: WanVAE_.tiled_decode (vae.py:631-682) + WanVAE.decode's clamp (vae.py:949).  z [1, 16, T, h, w] → [1, 3, 1 + 4 (T-1), 8h, 8w] in [-1, 1].
+        The un-normalisation and conv2 (1x1) run once on the whole latent (pixel-wise: the same value per pixel as per tile).  Each latent tile then
+        goes through the decoder of its geometry with a cleared cache and WITHOUT the head's fused clamp; the raw tiles [T', 8 th, 8 tw, 3] are composed
+        into the output by x2v_vae_tile_compose_f32 (blend in pixels, crop to the stride, channel-first store, clamp).
+        tile_chunk_frames: latent frames per decoder pass after the first (None = all of them: a 32 x 32 latent tile gives the low-resolution stages 2 x 4
+        workgroups per frame; any value gives the same bits)."""
+        zc, t, h, w = z.shape[1:]
+        if self.conv2_w is None:
+            raise lib.X2VError("decode: the state dict holds no decoder (conv2.* / decoder.* tensors)")
+        plan = tile_plan(h, w, *self.tile_geometry())
+        zl = z[0].permute(1, 2, 3, 0).contiguous().float()
+        zn = torch.empty_like(zl)
+        lib.vae_prep(zl, zn, (h * w * zc, w * zc), a=scale[1].float().contiguous(), b=scale[0].float().contiguous())
+        x = torch.empty_like(zn)
+        lib.vae_conv(zn, (h * w * zc, w * zc, zc), self.conv2_w, x, t, h, w, bias=self.conv2_b)
+        bounds = chunk_bounds(t, max(1, t - 1) if tile_chunk_frames is None else max(1, int(tile_chunk_frames)))
+        t_out = 1 + 4 * (t - 1)
+        raw = []
+        for p in plan["tiles"]:
+            dec = self._tile_module(Decoder3d, self._tile_decoders, self.decoder, (h, w), (p["th"], p["tw"]))
+            xt = x[:, p["y0"] : p["y0"] + p["th"], p["x0"] : p["x0"] + p["tw"]].contiguous()
+            tile = torch.empty((t_out, 8 * p["th"], 8 * p["tw"], 3), dtype=torch.float32, device=x.device)
+            dec.clear_cache()
+            f = 0
+            for a, b in bounds:
+                o = dec.forward(xt[a:b], clamp=False)
+                tile[f : f + o.shape[0]].copy_(o)
+                f += o.shape[0]
+            dec.clear_cache()
+            raw.append(tile)
+        out = torch.empty((1, 3, t_out, 8 * h, 8 * w), dtype=torch.float32, device=x.device)
+        compose_tiles(plan, raw, out[0], scale=8, clamp=True)
+        return out
+
+    def tiled_encode(self, x, scale, chunk_frames=None):
+        """reference: WanVAE_.tiled_encode (vae.py:568-629); in vae_enc.py."""
+        from . import vae_enc
+
+        return vae_enc.tiled_encode(self, x, scale, chunk_frames)
 
     def encode(self, x, scale, chunk_frames=None):
         """x [1, 3, T, H, W] (T = 1 + 4k); scale = [mean, inv_std] → mu [1, z_dim, 1 + k, H / 8, W / 8] fp32, (mu - mean) * inv_std (vae.py:684-711)."""
@@ -290,9 +418,13 @@ class WanVAE_:
 
 
 class WanVAE:
-    """reference: vae.py:789-957 (`use_tiling` is not built)."""
+    """reference: vae.py:789-957.  `use_tiling` (the reference configs' "use_tiling_vae") selects WanVAE_.tiled_decode / tiled_encode: overlapping
+    256 x 256 px tiles at a 192 px stride, decoded / encoded independently and cross-faded — a different video from the plain decode's (relative L2
+    0.4 with seeded weights), with buffers sized by the tile and the frames per pass, not by the frame area (720p x 81f decode: 50 GB at the whole-clip
+    default of `tile_chunk_frames`, 15.8 GB at 4).  `parallel` keeps precedence over it, as in vae.py:935-949."""
 
-    def __init__(self, sd, z_dim=16, dim=96, device="cuda", parallel=False, conv16="split", chunk_frames=4, encode_chunk_frames=4, use_tiling=False):
+    def __init__(self, sd, z_dim=16, dim=96, device="cuda", parallel=False, conv16="split", chunk_frames=4, encode_chunk_frames=4, use_tiling=False,
+                 tile_chunk_frames=None):
         """conv16 selects how the 3x3(x3) convolutions multiply (accumulation, residual stream, norms and attention are fp32 in every mode):
           "split" (default)  activations and weights as hi + lo fp16 pairs (~22 mantissa bits), three 16-bit products per fp32 product:
                              fp32-grade — it meets the all-fp32 decode's tolerance against the reference's fp32 decode (vae.py:794) — at
@@ -304,13 +436,20 @@ class WanVAE:
         self.inv_std = 1.0 / torch.tensor(synth.WAN_VAE_STD, dtype=torch.float32, device=device)
         self.scale = [self.mean, self.inv_std]
         self.use_tiling = use_tiling
+        self.tile_chunk_frames = tile_chunk_frames  # latent frames per decoder pass inside a tile (None: the whole clip behind the first frame)
         self.model = WanVAE_(sd, dim=dim, z_dim=z_dim, device=device, conv16=conv16, chunk_frames=chunk_frames, encode_chunk_frames=encode_chunk_frames)
+
+    def _tiling_device(self, what):
+        """The tiled paths exist on the GPU only (the product has no CPU path): said before the state dict is looked at."""
+        if torch.device(self.device).type != "cuda":
+            raise lib.X2VError(f"WanVAE.{what}: use_tiling (tiled_{what}) is not built for device {self.device!r}: the tile driver and its compose kernel are HIP")
 
     def encode(self, videos, args=None):
         """videos: list of [3, T, H, W] in [-1, 1] → list of latents [z_dim, 1 + (T - 1) / 4, H / 8, W / 8] fp32 (vae.py:867-881; `args` is accepted for the
         reference's signature — its cpu_offload has no counterpart here)."""
         if self.use_tiling:
-            raise lib.X2VError("WanVAE.encode: use_tiling (tiled_encode, vae.py:568) is not built")
+            self._tiling_device("encode")
+            return [self.model.tiled_encode(u.unsqueeze(0).to(self.device), self.scale).float().squeeze(0) for u in videos]
         return [self.model.encode(u.unsqueeze(0).to(self.device), self.scale).float().squeeze(0) for u in videos]
 
     def decode_dist(self, zs, world_size, cur_rank, split_dim):
@@ -327,6 +466,7 @@ class WanVAE:
             lo, hi = total - (chunk + 2 * pad), total
         else:
             lo, hi = cur_rank * chunk - pad, (cur_rank + 1) * chunk + pad
+        lo, hi = max(lo, 0), min(hi, total)  # the reference's slices clip (a one-rank group: the whole latent)
         zs = zs.narrow(split_dim, lo, hi - lo).contiguous()
         images = self.model.decode(zs.unsqueeze(0).to(self.device), self.scale)
         px = split_dim + 1
@@ -344,8 +484,6 @@ class WanVAE:
     def decode(self, zs, generator=None, config=None):
         """zs [16, T, h, w] → images [1, 3, T_out, 8h, 8w] fp32 in [-1, 1] (vae.py:931-957; `parallel` = the decode_dist
         branch when H or W divides by the world size, else the plain decode like the reference's fallback)."""
-        if self.use_tiling:
-            raise lib.X2VError("WanVAE.decode: use_tiling (tiled_decode, vae.py:631) is not built")
         if self.parallel:
             import torch.distributed as dist
 
@@ -354,4 +492,7 @@ class WanVAE:
                 return self.decode_dist(zs, n, r, 3)
             if zs.shape[2] % n == 0:
                 return self.decode_dist(zs, n, r, 2)
+        elif self.use_tiling:
+            self._tiling_device("decode")
+            return self.model.tiled_decode(zs.unsqueeze(0).to(self.device), self.scale, tile_chunk_frames=self.tile_chunk_frames)
         return self.model.decode(zs.unsqueeze(0).to(self.device), self.scale)

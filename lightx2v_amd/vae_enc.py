@@ -25,9 +25,12 @@ from .vae import Decoder3d, _split16
 class Encoder3d(Decoder3d):
     """reference: vae.py:265-374."""
 
-    def __init__(self, sd, dim, image_hw, device, conv16="split"):
-        self._setup(sd, "encoder.", image_hw, device, conv16)  # conv16 as in Decoder3d; _rep here: downsample3d's "first chunk has passed" (vae.py:146-149)
+    def __init__(self, sd, dim, image_hw, device, conv16="split", share=None):
+        self._setup(sd, "encoder.", image_hw, device, conv16, share)  # conv16 as in Decoder3d; _rep here: downsample3d's "first chunk has passed" (vae.py:146-149)
         self.dims, self.plan = synth.wan_vae_encoder_plan(dim)
+        if share is not None:  # another tile geometry of the same encoder (tiled_encode): the converted weights, the stride-2 and conv1 forms included
+            self.w_s2 = share.w_s2
+            return
         # the stride-2 kernel's weights: fp16 / split operands in 32-channel slabs, [Cout, 3, 3, Cs] (fp32 mode: the polyphase convolutions of _down2d)
         self.w_s2 = {}
         if conv16:
@@ -153,22 +156,20 @@ def encode_chunk_bounds(t, chunk_frames):
     return list(zip(edges[:-1], edges[1:]))
 
 
-def encode(model, x, scale, chunk_frames=None):
-    """WanVAE_.encode (vae.py:684-711) for vae.WanVAE_ `model`: x [1, 3, T, H, W] → mu [1, z_dim, 1 + (T - 1) // 4, H / 8, W / 8] fp32, normalised."""
+def _check_video(model, x, chunk_frames):
     if x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != 3:
         raise lib.X2VError(f"encode: expected a [1, 3, T, H, W] video, got {tuple(x.shape)}")
-    _, _, t, h, w = x.shape
     chunk_frames = model.encode_chunk_frames if chunk_frames is None else int(chunk_frames)
-    bounds = encode_chunk_bounds(t, chunk_frames)
-    sd = model.sd
-    if "encoder.conv1.weight" not in sd or "conv1.weight" not in sd:
+    bounds = encode_chunk_bounds(x.shape[2], chunk_frames)
+    if "encoder.conv1.weight" not in model.sd or "conv1.weight" not in model.sd:
         raise lib.X2VError("encode: the state dict holds no encoder (encoder.* / conv1.* tensors)")
-    enc = model.encoder
-    if enc is None or (enc.h0, enc.w0) != (h, w):
-        enc = model.encoder = Encoder3d(sd, model.dim, (h, w), model.device, conv16=model.conv16)
     video = x[0].to(device=model.device, dtype=torch.float32)
-    if video.stride(3) != 1:
-        video = video.contiguous()
+    return (video if video.stride(3) == 1 else video.contiguous()), bounds
+
+
+def _mu(model, enc, video, bounds, scale):
+    """Encoder passes over `video` [3, T, H, W] (a device view) + conv1 → normalised mu, channels-last [T_lat, H / 8, W / 8, z_dim]."""
+    sd = model.sd
     enc.clear_cache()
     outs = [enc.forward(video[:, a:b]) for a, b in bounds]
     enc.clear_cache()
@@ -183,7 +184,39 @@ def encode(model, x, scale, chunk_frames=None):
     bf = ((b1 - mean) * inv_std).contiguous()
     mu = torch.empty((tl, hl, wl, z2), dtype=torch.float32, device=model.device)
     lib.vae_conv(feat, (hl * wl * 2 * z2, wl * 2 * z2, 2 * z2), wf, mu, tl, hl, wl, bias=bf)
-    return mu.permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+    return mu
+
+
+def encode(model, x, scale, chunk_frames=None):
+    """WanVAE_.encode (vae.py:684-711) for vae.WanVAE_ `model`: x [1, 3, T, H, W] → mu [1, z_dim, 1 + (T - 1) // 4, H / 8, W / 8] fp32, normalised."""
+    video, bounds = _check_video(model, x, chunk_frames)
+    h, w = video.shape[2:]
+    enc = model.encoder
+    if enc is None or (enc.h0, enc.w0) != (h, w):
+        enc = model.encoder = Encoder3d(model.sd, model.dim, (h, w), model.device, conv16=model.conv16)
+    return _mu(model, enc, video, bounds, scale).permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+
+
+def tiled_encode(model, x, scale, chunk_frames=None):
+    """WanVAE_.tiled_encode (vae.py:568-629): every 256 x 256 px tile of the video (a strided view of the resident video, read in place by conv1's producer)
+    goes through the encoder of its geometry with a cleared cache, in the usual frame chunks; the tiles' normalised mu [T_lat, th, tw, z_dim] are blended
+    in latent units, cropped to the stride and stored channel-first by x2v_vae_tile_compose_f32 (no clamp).  H and W must be multiples of 8: the tile
+    starts are multiples of the 8-aligned stride, and a tile of fewer than 8 rows or columns has no latent."""
+    from .vae import compose_tiles, tile_plan
+
+    video, bounds = _check_video(model, x, chunk_frames)
+    _, t, h, w = video.shape
+    if h % 8 or w % 8:
+        raise lib.X2VError(f"tiled encode: the video's height and width must be multiples of 8, got {h}x{w}")
+    plan = tile_plan(h // 8, w // 8, *model.tile_geometry())
+    raw = []
+    for p in plan["tiles"]:
+        hw = (8 * p["th"], 8 * p["tw"])
+        enc = model._tile_module(Encoder3d, model._tile_encoders, model.encoder, (h, w), hw)
+        raw.append(_mu(model, enc, video[:, :, 8 * p["y0"] : 8 * p["y0"] + hw[0], 8 * p["x0"] : 8 * p["x0"] + hw[1]], bounds, scale))
+    out = torch.empty((1, model.z_dim, raw[0].shape[0], h // 8, w // 8), dtype=torch.float32, device=model.device)
+    compose_tiles(plan, raw, out[0])
+    return out
 
 
 def i2v_latent_hw(img_h, img_w, target_height, target_width, vae_stride, patch_size):
@@ -252,4 +285,4 @@ def encode_flops(t, h, w, dim=96, z_dim=16):
     return f
 
 
-__all__ = ["Encoder3d", "encode", "encode_chunk_bounds", "encode_flops", "i2v_first_frame_mask", "i2v_latent_hw", "i2v_video", "run_vae_encoder"]
+__all__ = ["Encoder3d", "encode", "tiled_encode", "encode_chunk_bounds", "encode_flops", "i2v_first_frame_mask", "i2v_latent_hw", "i2v_video", "run_vae_encoder"]

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--distill", action="store_true", help="4-step distilled schedule, no CFG (BASELINE config #4)")
     ap.add_argument("--vae16", action="store_true", help="fastest VAE decode: convolution operands rounded to fp16")
     ap.add_argument("--vae32", action="store_true", help="VAE convolutions on the fp32 matrix instruction (default: hi/lo fp16 split, fp32-grade)")
+    ap.add_argument("--tiling-vae", action="store_true", help='the reference configs\' "use_tiling_vae": WanVAE(use_tiling=True) — tiled decode (and encode with --image / --encode)')
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
@@ -88,7 +89,8 @@ def main():
     vae_sd = synth.synth_wan_vae_weights(dim=96, seed=0)
     if encode:  # one VAE state dict with both halves, as the released Wan2.1_VAE.pth
         vae_sd = {**vae_sd, **synth.synth_wan_vae_encoder_weights(dim=96, seed=0)}
-    decoder = vae.WanVAE(vae_sd, dim=96, conv16=(True if a.vae16 else False if a.vae32 else "split"), parallel=world > 1)
+    decoder = vae.WanVAE(vae_sd, dim=96, conv16=(True if a.vae16 else False if a.vae32 else "split"), parallel=world > 1,
+                         use_tiling=a.tiling_vae)
     if encode:
         from lightx2v_amd import clip, vae_enc
 
@@ -154,7 +156,7 @@ def main():
     assert torch.isfinite(video).all() and torch.isfinite(sch.latents).all()
     frames = wl["frames"]
     rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"ulysses-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
-           "teacache_thresh": a.teacache, "vae_conv_operands": "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
+           "teacache_thresh": a.teacache, "vae_conv_operands": "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "vae_tiling": bool(a.tiling_vae and world == 1), "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
            "frames": frames, "video_shape": list(video.shape), "fps_denoise_only": frames / (t1 - t0), "fps_with_vae": frames / (t2 - t0),
            "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}
     if encode:  # both conditioning tensors were built from the image here

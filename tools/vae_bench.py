@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Times WanVAE.decode (HIP path) on a synthetic latent of the BASELINE shape (720p x 81 frames: z [16,21,90,160]) and
 reports the convolution kernel's algorithmic TFLOP/s (2*T*H*W*Cout*Cin*taps per launch, summed over launches).
-    python tools/vae_bench.py [--latent 16,21,90,160] [--reps 1]"""
+    python tools/vae_bench.py [--latent 16,21,90,160] [--reps 1] [--tiled]
+--tiled adds, in the same process and on the same latent, the use_tiling decode (256 / 192 px tiles, WanVAE_.tiled_decode) with its peak memory, and times
+the one-pass tile composition (x2v_vae_tile_compose_f32) against the sequential blend_axis_ path on the same raw tiles: a second JSON line."""
 import argparse
 import json
 import os
@@ -21,6 +23,8 @@ def main():
     ap.add_argument("--conv16", action="store_true", help="opt-in fp16 convolution operands")
     ap.add_argument("--split", action="store_true", help="hi/lo fp16 split of the convolution operands (fp32-grade; WanVAE's default)")
     ap.add_argument("--chunk-frames", type=int, default=4, help="latent frames per decoder pass (1 = the reference's chunking)")
+    ap.add_argument("--tiled", action="store_true", help="also time the use_tiling decode and the tile composition (second JSON line)")
+    ap.add_argument("--tile-chunk-frames", default="none", help="--tiled: latent frames per decoder pass inside a tile, comma-separated values each timed in turn (none = the whole clip, WanVAE's default)")
     a = ap.parse_args()
     shape = tuple(int(v) for v in a.latent.split(","))
     lib.init(0)
@@ -57,6 +61,62 @@ def main():
     assert torch.isfinite(out).all()
     print(json.dumps({"workload": f"wan_vae_decode z{list(shape)} -> {list(out.shape)}", "conv_operands": "fp16 hi/lo split" if a.split else "fp16" if a.conv16 else "fp32", "chunk_frames": a.chunk_frames, "seconds": dt, "conv_tflop": f1 / 1e12, "tflops_per_s": f1 / dt / 1e12,
                       "frac_of_fp32_mfma_peak_157": f1 / dt / 1e12 / 157.3, "hbm_gb_allocated": torch.cuda.max_memory_allocated() / 1e9}))
+    if a.tiled:
+        vae.lib.vae_conv, vae.lib.vae_conv16 = orig, orig16
+        del m, out
+        torch.cuda.empty_cache()
+        for k in a.tile_chunk_frames.split(","):
+            print(json.dumps(tiled_leg(sd, z, a, dt, f1, None if k == "none" else int(k))))
+
+
+def compose_bytes(plan, t, c, scale):
+    """Bytes the composition has to move: every output value once out, and in the raw values it is made of (centre, and up / left / up-left inside the blend zones)."""
+    n = sum(2 * p["rh"] * p["rw"] + p["ev"] * p["rw"] + p["rh"] * p["eh"] + p["ev"] * p["eh"] for p in plan["tiles"])
+    return 4.0 * t * c * scale * scale * n
+
+
+def tiled_leg(sd, z, a, plain_s, plain_flop, tile_chunk_frames):
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    m = vae.WanVAE(sd, dim=96, conv16=("split" if a.split else a.conv16), use_tiling=True, tile_chunk_frames=tile_chunk_frames)
+    out = m.decode(z)  # warm-up: builds the (at most four) tile decoders and their buffers
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(a.reps, 2)):
+        t0 = time.perf_counter()
+        out = m.decode(z)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    assert torch.isfinite(out).all() and out.abs().max().item() <= 1.0
+    peak = (torch.cuda.max_memory_allocated() - base) / 1e9
+    _, t, h, w = z.shape
+    plan = vae.tile_plan(h, w, *m.model.tile_geometry())
+    t_out = out.shape[2]
+    px_tiles = sum(64 * p["th"] * p["tw"] for p in plan["tiles"])
+    # the composition alone, fused vs sequential, on raw tiles of the decode's shapes, alternating
+    g = torch.Generator(device="cuda").manual_seed(1)
+    raw = [torch.randn(t_out, 8 * p["th"], 8 * p["tw"], 3, device="cuda", generator=g) for p in plan["tiles"]]
+    seq_plan = dict(plan, mode="sequential")  # the in-place path takes any geometry (it blends the tiles it is given: values drift over the reps, the work does not)
+    img = torch.empty_like(out[0])
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    res = {"fused": [], "sequential": []}
+    for rep in range(6):
+        for name, pl in (("fused", plan), ("sequential", seq_plan)):
+            ev[0].record()
+            vae.compose_tiles(pl, raw, img, scale=8, clamp=True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if rep:  # the first pass of either is the warm-up
+                res[name].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    nbytes = compose_bytes(plan, t_out, 3, 8)
+    fused_s, seq_s = min(res["fused"]), min(res["sequential"])
+    dt = min(times)
+    return {"workload": f"wan_vae_tiled_decode z{list(z.shape)} -> {list(out.shape)}", "tiles": [plan["rows"], plan["cols"]], "tile_px": [m.model.tile_sample_min_height, m.model.tile_sample_stride_height],
+            "tile_chunk_frames": tile_chunk_frames, "seconds": dt, "seconds_all": times, "plain_seconds": plain_s, "ratio_to_plain": dt / plain_s, "pixel_ratio_tiles_to_image": px_tiles / (64.0 * h * w),
+            "plain_conv_tflop": plain_flop / 1e12, "hbm_gb_peak_tiled": peak, "compose_fused_s": fused_s, "compose_fused_s_all": res["fused"], "compose_sequential_s": seq_s,
+            "compose_sequential_s_all": res["sequential"], "compose_gb_moved": nbytes / 1e9, "compose_fused_tb_per_s": nbytes / fused_s / 1e12,
+            "compose_share_of_tiled_decode": fused_s / dt}
 
 
 if __name__ == "__main__":
