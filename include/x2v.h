@@ -420,7 +420,7 @@ int x2v_vae_prep_f32(const float* x, float* y, int T, int Hh, int Ww, int C, con
                      int64_t y_frame_stride, int64_t y_row_stride, void* stream);
 
 /* In-place s[M,N] = softmax(scale * s) rows, fp32 — the softmax of F.scaled_dot_product_attention in the VAE
- * AttentionBlock (vae.py:249-253).  N % 4 == 0. */
+ * AttentionBlock (vae.py:249-253).  N % 4 == 0; scale > 0 (the row maximum is taken before scaling; anything else, NaN included, is X2V_E_ARG). */
 int x2v_softmax_rows_f32(float* s, int64_t ld, int64_t M, int N, float scale, void* stream);
 
 /* ---- Wan VAE encoder (models/video_encoders/hf/wan/vae.py Encoder3d :265-374, WanVAE_.encode :684-711) ------------------------
@@ -512,7 +512,7 @@ int x2v_groupnorm_affine_f32(const float* x, int64_t npix, int C, int G, const f
 
 /* In-place s[M,N] = softmax(scale*s) over the frame-causal prefix: row i sees keys j < min(n_keys, (i/hw + 1)*hw), the
  * rest (incl. padding columns n_keys..N) becomes 0 (prepare_causal_attention_mask, unet_causal_3d_blocks.py:48-63, in
- * UNetMidBlockCausal3D.forward :629-634). */
+ * UNetMidBlockCausal3D.forward :629-634).  scale > 0 (the row maximum is taken before scaling; anything else, NaN included, is X2V_E_ARG). */
 int x2v_softmax_rows_causal_f32(float* s, int64_t ld, int64_t M, int N, float scale, int hw, int n_keys, void* stream);
 
 /* Linear cross-fade of overlapping tiles along one axis, tensors viewed as [outer][axis][inner]:

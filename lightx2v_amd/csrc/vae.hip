@@ -990,6 +990,7 @@ extern "C" __attribute__((visibility("default"))) int x2v_vae_prep_f32(const flo
 
 extern "C" __attribute__((visibility("default"))) int x2v_softmax_rows_f32(float* s, int64_t ld, int64_t M, int N, float scale, void* stream) {
   X2V_REQUIRE(s, X2V_E_ARG, "softmax_rows: null pointer");
+  X2V_REQUIRE(scale > 0.f, X2V_E_ARG, "softmax_rows: scale must be > 0 (the stabiliser is max(s) * scale)");
   X2V_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0 && ld >= N && M < (1ll << 31), X2V_E_SHAPE, "softmax_rows: bad shape (N %% 4 == 0)");
   X2V_REQUIRE(aligned16(s), X2V_E_ALIGN, "softmax_rows: 16-byte alignment");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, s, ld, M, N, scale);
@@ -1190,6 +1191,7 @@ extern "C" __attribute__((visibility("default"))) int x2v_groupnorm_affine_f32(c
 
 extern "C" __attribute__((visibility("default"))) int x2v_softmax_rows_causal_f32(float* s, int64_t ld, int64_t M, int N, float scale, int hw, int n_keys, void* stream) {
   X2V_REQUIRE(s, X2V_E_ARG, "softmax_rows_causal: null pointer");
+  X2V_REQUIRE(scale > 0.f, X2V_E_ARG, "softmax_rows_causal: scale must be > 0 (the stabiliser is max(s) * scale)");
   X2V_REQUIRE(M > 0 && N > 0 && hw > 0 && ld >= N && n_keys > 0 && n_keys <= N && M < (1ll << 31), X2V_E_SHAPE, "softmax_rows_causal: bad shape");
   hipLaunchKernelGGL(softmax_rows_causal_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, s, ld, N, scale, hw, n_keys);
   X2V_LAUNCH_CHECK("softmax_rows_causal launch");
