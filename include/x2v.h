@@ -521,6 +521,32 @@ int x2v_softmax_rows_causal_f32(float* s, int64_t ld, int64_t M, int N, float sc
 int x2v_blend_axis_f32(const float* a, float* b, int64_t outer, int na, int nb, int64_t inner, int64_t a_outer_stride, int64_t b_outer_stride, int extent,
                        void* stream);
 
+/* ---- Wan tiny VAE / TAEHV decoder (models/video_encoders/hf/tae.py, wan/vae_tiny.py), bf16, channels-last; see lightx2v_amd/csrc/taehv.hip ---- */
+
+#define X2V_C2D_RELU 1          /* ReLU behind everything else (nn.ReLU after a conv, MemBlock.act) */
+#define X2V_C2D_UPSAMPLE_READ 2 /* the operand is read at (h >> 1, w >> 1): nn.Upsample(scale_factor=2) in front of the convolution, never materialised; x is [T][(H+1)/2][(W+1)/2][Cin] */
+#define X2V_C2D_TWO_SOURCE 4    /* MemBlock's conv(cat([x_t, x_{t-1}], 1)): weights [Cout][k][k][2 Cin], channels Cin .. 2 Cin - 1 read frame t - 1 of x; frame -1 is `mem` or, mem NULL, zero */
+#define X2V_C2D_HEAD 8          /* v = RN(2 v - 1) behind the bias (WanVAE_tiny.decode's .mul_(2).sub_(1)) */
+
+/* 2-D convolution, k = ksize in {1, 3} with zero "same" padding, bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16, bf16 out; RN = one rounding to
+ * nearest even to bf16, as the reference's bf16 modules round:
+ *   acc[t,h,w,co] = sum_{s, dh, dw, c} X_s[t][(h + dh - k/2) >> u][(w + dw - k/2) >> u][c] * w[((co * k + dh) * k + dw) * Ctot + s * Cin + c]
+ *   X_0[t] = x + t * x_frame_stride, X_1[t] = X_0[t - 1] (X_1[0] = mem, or zero), X[..][r][q][c] = X + r * x_row_stride + q * x_px_stride + c; taps whose (h + dh - k/2,
+ *   w + dw - k/2) lies outside [0, H) x [0, W) read zero; u = 1 with X2V_C2D_UPSAMPLE_READ else 0; s < 2, Ctot = 2 Cin with X2V_C2D_TWO_SOURCE else s < 1, Ctot = Cin;
+ *   v = RN(acc + bias[co]) (bias optional);  resid: v = RN(v + resid[same offset as y]);  X2V_C2D_HEAD: v = RN(2 v - 1);  X2V_C2D_RELU: v = max(v, 0);
+ *   y[((t - frame_trim) * tsplit + co / Cb) * y_frame_stride + h * y_row_stride + w * y_px_stride + (co % Cb) * y_ch_stride] = v,  Cb = Cout / tsplit
+ * for t = frame_trim .. T - 1 (frames below frame_trim are neither computed nor stored).  tsplit > 1 is TGrow (tae.py:46-55): cout block j of frame t goes to
+ * frame tsplit * t + j.  A channel-first y (y_ch_stride != 1) is the output head's [3][T][H][W] store.
+ * Cin % 8 == 0 (% 32 with X2V_C2D_TWO_SOURCE), any Cout; x strides in elements, multiples of 8; x, mem, w 16-byte aligned; resid shares y's strides; no residual with tsplit > 1. */
+int x2v_conv2d_bf16(const void* x, const void* mem, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride, const void* w, const void* bias, const void* resid,
+                    void* y, int64_t y_frame_stride, int64_t y_row_stride, int64_t y_px_stride, int64_t y_ch_stride, int T, int H, int W, int Cin, int Cout, int ksize,
+                    int flags, int tsplit, int frame_trim, void* stream);
+
+/* Clamp (tae.py:19-21) from the caller's channel-first latent to the first convolution's channels-last operand:
+ *   y[((t * H + h) * W + w) * C + c] = RN(RN(tanh(RN(RN(z[c * c_stride + t * t_stride + h * W + w]) / 3))) * 3)
+ * z fp32 (z_is_f32 = 1; its RN is the reference's .to(bfloat16)) or bf16 (0); y bf16, 16-byte aligned; C % 8 == 0. */
+int x2v_taehv_clamp_bf16(const void* z, int z_is_f32, int64_t c_stride, int64_t t_stride, void* y, int T, int H, int W, int C, void* stream);
+
 /* ---- CLIP ViT-H/14 image tower (fp16): the producer of i2v's clip_encoder_out (runners/wan/wan_runner.py:191-198; the reference runs the tower in fp16,
  * :71-72).  fp16 tensors are raw IEEE half bits; LayerNorm parameters are fp32. ---- */
 

@@ -107,6 +107,9 @@ PROTOTYPES = {
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
     "x2v_blend_axis_f32": [_c_void_p, _c_void_p, _i64, _i32, _i32, _i64, _i64, _i64, _i32, _c_void_p],
+    "x2v_conv2d_bf16": [_c_void_p, _c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                        _c_void_p],
+    "x2v_taehv_clamp_bf16": [_c_void_p, _i32, _i64, _i64, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p],
 }
 _RESTYPES = {"x2v_last_error": ctypes.c_char_p, "x2v_version": ctypes.c_char_p}
 
@@ -1049,6 +1052,53 @@ def vae_replicate_border_(buf, lead, pad):
         c //= 2
     init()
     _check(_lib.x2v_vae_replicate_border_f32(_p(buf), frames, lead, hp, wp, c, pad, _stream()), "vae_replicate_border")
+
+
+C2D_RELU, C2D_UPSAMPLE_READ, C2D_TWO_SOURCE, C2D_HEAD = 1, 2, 4, 8  # x2v.h X2V_C2D_*
+
+
+def conv2d_bf16(x, weight, out, H, W, bias=None, resid=None, mem=None, flags=0, tsplit=1, frame_trim=0, out_strides=None):
+    """x2v_conv2d_bf16.  x: bf16 device VIEW [T, Hin, Win, Cin] with unit channel stride (Hin, Win = H, W, or their halves rounded up with C2D_UPSAMPLE_READ);
+    weight [Cout, k, k, Cin] (or [.., 2 Cin] with C2D_TWO_SOURCE) contiguous; mem: the frame in front of x[0] for the two-source form ([Hin, Win, Cin] in x's row and
+    pixel strides) or None (zero); out: bf16 device view whose first element is output frame 0, pixel (0, 0), channel 0, addressed by out_strides = (frame, row, pixel,
+    channel) in elements (default: a channels-last [T_out, H, W, Cout / tsplit] tensor's own); resid: bf16 view in out's strides."""
+    for t, name in ((x, "x"), (weight, "weight"), (out, "out"), (bias, "bias"), (resid, "resid"), (mem, "mem")):
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_cuda):
+            raise X2VError(f"conv2d_bf16 {name}: expected a bfloat16 device tensor, got {t.dtype} on {t.device}; the x2v HIP path has no CPU fallback")
+    if x.dim() != 4 or x.stride(3) != 1 or weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != weight.shape[2]:
+        raise X2VError(f"conv2d_bf16: x must be [T, H, W, C] with unit channel stride and weight a contiguous [Cout, k, k, C], got {tuple(x.shape)} {x.stride()} / {tuple(weight.shape)}")
+    T, Hin, Win, Cin = x.shape
+    Cout, k = weight.shape[0], weight.shape[1]
+    up = 1 if flags & C2D_UPSAMPLE_READ else 0
+    if weight.shape[3] != (2 if flags & C2D_TWO_SOURCE else 1) * Cin or (Hin, Win) != ((H + up) >> up, (W + up) >> up):
+        raise X2VError(f"conv2d_bf16: x {tuple(x.shape)} / weight {tuple(weight.shape)} / output {H} x {W} / flags {flags} disagree")
+    if mem is not None and (tuple(mem.shape) != (Hin, Win, Cin) or mem.stride() != x.stride()[1:]):
+        raise X2VError(f"conv2d_bf16: mem must be one frame in x's layout, got {tuple(mem.shape)} strides {mem.stride()}")
+    if bias is not None and (bias.numel() != Cout or not bias.is_contiguous()):
+        raise X2VError(f"conv2d_bf16: bias of {bias.numel()} elements for {Cout} output channels")
+    if out_strides is None:
+        if out.dim() != 4 or tuple(out.shape[1:]) != (H, W, Cout // tsplit) or out.shape[0] != (T - frame_trim) * tsplit:
+            raise X2VError(f"conv2d_bf16: out {tuple(out.shape)} is not [{(T - frame_trim) * tsplit}, {H}, {W}, {Cout // tsplit}]")
+        out_strides = out.stride()
+    if resid is not None and out_strides == tuple(out.stride()) and (resid.shape != out.shape or resid.stride() != out.stride()):
+        raise X2VError("conv2d_bf16: resid must have out's shape and strides")
+    ys = [int(s) for s in out_strides]
+    init()
+    _check(_lib.x2v_conv2d_bf16(_p(x), _p(mem), x.stride(0), x.stride(1), x.stride(2), _p(weight), _p(bias), _p(resid), _p(out), ys[0], ys[1], ys[2], ys[3], T, H, W, Cin, Cout,
+                                k, flags, tsplit, frame_trim, _stream()), "conv2d_bf16")
+    return out
+
+
+def taehv_clamp(z, out):
+    """x2v_taehv_clamp_bf16: z [C, T, h, w] fp32 or bf16 device tensor with contiguous rows -> out [T, h, w, C] contiguous bf16 = tanh(z / 3) * 3 in the reference's roundings."""
+    if z.dtype not in (torch.float32, torch.bfloat16) or not z.is_cuda or z.dim() != 4 or z.stride(3) != 1 or (z.shape[2] > 1 and z.stride(2) != z.shape[3]):
+        raise X2VError(f"taehv_clamp: expected a [C, T, h, w] float32 / bfloat16 device tensor with contiguous frames, got {z.dtype} {tuple(z.shape)} {z.stride()} on {z.device}")
+    C, T, h, w = z.shape
+    if out.dtype != torch.bfloat16 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (T, h, w, C):
+        raise X2VError(f"taehv_clamp: out must be a contiguous bfloat16 device tensor [{T}, {h}, {w}, {C}], got {out.dtype} {tuple(out.shape)}")
+    init()
+    _check(_lib.x2v_taehv_clamp_bf16(_p(z), int(z.dtype == torch.float32), z.stride(0), z.stride(1), _p(out), T, h, w, C, _stream()), "taehv_clamp")
+    return out
 
 
 def groupnorm_affine(x, groups, gamma, beta, eps=1e-6):

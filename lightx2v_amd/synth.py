@@ -381,6 +381,44 @@ def synth_wan_vae_weights(dim=96, z_dim=16, seed=0, device="cpu"):
     return sd
 
 
+TAEHV_WIDTHS = (256, 128, 64, 64)  # tae.py:191
+
+
+def synth_taehv_weights(seed=0, device="cpu"):
+    """Seeded bf16 weights of the TAEHV *decoder* under the released checkpoint's names (tae.py:193-217: decoder.1 / .8 / .14 / .20 / .22 the plain convolutions,
+    decoder.{3,4,5,9,10,11,15,16,17}.conv.{0,2,4} the MemBlocks, decoder.{7,13,19}.conv the TGrows, stored with stride 2 at 13 and 19 as the checkpoint has them).
+    He-style gains (not PyTorch's default init, under which the decoder's output is ~0.03 and nothing is tested): std = gain * sqrt(2 / fan_in) in front of a ReLU;
+    a MemBlock's last convolution is damped (gain 0.5) so that the three residual additions of a stage do not run away; the TGrows and the bias-free stage
+    convolutions keep the variance (sqrt(1 / fan_in)); the head lands the video at O(1).  tools/gen_golden_taehv.py asserts the output's standard deviation
+    (0.3 .. 3) and the positive share in front of every ReLU (20 % .. 80 %)."""
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(name, cout, cin, k, std, bias=True):
+        sd[f"{name}.weight"] = (torch.randn((cout, cin, k, k), generator=gen) * std).to(device=device, dtype=torch.bfloat16)
+        if bias:
+            sd[f"{name}.bias"] = (torch.randn((cout,), generator=gen) * 0.05).to(device=device, dtype=torch.bfloat16)
+
+    def he(fan):
+        return math.sqrt(2.0 / fan)
+
+    n = TAEHV_WIDTHS
+    conv("decoder.1", n[0], 16, 3, he(16 * 9) / 1.5)  # the Clamp output has a standard deviation of ~1.5 for latents drawn at x 2.5
+    idx = 3
+    for stage, stride in ((0, 1), (1, 2), (2, 2)):
+        c = n[stage]
+        for b in range(3):
+            p = f"decoder.{idx + b}.conv"
+            conv(p + ".0", c, 2 * c, 3, he(2 * c * 9))
+            conv(p + ".2", c, c, 3, he(c * 9))
+            conv(p + ".4", c, c, 3, 0.5 * he(c * 9))
+        conv(f"decoder.{idx + 4}.conv", c * stride, c, 1, math.sqrt(1.0 / c), bias=False)
+        conv(f"decoder.{idx + 5}", n[stage + 1], c, 3, (he(c * 9) if stage == 2 else math.sqrt(1.0 / (c * 9))), bias=False)
+        idx += 6
+    conv("decoder.22", 3, n[3], 3, 0.35 * math.sqrt(1.0 / (n[3] * 9)))
+    return sd
+
+
 def wan_vae_encoder_plan(dim=96, dim_mult=(1, 2, 4, 4), num_res_blocks=2, temperal_downsample=(False, True, True)):
     """Encoder3d.__init__ (vae.py:265-320): channel plan and the `downsamples` Sequential as (index, kind, in_dim, out_dim)."""
     dims = [dim * u for u in [1] + list(dim_mult)]

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--vae16", action="store_true", help="fastest VAE decode: convolution operands rounded to fp16")
     ap.add_argument("--vae32", action="store_true", help="VAE convolutions on the fp32 matrix instruction (default: hi/lo fp16 split, fp32-grade)")
     ap.add_argument("--tiling-vae", action="store_true", help='the reference configs\' "use_tiling_vae": WanVAE(use_tiling=True) — tiled decode (and encode with --image / --encode)')
+    ap.add_argument("--tiny-vae", action="store_true", help='the reference configs\' "tiny_vae": decode with WanVAE_tiny (TAEHV, lightx2v_amd/vae_tiny.py) instead of WanVAE; single GPU')
+    ap.add_argument("--tiny-vae-ckpt", default=None, help="--tiny-vae: the released taew2_1.pth (default: seeded synthetic weights)")
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
@@ -91,6 +93,13 @@ def main():
         vae_sd = {**vae_sd, **synth.synth_wan_vae_encoder_weights(dim=96, seed=0)}
     decoder = vae.WanVAE(vae_sd, dim=96, conv16=(True if a.vae16 else False if a.vae32 else "split"), parallel=world > 1,
                          use_tiling=a.tiling_vae)
+    encoder_vae = decoder  # the i2v conditioning is encoded by the full VAE in either case
+    if a.tiny_vae:  # WanRunner.load_vae_decoder (wan_runner.py:136-150): the tiny decoder replaces the full one on the decode side only
+        from lightx2v_amd import vae_tiny
+
+        if world > 1:
+            raise SystemExit("--tiny-vae: the tiny decoder has no multi-GPU form")
+        decoder = vae_tiny.WanVAE_tiny(a.tiny_vae_ckpt or synth.synth_taehv_weights(seed=0))
     if encode:
         from lightx2v_amd import clip, vae_enc
 
@@ -106,7 +115,7 @@ def main():
         enc_args = dict(target_height=8 * th, target_width=8 * tw, target_video_length=wl["frames"], vae_stride=cfg["vae_stride"], patch_size=cfg["patch_size"])
         if vae_enc.i2v_latent_hw(img.shape[1], img.shape[2], 8 * th, 8 * tw, cfg["vae_stride"], cfg["patch_size"]) != (th, tw):
             raise SystemExit(f"--image: a {img.shape[2]}x{img.shape[1]} image gives another latent grid than the workload's {tw}x{th} (use the workload's aspect ratio)")
-        vae_enc.run_vae_encoder(decoder, img, **enc_args)  # warm-up: allocates the encoder's buffers
+        vae_enc.run_vae_encoder(encoder_vae, img, **enc_args)  # warm-up: allocates the encoder's buffers
         clip.run_image_encoder(clip_model, img.cuda())
     if a.t5:
         from lightx2v_amd import t5
@@ -144,7 +153,7 @@ def main():
         inputs["image_encoder_output"]["clip_encoder_out"] = clip.run_image_encoder(clip_model, img.cuda())
         fence()
         tc = time.perf_counter()
-        inputs["image_encoder_output"]["vae_encode_out"] = vae_enc.run_vae_encoder(decoder, img, **enc_args)[0]
+        inputs["image_encoder_output"]["vae_encode_out"] = vae_enc.run_vae_encoder(encoder_vae, img, **enc_args)[0]
         fence()
     t0 = time.perf_counter()
     scheduler.run_denoise_loop(model, sch, inputs)
@@ -156,7 +165,7 @@ def main():
     assert torch.isfinite(video).all() and torch.isfinite(sch.latents).all()
     frames = wl["frames"]
     rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"ulysses-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
-           "teacache_thresh": a.teacache, "vae_conv_operands": "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "vae_tiling": bool(a.tiling_vae and world == 1), "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
+           "teacache_thresh": a.teacache, "vae_conv_operands": "bf16 (tiny VAE / TAEHV)" if a.tiny_vae else "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "tiny_vae": bool(a.tiny_vae), "vae_tiling": bool(a.tiling_vae and world == 1), "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
            "frames": frames, "video_shape": list(video.shape), "fps_denoise_only": frames / (t1 - t0), "fps_with_vae": frames / (t2 - t0),
            "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}
     if encode:  # both conditioning tensors were built from the image here

@@ -3,7 +3,11 @@
 reports the convolution kernel's algorithmic TFLOP/s (2*T*H*W*Cout*Cin*taps per launch, summed over launches).
     python tools/vae_bench.py [--latent 16,21,90,160] [--reps 1] [--tiled]
 --tiled adds, in the same process and on the same latent, the use_tiling decode (256 / 192 px tiles, WanVAE_.tiled_decode) with its peak memory, and times
-the one-pass tile composition (x2v_vae_tile_compose_f32) against the sequential blend_axis_ path on the same raw tiles: a second JSON line."""
+the one-pass tile composition (x2v_vae_tile_compose_f32) against the sequential blend_axis_ path on the same raw tiles: a second JSON line.
+    python tools/vae_bench.py --tiny [--tiny-latents "16,21,90,160;16,21,60,104"] [--out profiles/taehv_bench.json]
+--tiny measures the tiny VAE (TAEHV, lightx2v_amd/vae_tiny.py) instead: per latent shape the HIP decode of the whole clip and with chunk_frames=4 (with peak memory),
+the full Wan decode (this tool's default leg) in the same process, and the same TAEHV graph through plain PyTorch bf16 on the same GPU (tests/taehv_restatement.py on
+F.conv2d, whole clip), with the box calibration (lib.mfma_probe) before and after; one JSON document, printed and written to --out."""
 import argparse
 import json
 import os
@@ -25,7 +29,13 @@ def main():
     ap.add_argument("--chunk-frames", type=int, default=4, help="latent frames per decoder pass (1 = the reference's chunking)")
     ap.add_argument("--tiled", action="store_true", help="also time the use_tiling decode and the tile composition (second JSON line)")
     ap.add_argument("--tile-chunk-frames", default="none", help="--tiled: latent frames per decoder pass inside a tile, comma-separated values each timed in turn (none = the whole clip, WanVAE's default)")
+    ap.add_argument("--tiny", action="store_true", help="measure the tiny VAE (TAEHV) against the full decode and plain PyTorch bf16")
+    ap.add_argument("--tiny-latents", default="16,21,90,160;16,21,60,104", help="--tiny: latent shapes, ';'-separated (720p x 81f; 480p x 81f)")
+    ap.add_argument("--tiny-legs", default="hip,full,torch", help="--tiny: which legs to run")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "taehv_bench.json"))
     a = ap.parse_args()
+    if a.tiny:
+        return tiny_main(a)
     shape = tuple(int(v) for v in a.latent.split(","))
     lib.init(0)
     sd = synth.synth_wan_vae_weights(dim=96, seed=0)
@@ -67,6 +77,88 @@ def main():
         torch.cuda.empty_cache()
         for k in a.tile_chunk_frames.split(","):
             print(json.dumps(tiled_leg(sd, z, a, dt, f1, None if k == "none" else int(k))))
+
+
+def _timed(fn, reps):
+    """Warm-up call, then `reps` calls timed one by one with a device synchronisation behind each -> (last result, seconds each)."""
+    out = fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return out, times
+
+
+def tiny_main(a):
+    from lightx2v_amd import vae_tiny
+    from tests import taehv_restatement as R
+
+    lib.init(0)
+    legs = a.tiny_legs.split(",")
+    reps = max(a.reps, 3)
+    sd = synth.synth_taehv_weights(seed=0)
+    doc = {"tool": "tools/vae_bench.py --tiny", "weights": "synth.synth_taehv_weights(seed=0)", "reps": reps, "timing": "wall clock around decode + synchronize, warm-up outside; min and all reps",
+           "box_calibration": {"kernel": "v_mfma_f32_16x16x32_bf16 (x2v_mfma_probe_bf16)", "mfma_probe_tflops_before": lib.mfma_probe(500)}, "shapes": []}
+    flops = [0.0]
+    orig = lib.conv2d_bf16
+
+    def counted(x, weight, out, H, W, **kw):
+        flops[0] += 2.0 * (x.shape[0] - kw.get("frame_trim", 0)) * H * W * weight.numel()
+        return orig(x, weight, out, H, W, **kw)
+
+    for spec in a.tiny_latents.split(";"):
+        shape = tuple(int(v) for v in spec.split(","))
+        z = (torch.randn(*shape, generator=torch.Generator().manual_seed(5)) * 2.5).cuda()
+        rec = {"latent": list(shape)}
+        if "hip" in legs:
+            for name, chunk in (("hip_whole_clip", None), ("hip_chunk_frames_4", 4)):
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                m = vae_tiny.WanVAE_tiny(sd, chunk_frames=chunk)
+                vae_tiny.lib.conv2d_bf16, flops[0] = counted, 0.0
+                m.decode(z)
+                vae_tiny.lib.conv2d_bf16 = orig
+                out, times = _timed(lambda: m.decode(z), reps)
+                assert torch.isfinite(out.float()).all()
+                rec[name] = {"seconds": min(times), "seconds_all": times, "conv_tflop": flops[0] / 1e12, "tflops_per_s": flops[0] / min(times) / 1e12,
+                             "hbm_gb_peak": (torch.cuda.max_memory_allocated() - base) / 1e9, "video": list(out.shape)}
+                del m, out
+        if "full" in legs:
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            full = vae.WanVAE(synth.synth_wan_vae_weights(dim=96, seed=0), dim=96, conv16="split", chunk_frames=4)
+            zf = torch.randn(*shape, generator=torch.Generator().manual_seed(5)).cuda()
+            out, times = _timed(lambda: full.decode(zf), 1 if shape[1] * shape[2] * shape[3] > 100000 else reps)
+            rec["full_wan_vae_split_chunk4"] = {"seconds": min(times), "seconds_all": times, "hbm_gb_peak": (torch.cuda.max_memory_allocated() - base) / 1e9}
+            del full, out, zf
+        if "torch" in legs:
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            sdg = {k: v.cuda() for k, v in sd.items()}
+            try:
+                out, times = _timed(lambda: R.wan_decode(sdg, z), reps)
+                rec["torch_bf16_f_conv2d_whole_clip"] = {"seconds": min(times), "seconds_all": times, "hbm_gb_peak": (torch.cuda.max_memory_allocated() - base) / 1e9}
+                del out
+            except RuntimeError as e:  # reported as it comes out (an out-of-memory or a MIOpen refusal at this size is a result)
+                rec["torch_bf16_f_conv2d_whole_clip"] = {"error": str(e)[:300]}
+        if "hip_whole_clip" in rec and "full_wan_vae_split_chunk4" in rec:
+            rec["tiny_over_full"] = rec["hip_whole_clip"]["seconds"] / rec["full_wan_vae_split_chunk4"]["seconds"]
+        if "hip_whole_clip" in rec and "seconds" in rec.get("torch_bf16_f_conv2d_whole_clip", {}):
+            rec["hip_over_torch"] = rec["hip_whole_clip"]["seconds"] / rec["torch_bf16_f_conv2d_whole_clip"]["seconds"]
+        doc["shapes"].append(rec)
+        print(json.dumps(rec), flush=True)
+    doc["box_calibration"]["mfma_probe_tflops_after"] = lib.mfma_probe(500)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc))
 
 
 def compose_bytes(plan, t, c, scale):
