@@ -467,9 +467,10 @@ int x2v_vae_prep_ex_f32(const float* x, float* y, int T, int Hh, int Ww, int C, 
  * are fp16 (strides in halves, Cin % 64 == 0), accumulation fp32 on v_mfma_f32_32x32x16_f16, bias / residual / output fp32 — the residual
  * stream and the normalisation statistics keep fp32, only the convolution operands are rounded.  Same flags and layouts as the fp32 entry, plus
  * 4 = the per-tap kernel and 8 = the 64-pixel halo kernel (kernel choice for A/B runs and tests: by default 3x3 kernels on images at least 16 pixels wide
- * with Cin % 32 == 0 and Cout % 96 == 0, Cout % 128 == 0 or Cout <= 16 take the 128-pixel kernel on v_mfma_f32_16x16x32_f16, whose reduction order differs in
- * rounding; other 3x3 kernels at least 16 pixels wide the 64-pixel halo kernel; everything else the per-tap kernel) and 16 = the last 32 channels of Cin
- * are zero padding in both operands (skipped where the kernel steps in 32 channels; a no-op for the results). */
+ * with Cin % 32 == 0 and Cout % 96 == 0, Cout % 128 == 0 or Cout <= 16, without the time-split, take the 128-pixel kernel on v_mfma_f32_16x16x32_f16, whose
+ * reduction order differs in rounding; other 3x3 kernels at least 16 pixels wide, without the time-split, the 64-pixel halo kernel — in the released models the
+ * Wan encoder's 32-cout head alone; everything else the per-tap kernel) and 16 = the last 32 channels of Cin are zero padding in both operands (the 128-pixel
+ * kernel, which steps in 32 channels, skips them; a no-op for the results). */
 int x2v_vae_conv_f16(const void* xp, int64_t x_frame_stride, int64_t x_row_stride, int64_t x_px_stride, const void* w, int64_t w_row_stride, const float* bias,
                      const float* resid, float* y, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags, void* stream);
 

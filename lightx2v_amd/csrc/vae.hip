@@ -609,9 +609,9 @@ __global__ __launch_bounds__(256) void tile_compose_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------
 // Halo-tiled form of the 16-bit convolution for 3x3 spatial kernels (kt = 1 or 3), 64 pixels per wave.  What still reaches it: by default the 3x3
 // convolutions at least 16 pixels wide whose Cout the 128-pixel kernel of vae16g.hip does not take (vae_conv16g_ok: Cout neither a multiple of 96 or
-// 128 nor <= 16) — at the released widths that is the Wan encoder's head alone (384 -> 32 couts, vae_enc.py); a kernel trace of the encoder tests
-// (profiles/vae_conv_refactor_isa.txt) shows NF = 1 for that head and for the 32-cout convolutions of the tests' dim-32 model, NF = 2 for that model's
-// 64-cout ones, and no NF = 3 / 4 launch — and any 3x3 shape on request (flag 8 of x2v_vae_conv_f16: the tests' cross-check of the 128-pixel kernel).
+// 128 nor <= 16) — in the released models that is the Wan encoder's head alone (384 -> 32 couts, vae_enc.py; tests/test_vae_conv_ref_host.py pins it), the
+// tests' dim-32 model adds 32- and 64-cout ones — and any 3x3 shape on request (flag 8 of x2v_vae_conv_f16: the tests' cross-check of the 128-pixel kernel).
+// It stays for that head: on the per-tap kernel the head takes 441 us instead of 214 and the tiled 720p encode 2.7 % longer (profiles/vae_halo64_retire_encode_abab.txt).
 // The per-tap kernel stages a fresh 256-pixel input block for every tap — 48 KB from the L2 per 4.2 MFLOP, and the PMC profile shows it pinned at the
 // L2's aggregate request rate (11 TB/s, matrix pipe 32 % busy).  Here a workgroup owns an 8 x 32 pixel tile of one output frame and stages, per input
 // frame tap dt and 64-channel slab, the 10 x 34 pixel HALO block once (44 KB); the nine spatial taps then read their shifted

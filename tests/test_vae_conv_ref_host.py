@@ -115,6 +115,67 @@ def test_dispatch_restated():
     assert all(V.cached_ok(sp) for sp in V.HALO128_CACHED)
 
 
+def test_dispatch_of_the_released_vaes():
+    """Every 16-bit 3x3 convolution of the Wan decoder and encoder (dim 96, split operands: 3 C planes in a 64-channel-padded pixel, vae.py Decoder3d._setup)
+    and of the HunyuanVideo decoder (fp16 operands, hunyuan_vae.py) at the 720p widths of its stage takes the 128-pixel body — but the Wan encoder's head
+    (384 -> 32 couts), the one launch of the 64-pixel body in a released model."""
+    from lightx2v_amd import synth
+
+    W0 = 1280 // 8  # the latent's width
+    split = lambda c: (3 * c + 63) // 64 * 64
+    convs = []  # (name, W, Cin of the operand buffer, Cout, k)
+
+    def wan_res(name, w, cin, cout):
+        convs.extend([(name + "residual.2", w, split(cin), cout, (3, 3, 3)), (name + "residual.6", w, split(cout), cout, (3, 3, 3))])
+
+    dims, plan = synth.wan_vae_decoder_plan(96)  # conv1 (Cin = 16) is an fp32 convolution
+    w = W0
+    for m in (0, 2):
+        wan_res(f"decoder.middle.{m}.", w, dims[0], dims[0])
+    for idx, kind, cin, cout in plan:
+        if kind == "res":
+            wan_res(f"decoder.upsamples.{idx}.", w, cin, cout)
+        else:  # nearest upsampling, then a 3x3 convolution per frame (the time_conv is 3x1x1)
+            w *= 2
+            convs.append((f"decoder.upsamples.{idx}.resample.1", w, split(cin), cin // 2, (1, 3, 3)))
+    convs.append(("decoder.head.2", w, split(dims[-1]), 3, (3, 3, 3)))
+    assert w == 1280
+
+    dims, plan = synth.wan_vae_encoder_plan(96)
+    convs.append(("encoder.conv1", w, 64, dims[0], (3, 3, 3)))
+    for idx, kind, cin, cout in plan:
+        if kind == "res":
+            wan_res(f"encoder.downsamples.{idx}.", w, cin, cout)
+        else:  # the stride-2 kernel (and a 3x1x1 time_conv)
+            w //= 2
+    for m in (0, 2):
+        wan_res(f"encoder.middle.{m}.", w, dims[-1], dims[-1])
+    head = ("encoder.head.2", w, split(dims[-1]), 32, (3, 3, 3))
+    convs.append(head)
+    assert w == W0
+
+    def hy_res(name, w, cin, cout):
+        convs.extend([(name + "conv1", w, cin, cout, (3, 3, 3)), (name + "conv2", w, cout, cout, (3, 3, 3))])
+
+    cfg = synth.HUNYUAN_VAE_CFG  # conv_in (Cin = 16) is an fp32 convolution
+    top = cfg["block_out_channels"][-1]
+    for m in (0, 1):
+        hy_res(f"decoder.mid_block.resnets.{m}.", w, top, top)
+    for i, (cin, cout, _, fhw, has_up) in enumerate(synth.hunyuan_vae_up_plan(cfg)):
+        for j in range(cfg["layers_per_block"] + 1):
+            hy_res(f"decoder.up_blocks.{i}.resnets.{j}.", w, cin if j == 0 else cout, cout)
+        if has_up:
+            w *= fhw
+            convs.append((f"decoder.up_blocks.{i}.upsamplers.0", w, cout, cout, (3, 3, 3)))
+    convs.append(("decoder.conv_out", w, cfg["block_out_channels"][0], 3, (3, 3, 3)))
+    assert w == 1280
+
+    assert len(convs) == (2 * 14 + 3 + 1) + (1 + 2 * 10 + 1) + (2 * 14 + 3 + 1)  # residual blocks x 2, upsamplers, conv1 / heads
+    bodies = {c[0]: V.body_of("f16", *c[1:], 0) for c in convs if c is not head}
+    assert set(bodies.values()) == {"halo128 NCB6", "halo128 NCB8", "halo128 NCB1"}, {n: b for n, b in bodies.items() if not b.startswith("halo128")}
+    assert all(c[2] % 64 == 0 for c in convs) and V.body_of("f16", *head[1:], 0) == "halo64 NF1"
+
+
 def test_family_i_premises_and_emulations_at_the_largest_k():
     for sp in V.ALL_SPECS:
         inputs("I", sp).assert_premises()
