@@ -340,7 +340,11 @@ int x2v_gemm_int8_kernel_choice(int64_t M, int N, int K, int64_t ldx, int64_t ld
  * elements one e8m0 scale = the smallest power of two >= max|x|/448, elements = e4m3fn_rne(x / scale).
  * x bf16 [M,K]; q bytes [M,K] (ld = ldq); scales: bytes [K/128][M][4] — K-tile major, row, the 4 k blocks of that K-tile: the
  * layout x2v_gemm_mxfp8 consumes (as the reference's 128x4 swizzle is the sm120 tensor core's; logical element (m, kb) sits at
- * ((kb/4)*M + m)*4 + kb%4).  K % 128 == 0. */
+ * ((kb/4)*M + m)*4 + kb%4).  K % 128 == 0.
+ * NaN and Inf elements are outside the contract of their own 32-wide block and leave every other block's codes and scale byte as they
+ * are with 0 in the element's place (tests/test_gpu_mx_fp64.py); measured, not promised: a NaN is skipped by the block maximum (the
+ * scale byte and the other 31 codes are those with 0 in its place) and becomes a NaN code (0x7f / 0xff), an Inf gives scale byte 254,
+ * code 0x7f and +/-0 for the other 31 (profiles/mx_fp64_parity.txt). */
 int x2v_quant_mxfp8_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t M, int K, void* stream);
 
 /* y[M,N] = alpha * (deq(a)[M,K] . deq(b)[N,K]^T) + bias[n] → bf16, deq = e4m3 element * 2^(scale byte - 127) of its row and

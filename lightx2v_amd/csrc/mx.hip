@@ -10,8 +10,9 @@
 // line per load instead of 32 with a row-major [rows][K/32] table: 1.6-1.85 -> 2.4-2.7 PFLOP/s on the 14B shapes, profiles/r01_mxfp8_*).
 //
 // quant: HBM-bound — reads M*K bf16, writes M*K bytes + M*K/32 scale bytes (algorithmic bytes 3.03 per element).
-// GEMM:  MFMA-bound — 2*M*N*K FLOP per launch against the 5 PFLOP/s fp8 peak; the 128x128-tile / two-barrier structure of gemm.hip
-//        (first MX version: correctness and the instruction's data path; the 256x256 ping-pong form of gemm256.hip is the next step).
+// GEMM:  MFMA-bound — 2*M*N*K FLOP per launch against the 5 PFLOP/s fp8 peak.  Two bodies: gemm_mxfp8_kernel below, the 128x128-tile /
+//        two-barrier structure of gemm.hip (small shapes), and the MX instantiation of gemm256.hip's 256x256 ping-pong kernel (shapes that
+//        fill the chip, and every call with a fused epilogue); gemm_mxfp8_impl chooses.
 #include "x2v_common.h"
 
 namespace x2v {

@@ -12,6 +12,8 @@ tests hold no golden vectors for them — only the acceptance bound `error(mm_pr
 (lightx2v_kernel/test/mxfp8_mxfp8/test_mxfp8_quant.py:37), which tests/test_gpu_mx.py applies to the HIP path at the same shapes.
 One documented divergence: for an all-zero block the CUDA code multiplies 0 by rcp.approx.ftz(2^-127) = inf and stores NaN bytes; here
 (and in the HIP kernel) such a block is zero elements with scale byte 0.
+Non-finite inputs: quant_mxfp8's `amax` propagates a NaN into the block maximum, where the HIP kernel's fmaxf and the reference's __hmax2
+ignore it; the oracle agrees with the kernel on finite inputs only (include/x2v.h puts NaN / Inf elements outside the contract of their block).
 """
 import numpy as np
 import torch

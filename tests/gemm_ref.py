@@ -217,15 +217,15 @@ class Reject(AssertionError):
 class Case:
     """The checks of one test: (shape, body, epilogue, rule, largest d/tol or number of unequal elements, elements compared)."""
 
-    def __init__(self, name, record=True):
-        self.name, self.record, self.rows = name, record, []
+    def __init__(self, name, record=True, prefix="gemm_fp64"):
+        self.name, self.record, self.rows, self.prefix = name, record, [], prefix
 
     def _row(self, exp, body, rule, worst, n):
         self.rows.append((exp.inp.name, body, exp.what, rule, worst, n))
         if self.record:
             from tests.util import record as rec
 
-            rec(f"gemm_fp64 {self.name} {exp.inp.name} {body} {exp.what}", rule=rule, worst=worst, elements=n)
+            rec(f"{self.prefix} {self.name} {exp.inp.name} {body} {exp.what}", rule=rule, worst=worst, elements=n)
 
     def check(self, got, exp, body=""):
         return self.check_exact(got, exp, body) if exp.inp.family == "I" else self.check_bound(got, exp, body)
@@ -297,7 +297,6 @@ def emulate(inp, epi, use_bias=True, use_gate=True, period=0, chunk=0, mut=None)
     mut: one of R_MUTATIONS / I_MUTATIONS — a subtly WRONG kernel, for the host module's rejection tests.  Returns bf16 [M, N]."""
     x, w = inp.x.to(F32), inp.w.to(F32)
     bias, gate, resid = inp.bias.to(F32), inp.gate.to(F32), inp.resid_rows(period).to(F32)
-    rnd = "half_up" if mut == "half_up" else "trunc" if mut == "truncate" else "rne"
     if mut == "drop_k":
         x = x.clone()
         x[:, inp.K // 2 + 1] = 0
@@ -323,7 +322,15 @@ def emulate(inp, epi, use_bias=True, use_gate=True, period=0, chunk=0, mut=None)
         acc = acc * inp.sx[:, None] * inp.sw[None, :]
     if mut == "acc_bf16":
         acc = _r32(acc)
-    y = _r32(acc + bias if use_bias else acc, rnd)
+    return finish(acc + bias if use_bias else acc, epi, gate if use_gate else None, resid, mut)
+
+
+def finish(t32, epi, gate=None, resid=None, mut=None):
+    """The epilogue of a correct kernel from t32 = the fp32 value in front of the first rounding (emulate's, and tests/mx_ref.py's for the MXFP8
+    bodies): the contract's roundings around the kernels' fp32 activations.  gate, resid: fp32, or None.  mut as in emulate.  Returns bf16."""
+    rnd = "half_up" if mut == "half_up" else "trunc" if mut == "truncate" else "rne"
+    use_gate = gate is not None
+    y = _r32(t32, rnd)
     if epi == EPI_GELU:
         u = 0.7978845608028654 * (y + 0.044715 * y * y * y)
         y = _r32(y / (1.0 + torch.exp(-2.0 * u)), rnd)
