@@ -1,7 +1,8 @@
 // y[M,N] = epi(x[M,K] . W[N,K]^T + bias) — bf16 (or w8a8 e4m3fn) in, fp32 MFMA accumulate, bf16 out.
 // The fp8 variant shares the whole structure: a 128-byte operand row per stage is 64 bf16 or 128 fp8 k-values;
 // it issues v_mfma_scale_f32_32x32x64_f8f6f4 with unit (2^0) block scales — the only fp8 MFMA that runs at
-// the 2x rate on gfx950 — and applies the per-token x per-channel fp32 scales in the epilogue.
+// the 2x rate on gfx950 — and applies the per-token x per-channel fp32 scales in the epilogue.  Its MX mode (MXFP8, mx.hip's small shapes) hands
+// the same instruction the operands' own e8m0 block scales and multiplies by alpha in the epilogue.
 //
 // Bound: MFMA (bf16 dense peak ~2.5 PFLOP/s); algorithmic work 2*M*N*K FLOP per launch.
 //
@@ -44,12 +45,16 @@ __device__ __forceinline__ int swz_off(int r, int c) { return r * 128 + ((c ^ ((
 
 // I8 (with FP8 = true: the w8a8 operand and scale plumbing): int8 codes on v_mfma_i32_32x32x32_i8, four k-steps of 32 per 128-byte stage row, an
 // exact int32 accumulator converted to fp32 (v_cvt_f32_i32, round to nearest even) in front of the dequantisation.
-template <bool FP8, int EPI, bool I8>
+// MX (with FP8 = true, I8 = false: MXFP8, mx.hip): y = alpha * (A . W^T) + bias with per-(row, 32-k) e8m0 block scales applied by the MFMA; SA / SB are
+// the scale tables [K/128][rows] of one dword per operand row and K-tile, `sx` carries the device pointer to alpha (or null), `sw` is unused.
+template <bool FP8, int EPI, bool I8, bool MX = false>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                       const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
                                                       int N, int nk, const unsigned short* __restrict__ resid, int64_t ldr,
                                                       const unsigned short* __restrict__ gate, const float* __restrict__ sx,
-                                                      const float* __restrict__ sw, int ntm, int ntn, GemmBlocking gb) {
+                                                      const float* __restrict__ sw, int ntm, int ntn, GemmBlocking gb,
+                                                      const unsigned* __restrict__ SA, const unsigned* __restrict__ SB) {
+  static_assert(!MX || (FP8 && !I8), "MX: block-scaled fp8");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int a_kpb = gb.a_kpb > 0 && gb.a_kpb < nk ? gb.a_kpb : nk;
   const int tid = threadIdx.x;
@@ -88,7 +93,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
     char* as = smem + s * G_STAGE_BYTES + wid * (32 * 128);
     char* bs = as + GB_M * 128;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) glds16(a_src[i] + ((int64_t)(kt / a_kpb) * gb.a_cbs + (int64_t)(kt % a_kpb) * G_ROW_BYTES), as + i * 1024);  // K-blocked x
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (MX) glds16(a_src[i] + (int64_t)kt * G_ROW_BYTES, as + i * 1024);  // MXFP8 never passes blocked operands; the arithmetic below costs it 2 % at K = 13824
+      else glds16(a_src[i] + ((int64_t)(kt / a_kpb) * gb.a_cbs + (int64_t)(kt % a_kpb) * G_ROW_BYTES), as + i * 1024);  // K-blocked x
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(b_src[i] + (int64_t)kt * G_ROW_BYTES, bs + i * 1024);
   };
@@ -98,15 +106,48 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
   const int fl = lane & 31, fh = lane >> 5;
   // chunk order: bf16 step ks (K=16) and int8 step ks (K=32) read chunk ks*2+fh; fp8 step s (K=64) reads chunks s*4+fh*2+{0,1}.
   // In both cases A and B use the same (half-wave, element) -> k map, which is all an MFMA requires.
+  // MX: fragment chunks in the instruction's own k order (it matters once the hardware applies block scales; probed with
+  // tools/x2v_check-style unit tests, see tests/test_gpu_mx.py): of a lane's 32 bytes the first 16 are k = fh*16 .. +15 (scale block 0
+  // of the 64-wide step), the last 16 are k = 32 + fh*16 .. +15 (block 1); block b takes its scale from the lanes of half b.
+  // MFMA s of the K-tile therefore reads 16-byte chunks s*4 + fh and s*4 + 2 + fh.
   int a_off[2][4], b_off[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int c = (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
+      const int c = MX ? ((ks >> 1) * 4 + (ks & 1) * 2 + fh) : (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
       a_off[i][ks] = swz_off(wr * 64 + i * 32 + fl, c);
       b_off[i][ks] = swz_off(wc * 64 + i * 32 + fl, c) + GB_M * 128;
     }
+  // MX block scales: one dword per operand row and K-tile = the 4 scale bytes of its k blocks.  The instruction takes byte `opsel` of the
+  // scale VGPR of every lane; lanes fh = 1 (k block s*2 + 1) shift their dword down by one byte so that opsel = 2 s serves both halves.
+  // The dwords of a K-tile are loaded with its stage (sa_nxt / sb_nxt) and adopted, shifted, at the top of the iteration that multiplies it.
+  const unsigned* sa_row[2];
+  const unsigned* sb_row[2];
+  const int sh = fh * 8;
+  unsigned sa_cur[2], sb_cur[2], sa_nxt[2], sb_nxt[2];
+  if constexpr (MX) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int64_t gm = m0 + wr * 64 + i * 32 + fl;
+      gm = gm < M ? gm : M - 1;
+      int gn = n0 + wc * 64 + i * 32 + fl;
+      gn = gn < N ? gn : N - 1;
+      sa_row[i] = SA + gm;  // [K-tile][row] dwords
+      sb_row[i] = SB + gn;
+      sa_nxt[i] = sa_row[i][0];
+      sb_nxt[i] = sb_row[i][0];
+    }
+  }
+  // The wait that ends a stage's loads.  MX names the scale dwords as its operands: the compiler does not read the instruction in the string, and
+  // with the loads still pending in its own book-keeping it put a vmcnt(0) of its own in front of their first use, behind the NEXT stage's DMA issue
+  // (+6..+32 % time at the shapes of profiles/gemm128_mx_merge.txt).
+  auto wait_loads = [&] {
+    if constexpr (MX)
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(sa_nxt[0]), "+v"(sa_nxt[1]), "+v"(sb_nxt[0]), "+v"(sb_nxt[1])::"memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
 
   std::conditional_t<I8, i32x16_t, f32x16_t> acc[2][2];
 #pragma unroll
@@ -117,11 +158,27 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
 
   stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_loads();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
+    if constexpr (MX) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        sa_cur[i] = sa_nxt[i] >> sh;
+        sb_cur[i] = sb_nxt[i] >> sh;
+      }
+    }
+    if (kt + 1 < nk) {
+      stage(cur ^ 1, kt + 1);
+      if constexpr (MX) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          sa_nxt[i] = sa_row[i][(int64_t)(kt + 1) * M];
+          sb_nxt[i] = sb_row[i][(int64_t)(kt + 1) * N];
+        }
+      }
+    }
     const char* base = smem + cur * G_STAGE_BYTES;
     if constexpr (!FP8) {
 #pragma unroll
@@ -165,14 +222,21 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
           wb[i] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
         constexpr int kOne = 0x7f7f7f7f;  // e8m0 2^0 block scales
+        // first matrix operand = W (weight) fragment, second = A (activation) fragment: the accumulator's lane index is the output row
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, kOne, 0, kOne);
+          for (int j = 0; j < 2; ++j) {
+            if constexpr (!MX)
+              acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, kOne, 0, kOne);
+            else if (s2 == 0)
+              acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, (int)sb_cur[j], 0, (int)sa_cur[i]);
+            else
+              acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 2, (int)sb_cur[j], 2, (int)sa_cur[i]);
+          }
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_loads();
     __syncthreads();
   }
 
@@ -190,9 +254,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
       gn = gn + 3 < N ? gn : (N >= 4 ? N - 4 : 0);
       bv[j][g] = make_uint2(0u, 0u);
       if (bias != nullptr) bv[j][g] = *reinterpret_cast<const uint2*>(bias + gn);
-      if constexpr (FP8) swv[j][g] = *reinterpret_cast<const float4*>(sw + gn);
+      if constexpr (FP8 && !MX) swv[j][g] = *reinterpret_cast<const float4*>(sw + gn);
     }
-  if constexpr (FP8) {
+  float mx_alpha = 1.0f;
+  if constexpr (MX) {
+    if (sx != nullptr) mx_alpha = *sx;  // MX: `sx` carries the device pointer to alpha (x2v_gemm_mxfp8)
+  } else if constexpr (FP8) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int64_t gm = m0 + wr * 64 + i * 32 + fl;
@@ -211,23 +278,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
         float vv[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) vv[e] = (float)acc[i][j][4 * g + e];
-        if constexpr (FP8) {
+        if constexpr (MX) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) vv[e] *= mx_alpha;
+        } else if constexpr (FP8) {
           vv[0] = vv[0] * sxv[i] * swv[j][g].x;
           vv[1] = vv[1] * sxv[i] * swv[j][g].y;
           vv[2] = vv[2] * sxv[i] * swv[j][g].z;
           vv[3] = vv[3] * sxv[i] * swv[j][g].w;
         }
-        vv[0] += bf_lo(bv[j][g].x);
-        vv[1] += bf_hi(bv[j][g].x);
-        vv[2] += bf_lo(bv[j][g].y);
-        vv[3] += bf_hi(bv[j][g].y);
-        if (EPI == X2V_EPI_GELU_TANH) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) vv[e] = gelu_tanh_f(rbf(vv[e]));
-        } else if (EPI == X2V_EPI_SILU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) vv[e] = silu_f(rbf(vv[e]));
-        }
+        epi_bias_act4<EPI>(vv, bv[j][g].x, bv[j][g].y);
         uint2 pk;
         pk.x = pack_bf2(vv[0], vv[1]);
         pk.y = pack_bf2(vv[2], vv[3]);
@@ -282,10 +342,28 @@ static int launch_gemm(const void* x, int64_t ldx_bytes, const void* w, int64_t 
   }
   hipLaunchKernelGGL((gemm_kernel<FP8, EPI, I8>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)x, ldx_bytes, (const char*)w,
                      ldw_bytes, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)resid, ldr,
-                     (const unsigned short*)gate, sx, sw, ntm, ntn, gb);
+                     (const unsigned short*)gate, sx, sw, ntm, ntn, gb, (const unsigned*)nullptr, (const unsigned*)nullptr);
   X2V_LAUNCH_CHECK("gemm launch");
   return X2V_OK;
 }
+
+// MXFP8 (mx.hip), shapes below the 256x256 kernel's: e4m3 operands with e8m0 block-scale tables [K/128][rows][4]; alpha = device pointer or null.  No fused
+// epilogue (those go to gemm256_mx_dispatch).  Arguments validated by the caller.
+namespace x2v {
+int gemm128_mx_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                        int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
+  const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
+  {
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, true>, G_LDS_BYTES, "gemm_mxfp8 attr");
+    if (rc != X2V_OK) return rc;
+  }
+  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, true>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
+                     (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
+                     (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
+  X2V_LAUNCH_CHECK("gemm_mxfp8 launch");
+  return X2V_OK;
+}
+}  // namespace x2v
 
 // The shape rule of variant 0 (one place: the dispatcher and x2v_gemm_kernel_choice both ask it): the 256^2 kernel wants at least
 // ~one full round of tiles (256 CUs), a K loop longer than its pipeline, and 32-bit buffer offsets over a 256-row tile.

@@ -382,17 +382,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
           vv[2] = vv[2] * sxv[mi] * swv[nj][g].z;
           vv[3] = vv[3] * sxv[mi] * swv[nj][g].w;
         }
-        vv[0] += bf_lo(bv[nj][g].x);
-        vv[1] += bf_hi(bv[nj][g].x);
-        vv[2] += bf_lo(bv[nj][g].y);
-        vv[3] += bf_hi(bv[nj][g].y);
-        if (EPI == X2V_EPI_GELU_TANH) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) vv[e] = gelu_tanh_f(rbf(vv[e]));
-        } else if (EPI == X2V_EPI_SILU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) vv[e] = silu_f(rbf(vv[e]));
-        }
+        epi_bias_act4<EPI>(vv, bv[nj][g].x, bv[nj][g].y);
         uint2 pk;
         pk.x = pack_bf2(vv[0], vv[1]);
         pk.y = pack_bf2(vv[2], vv[3]);

@@ -137,17 +137,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto epi_phase_a = [&](auto ic) {
     constexpr int I = decltype(ic)::value, wb = I & 7;
     float vv[4] = {acc_read<4 * I + 0>(), acc_read<4 * I + 1>(), acc_read<4 * I + 2>(), acc_read<4 * I + 3>()};
-    vv[0] += bf_lo(e_bias[wb].x);
-    vv[1] += bf_hi(e_bias[wb].x);
-    vv[2] += bf_lo(e_bias[wb].y);
-    vv[3] += bf_hi(e_bias[wb].y);
-    if (EPI == X2V_EPI_GELU_TANH) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) vv[e] = gelu_tanh_f(rbf(vv[e]));
-    } else if (EPI == X2V_EPI_SILU) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) vv[e] = silu_f(rbf(vv[e]));
-    }
+    epi_bias_act4<EPI>(vv, e_bias[wb].x, e_bias[wb].y);
     // [row r16][256 B], 16-byte chunk (2 wb + (g16 >> 1)) ^ r16, half g16 & 1
     const int wa = r16 * 256 + (((((g16 >> 1) ^ r16) << 4)) ^ (wb * 32)) + (g16 & 1) * 8;
     *reinterpret_cast<u32x2_t*>(strip + wa) = u32x2_t{pack_bf2(vv[0], vv[1]), pack_bf2(vv[2], vv[3])};

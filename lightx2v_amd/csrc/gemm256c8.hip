@@ -256,17 +256,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       vv[1] = vv[1] * e_sx[xb] * e_sw[ch][j].y;
       vv[2] = vv[2] * e_sx[xb] * e_sw[ch][j].z;
       vv[3] = vv[3] * e_sx[xb] * e_sw[ch][j].w;
-      vv[0] += bf_lo(e_bias[ch][j].x);
-      vv[1] += bf_hi(e_bias[ch][j].x);
-      vv[2] += bf_lo(e_bias[ch][j].y);
-      vv[3] += bf_hi(e_bias[ch][j].y);
-      if (EPI == X2V_EPI_GELU_TANH) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = gelu_tanh_f(rbf(vv[e]));
-      } else if (EPI == X2V_EPI_SILU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = silu_f(rbf(vv[e]));
-      }
+      epi_bias_act4<EPI>(vv, e_bias[ch][j].x, e_bias[ch][j].y);
       *reinterpret_cast<u32x2_t*>(strip + (wa0 ^ (j << 4))) = u32x2_t{pack_bf2(vv[0], vv[1]), pack_bf2(vv[2], vv[3])};
     });
   };

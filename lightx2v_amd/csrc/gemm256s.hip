@@ -242,17 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       constexpr int I = decltype(ic)::value, xb = I >> 3, wb = I & 7;
       const int ml = wr * 128 + xb * 16 + r16, nl = wc * 128 + wb * 16 + 4 * g16;
       float vv[4] = {acc_read<4 * I + 0>(), acc_read<4 * I + 1>(), acc_read<4 * I + 2>(), acc_read<4 * I + 3>()};
-      vv[0] += bf_lo(bv[wb].x);
-      vv[1] += bf_hi(bv[wb].x);
-      vv[2] += bf_lo(bv[wb].y);
-      vv[3] += bf_hi(bv[wb].y);
-      if (EPI == X2V_EPI_GELU_TANH) {
-  #pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = gelu_tanh_f(rbf(vv[e]));
-      } else if (EPI == X2V_EPI_SILU) {
-  #pragma unroll
-        for (int e = 0; e < 4; ++e) vv[e] = silu_f(rbf(vv[e]));
-      }
+      X2V_EPI_BIAS_ACT4(EPI, vv, bv[wb].x, bv[wb].y);  // epi_bias_act4's body in place (x2v_common.h says why)
       uint2 pk;
       pk.x = pack_bf2(vv[0], vv[1]);
       pk.y = pack_bf2(vv[2], vv[3]);

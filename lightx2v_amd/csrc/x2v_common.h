@@ -115,6 +115,28 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 
+// The bias and activation step of every GEMM epilogue (tests/gemm_ref.py::finish): four consecutive output columns get their bf16 bias (two packed
+// pairs), and an activation takes the sum rounded to bf16.  The dequantisation in front and the pack and store behind differ per kernel and stay there.
+// The rule is written as a macro and wrapped by the function: gemm256s.hip expands the macro in place, because through the function call the GELU and
+// SiLU instantiations of its one-tile kernel came out with 165 / 84 instructions in another order (profiles/gemm128_mx_merge_isa.txt); every other
+// GEMM body calls the function and keeps its instruction stream.
+#define X2V_EPI_BIAS_ACT4(EPI, vv, bias01, bias23)                                \
+  do {                                                                            \
+    (vv)[0] += bf_lo(bias01);                                                     \
+    (vv)[1] += bf_hi(bias01);                                                     \
+    (vv)[2] += bf_lo(bias23);                                                     \
+    (vv)[3] += bf_hi(bias23);                                                     \
+    if ((EPI) == X2V_EPI_GELU_TANH) {                                             \
+      _Pragma("unroll") for (int e = 0; e < 4; ++e) (vv)[e] = gelu_tanh_f(rbf((vv)[e])); \
+    } else if ((EPI) == X2V_EPI_SILU) {                                           \
+      _Pragma("unroll") for (int e = 0; e < 4; ++e) (vv)[e] = silu_f(rbf((vv)[e]));      \
+    }                                                                             \
+  } while (0)
+template <int EPI>
+__device__ __forceinline__ void epi_bias_act4(float* vv, unsigned bias01, unsigned bias23) {
+  X2V_EPI_BIAS_ACT4(EPI, vv, bias01, bias23);
+}
+
 // ---- wave / block reductions -------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,5 +1,5 @@
-"""float64 references, seeded inputs, fp32 emulations and the GPU module's lists for the MXFP8 path: quant_mxfp8_kernel and gemm_mxfp8_kernel
-(lightx2v_amd/csrc/mx.hip) and the MX instantiation of gemm256_kernel (gemm256.hip).  Plain PyTorch on float64; nothing here imports the library or
+"""float64 references, seeded inputs, fp32 emulations and the GPU module's lists for the MXFP8 path: quant_mxfp8_kernel
+(lightx2v_amd/csrc/mx.hip) and the MX instantiations of gemm_kernel (gemm.hip, 128x128) and gemm256_kernel (gemm256.hip).  Plain PyTorch on float64; nothing here imports the library or
 oracle/.  bf16 rounding, Expect, Case, the epilogue chains and both acceptance rules are tests/gemm_ref.py's.  Shared by tests/test_mx_ref_host.py
 (the yardstick checked without a GPU) and tests/test_gpu_mx_fp64.py (the kernels checked against it).
 

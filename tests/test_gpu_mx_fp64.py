@@ -1,4 +1,4 @@
-"""The MXFP8 path — quant_mxfp8_kernel and gemm_mxfp8_kernel (128x128) of mx.hip and the MX instantiation of gemm256.hip's 256x256 ping-pong kernel —
+"""The MXFP8 path — quant_mxfp8_kernel of mx.hip and the MX instantiations of gemm.hip's 128x128 kernel and of gemm256.hip's 256x256 ping-pong kernel —
 against the float64 references of tests/mx_ref.py, at the smallest shapes at which each edge exists.  tests/test_mx_ref_host.py shows which subtly
 wrong kernels and quantisers this rejects.
 

@@ -4,9 +4,10 @@ for every kernel its register counts, scratch and static LDS on both sides, whet
 is identical from the kernel's entry to the end of its K loop (the last s_barrier), followed by the differing instructions.  Comment lines, the
 compile-unit id and basic-block numbering are ignored.  Kernel names are demangled with llvm-cxxfilt or c++filt; --rename REGEX=REPLACEMENT (repeatable) maps
 the OLD side's names onto the new ones where a kernel was renamed.  An OLD argument may name several files joined with '+' (OLDa.s+OLDb.s): their
-kernels are taken together, for two files that were merged into the one NEW file.  Also reports the accumulator AUDIT rule of the single-stream GEMM kernels on the
+kernels are taken together, for two files that were merged into the one NEW file; a NEW argument may do the same, for a kernel that moved from one
+file to another.  Also reports the accumulator AUDIT rule of the single-stream GEMM kernels on the
 NEW side: no v_accvgpr_* and no a[..] operand outside ;;#ASMSTART / ;;#ASMEND.
-usage: isa_diff.py [--rename REGEX=REPLACEMENT ...] OLD.s[+OLDb.s] NEW.s [OLD2.s NEW2.s ...] > profiles/<what>_isa.txt"""
+usage: isa_diff.py [--rename REGEX=REPLACEMENT ...] OLD.s[+OLDb.s] NEW.s[+NEWb.s] [OLD2.s NEW2.s ...] > profiles/<what>_isa.txt"""
 import difflib
 import os
 import re
@@ -77,9 +78,11 @@ def main(argv):
     print(f"{'kernel':64s} {'identical':10s} {'to K-loop end':13s} sgpr / vgpr / agpr / spilled vgprs / scratch / static LDS   old -> new")
     bad = stray_total = count = 0
     for old_path, new_path in zip(argv[0::2], argv[1::2]):
-        old, new = {}, kernels(new_path)
+        old, new = {}, {}
         for part in old_path.split("+"):
             old.update(kernels(part, renames))
+        for part in new_path.split("+"):
+            new.update(kernels(part))
         for name in sorted(set(old) | set(new)):
             if name not in old or name not in new:
                 print(f"{name:64s} only in {'old' if name in old else 'new'}")
