@@ -364,6 +364,43 @@ int x2v_gemm_mxfp8_epi(const void* a, int64_t lda, const void* sa, const void* b
 int x2v_gemm_mxfp8_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
                            void* y, int64_t ldy, int64_t M, int N, int K, int variant, void* stream);
 
+/* MXFP6 weight quantisation — replaces lightx2v_kernel.gemm.scaled_fp6_quant (lightx2v_kernel/python/lightx2v_kernel/gemm.py:58-68,
+ * csrc/gemm/mxfp6_quant_kernels_sm120.cu:168-225).  x2v_quant_mxfp8_bf16's contract with 28 in place of 448 and e3m2 in place of e4m3fn:
+ * per 32 consecutive K elements the scale byte = biased exponent of the smallest power of two >= max|x| / 28 (the quotient in fp32 with
+ * denormals, saturating at 254; an all-zero block -> byte 0 and zero codes), code = e3m2(x * 2^(127 - byte)), one rounding to nearest-even,
+ * saturating at +/-28, sign of zero kept.  e3m2: 1 sign, 3 exponent bits (bias 3), 2 mantissa bits, code = s<<5 | e<<2 | m; subnormals
+ * m * 2^-4, largest number 28, no NaN / Inf.
+ * x bf16 [M,K] (ldx % 8 == 0, 16-byte aligned); q bytes [M, 3K/4] (ldq in bytes, ldq % 4 == 0, 4-byte aligned): the reference's dense
+ * little-endian packing (mxfp6_quant_kernels_sm120.cu:74-99, 4 codes -> 3 bytes) — code j of a row sits at bits 6j .. 6j+5 of the row's
+ * bytes; scales: the [K/128][M][4] table of x2v_quant_mxfp8_bf16.  K % 128 == 0.
+ * NaN and Inf elements are outside the contract of their own 32-wide block and leave every other block as with 0 in their place
+ * (tests/test_gpu_mx6.py); measured, not promised: a NaN is skipped by the block maximum (the scale byte and the other 31 codes are those
+ * with 0 in its place) and saturates to +/-28 (e3m2 has no NaN code), an Inf gives scale byte 254, code 0x1f and +/-0 for the other 31
+ * (profiles/mx6_fp64_parity.txt). */
+int x2v_quant_mxfp6_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t M, int K, void* stream);
+
+/* y[M,N] = alpha * (deq(a)[M,K] . deq(b)[N,K]^T) + bias[n] → bf16 with a = MXFP8 (e4m3) activations of x2v_quant_mxfp8_bf16 and
+ * b = MXFP6 (e3m2) weights of x2v_quant_mxfp6_bf16, packed [N, 3K/4], ldb in BYTES — replaces
+ * lightx2v_kernel.gemm.cutlass_scaled_mxfp6_mxfp8_mm (gemm.py:84-88, csrc/gemm/mxfp6_mxfp8_scaled_mm_kernels_sm120.cu:39-46).  sa, sb, alpha,
+ * bias and the rounding points as x2v_gemm_mxfp8.  Runs on v_mfma_scale_f32_32x32x64_f8f6f4 with the weight operand in format 3 (e3m2) next
+ * to the e4m3 one, the e8m0 block scales applied by the instruction.
+ * K % 128 == 0, N % 8 == 0; a, y: rows 16-byte aligned (lda % 16, ldy % 8); b: 4-byte aligned with ldb % 4 == 0 and ldb >= 3K/4 (the
+ * weight tile is staged in 12-byte pieces); scale tables 4-byte, bias 8-byte aligned.
+ * Two bodies, chosen as for x2v_gemm_mxfp8: the fp6 mode of the 128x128-tile kernel and of the 256x256-tile ping-pong kernel (shapes that fill
+ * the chip and every fused epilogue; it addresses a tile with 32-bit offsets: lda, ldb < 2^24 bytes, else X2V_E_SHAPE). */
+int x2v_gemm_mxfp6_mxfp8(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                         void* y, int64_t ldy, int64_t M, int N, int K, void* stream);
+
+/* x2v_gemm_mxfp6_mxfp8 with the fused epilogues of x2v_gemm_mxfp8_epi (X2V_EPI_*; X2V_EPI_RESIDUAL without resid: X2V_E_ARG): what the fused
+ * block drivers call for a linear layer held in MXFP6 (operator class MMWeightMxfp6Hip). */
+int x2v_gemm_mxfp6_mxfp8_epi(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                             void* y, int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
+
+/* Same with x2v_gemm_mxfp8_variant's kernel selector: 0 = automatic, 1 = 128x128-tile kernel, 2 = 256x256-tile ping-pong kernel; anything else:
+ * X2V_E_ARG. */
+int x2v_gemm_mxfp6_mxfp8_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                                 const float* alpha, void* y, int64_t ldy, int64_t M, int N, int K, int variant, void* stream);
+
 /* Timestep sinusoid: y[n, dim] bf16 = [cos(t*f_j) | sin(t*f_j)], f_j = 10000^(-j/(dim/2)) computed in
  * float64 then rounded — replaces sinusoidal_embedding_1d (wan/infer/utils.py:161-172).  t: int64 [n]. */
 int x2v_sinusoid_embed_bf16(const int64_t* t, void* y, int n, int dim, void* stream);

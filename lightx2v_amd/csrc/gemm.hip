@@ -2,7 +2,8 @@
 // The fp8 variant shares the whole structure: a 128-byte operand row per stage is 64 bf16 or 128 fp8 k-values;
 // it issues v_mfma_scale_f32_32x32x64_f8f6f4 with unit (2^0) block scales — the only fp8 MFMA that runs at
 // the 2x rate on gfx950 — and applies the per-token x per-channel fp32 scales in the epilogue.  Its MX mode (MXFP8, mx.hip's small shapes) hands
-// the same instruction the operands' own e8m0 block scales and multiplies by alpha in the epilogue.
+// the same instruction the operands' own e8m0 block scales and multiplies by alpha in the epilogue; with MXM = 2 the weight operand is MXFP6 (packed
+// e3m2 codes, 96 bytes per row and K-tile).
 //
 // Bound: MFMA (bf16 dense peak ~2.5 PFLOP/s); algorithmic work 2*M*N*K FLOP per launch.
 //
@@ -39,22 +40,32 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 __device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)lds_wave_base, 16, 0, 0);
 }
+// 12 bytes per lane (global_load_lds_dwordx3): 16 packed 6-bit codes.  The LDS side keeps the 16-byte lane stride of the dwordx4 form (probed: lane l
+// writes bytes [16 l, 16 l + 12) from the wave's base and leaves the fourth dword alone), so a 96-byte fp6 row takes a 128-byte LDS row of 8 slots
+__device__ __forceinline__ void glds12(const void* g, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)lds_wave_base, 12, 0, 0);
+}
 
 // swizzled byte offset of 16-byte chunk `c` of row `r` in a [rows][128 B] tile
 __device__ __forceinline__ int swz_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+struct alignas(16) Dword3 { int x, y, z; };  // the 12 valid bytes of a 16-byte slot of the MXFP6 W tile
 
 // I8 (with FP8 = true: the w8a8 operand and scale plumbing): int8 codes on v_mfma_i32_32x32x32_i8, four k-steps of 32 per 128-byte stage row, an
 // exact int32 accumulator converted to fp32 (v_cvt_f32_i32, round to nearest even) in front of the dequantisation.
 // MX (with FP8 = true, I8 = false: MXFP8, mx.hip): y = alpha * (A . W^T) + bias with per-(row, 32-k) e8m0 block scales applied by the MFMA; SA / SB are
 // the scale tables [K/128][rows] of one dword per operand row and K-tile, `sx` carries the device pointer to alpha (or null), `sw` is unused.
-template <bool FP8, int EPI, bool I8, bool MX = false>
+// MXM = 2 (MXFP6 weights x MXFP8 activations, mx.hip): MX with W rows of packed e3m2 codes, 96 bytes per row and K-tile in HBM, staged in 12-byte
+// pieces (16 codes) with the fp8 lane -> (row, chunk) map and swizzle into the same [128][128 B] image (12 of every 16 bytes used), the W fragment
+// two 12-byte pieces in the low 6 dwords, cbsz = 3; the x side, the scale dwords, the K loop, the waits and the epilogue are MXFP8's.
+template <bool FP8, int EPI, bool I8, int MXM = 0>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                       const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
                                                       int N, int nk, const unsigned short* __restrict__ resid, int64_t ldr,
                                                       const unsigned short* __restrict__ gate, const float* __restrict__ sx,
                                                       const float* __restrict__ sw, int ntm, int ntn, GemmBlocking gb,
                                                       const unsigned* __restrict__ SA, const unsigned* __restrict__ SB) {
-  static_assert(!MX || (FP8 && !I8), "MX: block-scaled fp8");
+  constexpr bool MX = MXM != 0, MX6 = MXM == 2;
+  static_assert(MXM >= 0 && MXM <= 2 && (!MX || (FP8 && !I8)), "MX: block-scaled fp8 (1) or fp6 weights x fp8 (2)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int a_kpb = gb.a_kpb > 0 && gb.a_kpb < nk ? gb.a_kpb : nk;
   const int tid = threadIdx.x;
@@ -87,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
     int gn = n0 + r;
     gn = gn < N ? gn : N - 1;
     a_src[i] = A + gm * lda_bytes + c * 16;
-    b_src[i] = W + (int64_t)gn * ldw_bytes + c * 16;
+    b_src[i] = W + (int64_t)gn * ldw_bytes + c * (MX6 ? 12 : 16);
   }
   auto stage = [&](int s, int kt) {
     char* as = smem + s * G_STAGE_BYTES + wid * (32 * 128);
@@ -97,8 +108,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
       if constexpr (MX) glds16(a_src[i] + (int64_t)kt * G_ROW_BYTES, as + i * 1024);  // MXFP8 never passes blocked operands; the arithmetic below costs it 2 % at K = 13824
       else glds16(a_src[i] + ((int64_t)(kt / a_kpb) * gb.a_cbs + (int64_t)(kt % a_kpb) * G_ROW_BYTES), as + i * 1024);  // K-blocked x
     }
+    if constexpr (MX6) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) glds16(b_src[i] + (int64_t)kt * G_ROW_BYTES, bs + i * 1024);
+      for (int i = 0; i < 4; ++i) glds12(b_src[i] + (int64_t)kt * 96, bs + i * 1024);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) glds16(b_src[i] + (int64_t)kt * G_ROW_BYTES, bs + i * 1024);
+    }
   };
 
   // ---- MFMA fragment read offsets (bytes within a tile image); wave (wr, wc) owns rows wr*64.., cols wc*64..
@@ -117,7 +133,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
     for (int ks = 0; ks < 4; ++ks) {
       const int c = MX ? ((ks >> 1) * 4 + (ks & 1) * 2 + fh) : (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
       a_off[i][ks] = swz_off(wr * 64 + i * 32 + fl, c);
-      b_off[i][ks] = swz_off(wc * 64 + i * 32 + fl, c) + GB_M * 128;
+      // MXFP6 W (probed with one-hot codes against a one-hot x): the 32 codes of a lane are k = fh*32 .. +31 in order (scale block fh), not the fp8
+      // fragment's two halves: 12-byte chunks s*4 + fh*2 and s*4 + fh*2 + 1
+      const int c6 = (ks >> 1) * 4 + fh * 2 + (ks & 1);
+      b_off[i][ks] = swz_off(wc * 64 + i * 32 + fl, MX6 ? c6 : c) + GB_M * 128;
     }
   // MX block scales: one dword per operand row and K-tile = the 4 scale bytes of its k blocks.  The instruction takes byte `opsel` of the
   // scale VGPR of every lane; lanes fh = 1 (k block s*2 + 1) shift their dword down by one byte so that opsel = 2 s serves both halves.
@@ -216,10 +235,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
         for (int i = 0; i < 2; ++i) {
           const i32x4_t a0 = *reinterpret_cast<const i32x4_t*>(base + a_off[i][s2 * 2]);
           const i32x4_t a1 = *reinterpret_cast<const i32x4_t*>(base + a_off[i][s2 * 2 + 1]);
-          const i32x4_t b0 = *reinterpret_cast<const i32x4_t*>(base + b_off[i][s2 * 2]);
-          const i32x4_t b1 = *reinterpret_cast<const i32x4_t*>(base + b_off[i][s2 * 2 + 1]);
           xa[i] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-          wb[i] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+          if constexpr (MX6) {  // 32 codes = 6 dwords; the instruction reads the low 6 of the 8
+            const Dword3 b0 = *reinterpret_cast<const Dword3*>(base + b_off[i][s2 * 2]);
+            const Dword3 b1 = *reinterpret_cast<const Dword3*>(base + b_off[i][s2 * 2 + 1]);
+            wb[i] = i32x8_t{b0.x, b0.y, b0.z, b1.x, b1.y, b1.z, 0, 0};
+          } else {
+            const i32x4_t b0 = *reinterpret_cast<const i32x4_t*>(base + b_off[i][s2 * 2]);
+            const i32x4_t b1 = *reinterpret_cast<const i32x4_t*>(base + b_off[i][s2 * 2 + 1]);
+            wb[i] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
         }
         constexpr int kOne = 0x7f7f7f7f;  // e8m0 2^0 block scales
         // first matrix operand = W (weight) fragment, second = A (activation) fragment: the accumulator's lane index is the output row
@@ -229,7 +254,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
           for (int j = 0; j < 2; ++j) {
             if constexpr (!MX)
               acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, kOne, 0, kOne);
-            else if (s2 == 0)
+            else if constexpr (MX6) {  // format 3 = e3m2 ("bf6") for the first operand
+              if (s2 == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 3, 0, 0, (int)sb_cur[j], 0, (int)sa_cur[i]);
+              else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 3, 0, 2, (int)sb_cur[j], 2, (int)sa_cur[i]);
+            } else if (s2 == 0)
               acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, (int)sb_cur[j], 0, (int)sa_cur[i]);
             else
               acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 2, (int)sb_cur[j], 2, (int)sa_cur[i]);
@@ -354,13 +382,29 @@ int gemm128_mx_dispatch(const void* a, int64_t lda, const void* sa, const void* 
                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
   const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
   {
-    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, true>, G_LDS_BYTES, "gemm_mxfp8 attr");
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 1>, G_LDS_BYTES, "gemm_mxfp8 attr");
     if (rc != X2V_OK) return rc;
   }
-  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, true>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
+  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 1>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
                      (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
                      (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
   X2V_LAUNCH_CHECK("gemm_mxfp8 launch");
+  return X2V_OK;
+}
+
+// MXFP6 weights x MXFP8 activations (mx.hip), shapes below the 256x256 kernel's: b = packed e3m2 codes [N, 3K/4], ldb in bytes.  No fused epilogue
+// (those go to gemm256_mx6_dispatch).  Arguments validated by the caller.
+int gemm128_mx6_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
+  const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
+  {
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 2>, G_LDS_BYTES, "gemm_mxfp6_mxfp8 attr");
+    if (rc != X2V_OK) return rc;
+  }
+  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 2>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
+                     (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
+                     (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
+  X2V_LAUNCH_CHECK("gemm_mxfp6_mxfp8 launch");
   return X2V_OK;
 }
 }  // namespace x2v

@@ -38,8 +38,13 @@ constexpr int T_EPI_LD = 528;               // bytes per epilogue row (256 bf16 
 constexpr int T_LDS_BYTES = 256 * T_EPI_LD; // 135168 >= 8 * T_HALF_BYTES
 
 typedef __attribute__((address_space(3))) void* t_lds_ptr_t;
+struct alignas(16) T_Dword3 { int x, y, z; };  // the 12 valid bytes of a 16-byte slot of an MXFP6 W half-tile
 
-template <bool FP8, int EPI, int LEAD, int KW, bool MX>
+// MXM: 0 = per-channel scales (or bf16), 1 = MXFP8 (block scales applied by the instruction), 2 = MXFP6 weights x MXFP8 activations: W rows of packed
+// e3m2 codes, 96 bytes per row and K-tile, staged in 12-byte pieces (buffer_load_dwordx3 ... lds keeps the 16-byte lane stride in LDS and leaves the
+// fourth dword alone, so the half-tile image, the swizzle, the DMA instruction count and the counted vmcnt waits are MXFP8's), W fragments of
+// 6 dwords in the instruction's fp6 order (a lane's 32 codes are k = fh*32 .. +31), cbsz = 3.
+template <bool FP8, int EPI, int LEAD, int KW, int MXM>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                          const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
                                                          int N, int nk, const unsigned short* __restrict__ resid, int64_t ldr,
@@ -48,7 +53,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
                                                          const unsigned* __restrict__ SA, const unsigned* __restrict__ SB, GemmBlocking gb) {
 #if defined(__HIP_DEVICE_COMPILE__)
   static_assert(LEAD >= KW + 3 && LEAD <= 7 && LEAD >= 4, "see the hazard accounting in the header comment (and the A-half K offsets ak1/ak2)");
-  static_assert(!MX || FP8, "MX: block-scaled fp8");
+  constexpr bool MX = MXM != 0, MX6 = MXM == 2;
+  static_assert(MXM >= 0 && MXM <= 2 && (!MX || FP8), "MX: block-scaled fp8 (1) or fp6 weights x fp8 (2)");
   // bf16 runs on v_mfma_f32_16x16x32_bf16: at the board's power limit (where this kernel lives) the 16x16 shape delivers ~11 % more FLOP/s
   // than 32x32x16 for the same LDS fragment traffic (tools/probes/mfma_power_probe.hip, profiles/r02_mfma_power_probe.log)
   constexpr bool MI16 = !FP8;
@@ -73,6 +79,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
 
   // ---- buffer descriptors over this tile's valid rows (wave-uniform: kernel arguments + blockIdx only)
   const unsigned row_bytes = (unsigned)nk * 128u;
+  constexpr unsigned W_KT = MX6 ? 96u : 128u;  // bytes of a W row per K-tile
   const int rows_a = (int)min((int64_t)T_M, M - m0), rows_w = min(T_N, N - n0);
   // K-blocked x (GemmBlocking, x2v_common.h): K-tile kt of a row lives at (kt / a_kpb) * a_cbs + (kt % a_kpb) * 128 bytes; the range covers
   // the last block (rows past M of an earlier block alias the next block's rows: their results are never stored)
@@ -90,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
   T_AK_NEXT(ak2, akc2)
   const unsigned ak_first = ak1;  // tile 1, for the prologue
   const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(W + (int64_t)n0 * ldw_bytes), 0, (unsigned)((rows_w - 1) * ldw_bytes) + row_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)(W + (int64_t)n0 * ldw_bytes), 0, (unsigned)((rows_w - 1) * ldw_bytes) + (MX6 ? (unsigned)nk * W_KT : row_bytes), 0x00020000);
 
   // ---- per-lane DMA source offsets: wave `wid` stages rows [wid*16, wid*16+16) of a half (2 wave-instructions of
   //      8 rows x 8 chunks); [h*2+i] = half h (rows +128), instruction i.  The K offset travels in soffset.
@@ -102,10 +109,14 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
       const int r = (wid * 2 + i) * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((r >> 1) & 7);
       a_voff[h * 2 + i] = (unsigned)((h * 128 + r) * lda_bytes) + (unsigned)(c << 4);
-      w_voff[h * 2 + i] = (unsigned)((h * 128 + r) * ldw_bytes) + (unsigned)(c << 4);
+      w_voff[h * 2 + i] = (unsigned)((h * 128 + r) * ldw_bytes) + (unsigned)(MX6 ? c * 12 : c << 4);
     }
   // half J of a K-tile: 0 = B0 (W rows 0..127), 1 = A_a (x rows 0..127), 2 = B1 (W rows 128..255), 3 = A_b
 #define T_ISSUE1(J_, SLOT_, KOFF_, I_)                                                                                         \
+  if (MX6 && !((J_) & 1))                                                                                                      \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (t_lds_ptr_t)(smem + (SLOT_) * T_HALF_BYTES + (wid * 2 + (I_)) * 1024), 12,   \
+                                             w_voff[((J_) >> 1) * 2 + (I_)], (unsigned)(KOFF_), 0, 0);                         \
+  else                                                                                                                         \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(((J_) & 1) ? ra : rw, (t_lds_ptr_t)(smem + (SLOT_) * T_HALF_BYTES + (wid * 2 + (I_)) * 1024), 16, \
                                            ((J_) & 1) ? a_voff[((J_) >> 1) * 2 + (I_)] : w_voff[((J_) >> 1) * 2 + (I_)], (unsigned)(KOFF_), 0, 0);
 #define T_ISSUE(J_, SLOT_, KOFF_) { T_ISSUE1(J_, SLOT_, KOFF_, 0) T_ISSUE1(J_, SLOT_, KOFF_, 1) }
@@ -137,7 +148,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
       const int kp = FP8 ? (((ks >> 1) << 2) | ((ks & 1) << 1)) : (ks << 1);
       const int o = fl * 128 + ((lp ^ kp) << 4);
       rd_a[ks] = o + wr * 4096;
-      rd_b[ks] = o + wc * 4096;
+      // MXFP6 W: MFMA s reads the 12-byte pieces s*4 + fh*2 and s*4 + fh*2 + 1 (the lane's 32 codes are consecutive k)
+      rd_b[ks] = (MX6 ? fl * 128 + ((((((ks >> 1) << 2) | (fh << 1) | (ks & 1))) ^ swz) << 4) : o) + wc * 4096;
     }
   }
 
@@ -190,6 +202,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
 #define T_RD(DST_, SLOT_, RD_, EXTRA_) \
   _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) DST_[ks_] = *reinterpret_cast<const i32x4_t*>(smem + (SLOT_) * T_HALF_BYTES + (EXTRA_) + RD_[ks_]);
 
+  // W fragments; MXFP6: 12 bytes per slot (ds_read_b96), so a phase's W fragments hold 12 VGPRs, not 16 (with ds_read_b128 and the fourth dword
+  // dropped afterwards the kernel spilled 14 VGPRs)
+#define T_RDW(DST_, SLOT_)                                                                                                     \
+  if constexpr (MX6) {                                                                                                         \
+    _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) {                                                                      \
+      const T_Dword3 d_ = *reinterpret_cast<const T_Dword3*>(smem + (SLOT_) * T_HALF_BYTES + rd_b[ks_]);                       \
+      DST_[ks_] = i32x4_t{d_.x, d_.y, d_.z, 0};                                                                                \
+    }                                                                                                                          \
+  } else { T_RD(DST_, SLOT_, rd_b, 0) }
+
   // 8 MFMAs (fp8: 4) of one phase
 #define T_MFMA(MI0_, NJ_, WB_, I0_, I1_)                                                                                                 \
   if constexpr (MI16) {                                                                                                        \
@@ -208,11 +230,17 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
     constexpr int kOne = 0x7f7f7f7f; /* e8m0 2^0 block scales */                                                               \
     _Pragma("unroll") for (int idx_ = (I0_) / 4; idx_ < (I1_) / 4; ++idx_) {                                                   \
       const int s_ = idx_ >> 1, i_ = idx_ & 1;                                                                                 \
-      const i32x8_t wf_ = __builtin_shufflevector(WB_[2 * s_], WB_[2 * s_ + 1], 0, 1, 2, 3, 4, 5, 6, 7);                       \
+      const i32x8_t wf_ = MX6 ? __builtin_shufflevector(WB_[2 * s_], WB_[2 * s_ + 1], 0, 1, 2, 4, 5, 6, 3, 7) /* 2 x 12 bytes */ \
+                              : __builtin_shufflevector(WB_[2 * s_], WB_[2 * s_ + 1], 0, 1, 2, 3, 4, 5, 6, 7);                 \
       const i32x8_t xf_ = __builtin_shufflevector(xa[i_][2 * s_], xa[i_][2 * s_ + 1], 0, 1, 2, 3, 4, 5, 6, 7);                 \
       if constexpr (!MX)                                                                                                       \
         acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 0, 0, 0, kOne, 0, kOne); \
-      else if (s_ == 0)                                                                                                        \
+      else if constexpr (MX6) {                                                                                                \
+        if (s_ == 0)                                                                                                           \
+          acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 3, 0, 0, (int)sw_cur[NJ_], 0, (int)sx_cur[(MI0_) + i_]); \
+        else                                                                                                                   \
+          acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 3, 0, 2, (int)sw_cur[NJ_], 2, (int)sx_cur[(MI0_) + i_]); \
+      } else if (s_ == 0)                                                                                                      \
         acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 0, 0, 0, (int)sw_cur[NJ_], 0, (int)sx_cur[(MI0_) + i_]); \
       else                                                                                                                     \
         acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 0, 0, 2, (int)sw_cur[NJ_], 2, (int)sx_cur[(MI0_) + i_]); \
@@ -239,17 +267,17 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
     if constexpr ((Q_) == 0) {                                                                                                 \
       T_RD(xa[0], (TB_) * 4 + 1, rd_a, 0) T_RD(xa[1], (TB_) * 4 + 1, rd_a, 8192)                                               \
     } else if constexpr ((Q_) == 1) {                                                                                          \
-      T_RD(wb1, (TB_) * 4 + 2, rd_b, 0)                                                                                        \
+      T_RDW(wb1, (TB_) * 4 + 2)                                                                                                \
     } else if constexpr ((Q_) == 2) {                                                                                          \
       T_RD(xa[0], (TB_) * 4 + 3, rd_a, 0) T_RD(xa[1], (TB_) * 4 + 3, rd_a, 8192)                                               \
     } else {                                                                                                                   \
-      T_RD(wb0, ((TB_) ^ 1) * 4 + 0, rd_b, 0)                                                                                  \
+      T_RDW(wb0, ((TB_) ^ 1) * 4 + 0)                                                                                          \
     }                                                                                                                          \
     const bool live_ = (CHK_) ? (4 * t + (Q_) + LEAD < total) : true;                                                          \
     if constexpr (MX && (Q_) == 0) {                                                                                           \
       if ((CHK_) ? (t + 1 < nk) : true) T_SC_LOAD(t + 1)                                                                        \
     }                                                                                                                          \
-    if (live_) T_ISSUE(((Q_) + LEAD) & 3, ((TB_) * 4 + (Q_) + LEAD) & 7, ((((Q_) + LEAD) & 1) ? ((((Q_) + LEAD) / 4) == 1 ? ak1 : ak2) : (unsigned)((t + ((Q_) + LEAD) / 4) * 128)))          \
+    if (live_) T_ISSUE(((Q_) + LEAD) & 3, ((TB_) * 4 + (Q_) + LEAD) & 7, ((((Q_) + LEAD) & 1) ? ((((Q_) + LEAD) / 4) == 1 ? ak1 : ak2) : (unsigned)((t + ((Q_) + LEAD) / 4) * W_KT)))          \
     __builtin_amdgcn_sched_barrier(0);                                                                                         \
     __builtin_amdgcn_s_barrier();                                                                                              \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                         \
@@ -280,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
     if constexpr (MX) T_SC_LOAD(0)  // oldest loads in flight: complete after the prologue wait below
 #pragma unroll
     for (int g = 0; g < LEAD; ++g)
-      if (g < total) T_ISSUE(g & 3, g & 7, ((g & 1) ? ((g >> 2) ? ak_first : 0u) : (unsigned)((g >> 2) * 128)))
+      if (g < total) T_ISSUE(g & 3, g & 7, ((g & 1) ? ((g >> 2) ? ak_first : 0u) : (unsigned)((g >> 2) * W_KT)))
     // = the steady-state wait of "phase -1": leaves KW halves in flight, so B1 of K-tile 0 (read in phase 1 by the
     // wr = 0 waves, which see no later wait of the wr = 1 waves) has landed too
     if (total >= LEAD) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * KW) : "memory");
@@ -288,7 +316,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
     if constexpr (MX) T_SC_ADOPT()
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    T_RD(wb0, 0, rd_b, 0)
+    T_RDW(wb0, 0)
   }
   if (wr == 1) __builtin_amdgcn_s_barrier();  // the wr = 1 waves run one barrier behind (ping-pong)
   __builtin_amdgcn_sched_barrier(0);
@@ -328,6 +356,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
 #undef T_MFMA
 #undef T_MFMA_Q
 #undef T_RD
+#undef T_RDW
 #undef T_ISSUE
 #undef T_ISSUE1
 #undef T_SC_LOAD
@@ -425,7 +454,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
 #endif
 }
 
-template <bool FP8, int EPI, bool MX = false>
+template <bool FP8, int EPI, int MXM = 0>
 static int launch_gemm256(const void* x, int64_t ldx_bytes, const void* w, int64_t ldw_bytes, const void* bias, void* y, int64_t ldy, int64_t M, int N,
                           int nk, const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st,
                           const void* sa = nullptr, const void* sb = nullptr, GemmBlocking gb = GemmBlocking()) {
@@ -433,10 +462,10 @@ static int launch_gemm256(const void* x, int64_t ldx_bytes, const void* w, int64
   if (gm_tiles <= 0) gm_tiles = 4;  // m-tiles per scheduling group
   const int ntm = (int)((M + T_M - 1) / T_M), ntn = (N + T_N - 1) / T_N;
   {
-    int rc = ensure_dynamic_lds((const void*)gemm256_kernel<FP8, EPI, LEAD, KW, MX>, T_LDS_BYTES, "gemm256 attr");
+    int rc = ensure_dynamic_lds((const void*)gemm256_kernel<FP8, EPI, LEAD, KW, MXM>, T_LDS_BYTES, "gemm256 attr");
     if (rc != X2V_OK) return rc;
   }
-  hipLaunchKernelGGL((gemm256_kernel<FP8, EPI, LEAD, KW, MX>), dim3((unsigned)ntm * (unsigned)ntn), dim3(512), T_LDS_BYTES, st, (const char*)x, ldx_bytes,
+  hipLaunchKernelGGL((gemm256_kernel<FP8, EPI, LEAD, KW, MXM>), dim3((unsigned)ntm * (unsigned)ntn), dim3(512), T_LDS_BYTES, st, (const char*)x, ldx_bytes,
                      (const char*)w, ldw_bytes, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)resid, ldr,
                      (const unsigned short*)gate, sx, sw, ntm, ntn, gm_tiles, (const unsigned*)sa, (const unsigned*)sb, gb);
   X2V_LAUNCH_CHECK("gemm256 launch");
@@ -456,7 +485,14 @@ int gemm256_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, i
 int gemm256_mx_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
   return with_epilogue("gemm_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
-    return launch_gemm256<true, decltype(epi)::value, true>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+    return launch_gemm256<true, decltype(epi)::value, 1>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+  });
+}
+// MXFP6 weights x MXFP8 activations (mx.hip): b = packed e3m2 codes [N, 3K/4], ldb in bytes.  Arguments validated by the caller.
+int gemm256_mx6_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
+  return with_epilogue("gemm_mxfp6_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256<true, decltype(epi)::value, 2>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
   });
 }
 

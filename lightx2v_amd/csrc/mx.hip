@@ -13,6 +13,12 @@
 // GEMM:  MFMA-bound — 2*M*N*K FLOP per launch against the 5 PFLOP/s fp8 peak.  Two bodies, both the MX mode of a kernel of the GEMM family: gemm.hip's
 //        128x128-tile / two-barrier kernel (small shapes) and gemm256.hip's 256x256 ping-pong kernel (shapes that fill the chip, and every call
 //        with a fused epilogue); gemm_mxfp8_impl chooses.  This file keeps the quantiser, the entries and their argument checks.
+//
+// MXFP6 weights x MXFP8 activations (e3m2 weights packed 4 codes to 3 bytes, the same e8m0 scale per 32 K elements) — the package's second MX path
+//   scaled_fp6_quant                gemm.py:58-68, csrc/gemm/mxfp6_quant_kernels_sm120.cu:168-225
+//   cutlass_scaled_mxfp6_mxfp8_mm   gemm.py:84-88, csrc/gemm/mxfp6_mxfp8_scaled_mm_kernels_sm120.cu:39-46
+// is quant_mxfp6_kernel below and one more value (2) of the same two kernels' MX mode; gemm_mxfp6_impl chooses with the same rule.
+// quant: HBM-bound — 2 + 0.75 + 1/32 bytes per element.  GEMM: MFMA-bound at the fp8 rate (one operand is e4m3).
 #include "x2v_common.h"
 
 namespace x2v {
@@ -68,6 +74,58 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const unsigned short* 
   }
 }
 
+// MXFP6 (e3m2: 1 sign, 3 exponent bits of bias 3, 2 mantissa bits; subnormals m * 2^-4, largest number 28, no NaN / Inf) — the weight side of the
+// reference's mxfp6 x mxfp8 product (csrc/gemm/mxfp6_quant_kernels_sm120.cu:168-225).  The scale rule is MXFP8's with 28 in place of 448.
+// One lane = 16 consecutive elements (32 B in, 12 B = 16 codes of 6 bits out, the reference's dense little-endian string: code j of a row at bits
+// 6 j .. 6 j + 5 of the row's bytes), 2 lanes = one scale block, 8 lanes = one K-tile of a row.
+// |x| * 2^(127 - byte) <= 28 by construction; the clamp to 0x1f only keeps a NaN / Inf element (outside the contract) inside its 6 bits.
+__device__ __forceinline__ unsigned e3m2_rne(float v) {
+  const unsigned bits = __float_as_uint(v), sign = (bits >> 26) & 0x20u, mag = bits & 0x7fffffffu;
+  unsigned code;
+  if (mag >= 0x3e800000u) {  // >= 2^-2, the least normal: round the fp32 significand to 2 bits, ties to even; a carry moves into the exponent field
+    code = ((mag + 0xfffffu + ((mag >> 21) & 1u)) >> 21) - (124u << 2);
+    code = code > 0x1fu ? 0x1fu : code;
+  } else {
+    code = (unsigned)__builtin_rintf(__uint_as_float(mag) * 16.0f);  // steps of 2^-4; 4 is the least normal's code
+  }
+  return sign | code;
+}
+
+__global__ __launch_bounds__(256) void quant_mxfp6_kernel(const unsigned short* __restrict__ x, int64_t ldx, unsigned char* __restrict__ q, int64_t ldq,
+                                                          unsigned* __restrict__ sc, int64_t M, int K) {
+  const int kc = K >> 4;  // 32-byte chunks per row
+  const int64_t total = M * kc;
+  // the 8 lanes of one K-tile of one row (8 consecutive ids) are always all in range or all out of range (kc % 8 == 0)
+  for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (int64_t)gridDim.x * 256) {
+    const int64_t row = id / kc;
+    const int c = (int)(id - row * kc);
+    float v[16];
+    unpack8(*reinterpret_cast<const uint4*>(x + row * ldx + c * 16), v);
+    unpack8(*reinterpret_cast<const uint4*>(x + row * ldx + c * 16 + 8), v + 8);
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(v[j]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    const unsigned byte = e8m0_ceil(amax / 28.0f);
+    const unsigned e = 254u - byte;
+    const float inv = __uint_as_float(e >= 1u ? (e << 23) : 0x00400000u);  // 2^(127 - byte)
+    unsigned t[4];  // 4 codes = 24 bits
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      t[g] = e3m2_rne(v[4 * g] * inv) | (e3m2_rne(v[4 * g + 1] * inv) << 6) | (e3m2_rne(v[4 * g + 2] * inv) << 12) | (e3m2_rne(v[4 * g + 3] * inv) << 18);
+    unsigned* dst = reinterpret_cast<unsigned*>(q + row * ldq + c * 12);
+    dst[0] = t[0] | (t[1] << 24);
+    dst[1] = (t[1] >> 8) | (t[2] << 16);
+    dst[2] = (t[2] >> 16) | (t[3] << 8);
+    // the 4 scale bytes of a row's K-tile sit in lanes c, c+2, c+4, c+6 (8 lanes = 128 elements): gather them into one dword
+    unsigned dw = byte;
+    dw |= (unsigned)__shfl_down((int)byte, 2, 64) << 8;
+    dw |= (unsigned)__shfl_down((int)byte, 4, 64) << 16;
+    dw |= (unsigned)__shfl_down((int)byte, 6, 64) << 24;
+    if ((c & 7) == 0) sc[(int64_t)(c >> 3) * M + row] = dw;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ GEMM
 // gemm.hip: the MX mode of the 128x128-tile kernel (small shapes, no fused epilogue)
 int gemm128_mx_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
@@ -75,6 +133,12 @@ int gemm128_mx_dispatch(const void* a, int64_t lda, const void* sa, const void* 
 // gemm256.hip: the 256x256-tile ping-pong kernel with hardware block scales (large shapes)
 int gemm256_mx_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st);
+
+// the MXFP6-weight modes of the same two kernels
+int gemm128_mx6_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st);
+int gemm256_mx6_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st);
 
 }  // namespace x2v
 
@@ -136,4 +200,66 @@ extern "C" __attribute__((visibility("default"))) int x2v_gemm_mxfp8_epi(const v
                                                                         const void* bias, const float* alpha, void* y, int64_t ldy, int64_t M, int N, int K,
                                                                         int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
   return gemm_mxfp8_impl(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, 0, stream, epilogue, resid, ldr, gate);
+}
+
+// ------------------------------------------------------------------------------------------------ MXFP6 weights x MXFP8 activations
+extern "C" __attribute__((visibility("default"))) int x2v_quant_mxfp6_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t M, int K,
+                                                                          void* stream) {
+  X2V_REQUIRE(x && q && scales, X2V_E_ARG, "quant_mxfp6: null pointer");
+  X2V_REQUIRE(K > 0 && K % 128 == 0, X2V_E_SHAPE, "quant_mxfp6: K=%d must be a multiple of 128 (4 scale blocks = one K-tile of the GEMM)", K);
+  X2V_REQUIRE(ldx % 8 == 0 && ldq % 4 == 0 && ldx >= K && ldq >= K / 4 * 3 && aligned16(x) && ((uintptr_t)q % 4) == 0 && ((uintptr_t)scales % 4) == 0, X2V_E_ALIGN,
+              "quant_mxfp6: rows must be 16-byte (input) / 4-byte (output, ldq >= 3K/4 bytes) aligned, the scale table 4-byte aligned");
+  if (M <= 0) return X2V_OK;
+  const int64_t total = M * (K / 16);
+  const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(quant_mxfp6_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ldx, (unsigned char*)q, ldq,
+                     (unsigned*)scales, M, K);
+  X2V_LAUNCH_CHECK("quant_mxfp6 launch");
+  return X2V_OK;
+}
+
+// Two bodies, the MXM = 2 mode of gemm.hip's 128x128 kernel and of gemm256.hip's ping-pong kernel, chosen as for MXFP8 (gemm_mxfp8_impl): the
+// 256x256 body where gemm.hip::choose_kernel gives an fp8 product of this shape to it, and for every call with a fused epilogue.
+static int gemm_mxfp6_impl(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                           int64_t ldy, int64_t M, int N, int K, int variant, void* stream, int epilogue = X2V_EPI_NONE, const void* resid = nullptr,
+                           int64_t ldr = 0, const void* gate = nullptr) {
+  X2V_REQUIRE(a && sa && b && sb && y, X2V_E_ARG, "gemm_mxfp6_mxfp8: null pointer");
+  X2V_REQUIRE(variant >= 0 && variant <= 2, X2V_E_ARG, "gemm_mxfp6_mxfp8: unknown variant %d", variant);
+  X2V_REQUIRE(M > 0 && N > 0 && K > 0 && K % 128 == 0 && N % 8 == 0, X2V_E_SHAPE, "gemm_mxfp6_mxfp8: M=%lld N=%d K=%d (K %% 128 == 0, N %% 8 == 0)", (long long)M, N, K);
+  X2V_REQUIRE(lda % 16 == 0 && lda >= K && aligned16(a) && ldb % 4 == 0 && ldb >= K / 4 * 3 && ((uintptr_t)b % 4) == 0 && ldy % 8 == 0 && ldy >= N && aligned16(y) &&
+                  ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sb % 4) == 0 && (bias == nullptr || ((uintptr_t)bias % 8) == 0),
+              X2V_E_ALIGN, "gemm_mxfp6_mxfp8: rows of a and y 16-byte aligned, rows of b (3K/4 bytes) and the scale tables 4-byte aligned, bias 8-byte aligned");
+  X2V_REQUIRE((int64_t)(K / 128) * std::max<int64_t>(M, N) * 4 < (1ll << 32), X2V_E_SHAPE, "gemm_mxfp6_mxfp8: scale table of 4 GiB or more");
+  X2V_REQUIRE((M + 127) / 128 * (int64_t)((N + 127) / 128) < (1ll << 31), X2V_E_SHAPE, "gemm_mxfp6_mxfp8: too many tiles");
+  if (epilogue == X2V_EPI_RESIDUAL) {
+    X2V_REQUIRE(resid != nullptr, X2V_E_ARG, "gemm_mxfp6_mxfp8: residual epilogue needs resid");
+    X2V_REQUIRE(ldr % 8 == 0 && ldr >= N && aligned16(resid) && (gate == nullptr || aligned16(gate)), X2V_E_ALIGN,
+                "gemm_mxfp6_mxfp8: residual epilogue needs a 16-byte aligned residual (and gate)");
+  }
+  // lda >= K > ldb's 3K/4: the choice asked for (lda, lda) covers the span condition of both operands
+  const bool big = variant == 2 || epilogue != X2V_EPI_NONE || (variant == 0 && ldb < (1 << 24) && (x2v_gemm_kernel_choice(M, N, K, lda, lda, 1) & 0xff) == 2);
+  if (big) {
+    X2V_REQUIRE(lda < (1 << 24) && ldb < (1 << 24), X2V_E_SHAPE, "gemm_mxfp6_mxfp8: leading dimension too large for the 256x256 kernel (32-bit tile addressing)");
+    return gemm256_mx6_dispatch(epilogue, a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K / 128, resid, ldr, gate, (hipStream_t)stream);
+  }
+  return gemm128_mx6_dispatch(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K / 128, (hipStream_t)stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_mxfp6_mxfp8(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb,
+                                                                          const void* bias, const float* alpha, void* y, int64_t ldy, int64_t M, int N, int K,
+                                                                          void* stream) {
+  return gemm_mxfp6_impl(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, 0, stream);
+}
+
+// variant: 0 = automatic, 1 = 128x128-tile kernel, 2 = 256x256-tile ping-pong kernel (tests and A/B measurements)
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_mxfp6_mxfp8_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb,
+                                                                                  const void* bias, const float* alpha, void* y, int64_t ldy, int64_t M, int N,
+                                                                                  int K, int variant, void* stream) {
+  return gemm_mxfp6_impl(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, variant, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_gemm_mxfp6_mxfp8_epi(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb,
+                                                                              const void* bias, const float* alpha, void* y, int64_t ldy, int64_t M, int N, int K,
+                                                                              int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
+  return gemm_mxfp6_impl(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, 0, stream, epilogue, resid, ldr, gate);
 }

@@ -63,6 +63,10 @@ PROTOTYPES = {
     "x2v_gemm_mxfp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p],
     "x2v_gemm_mxfp8_epi": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_mxfp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
+    "x2v_quant_mxfp6_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_gemm_mxfp6_mxfp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p],
+    "x2v_gemm_mxfp6_mxfp8_epi": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "x2v_gemm_mxfp6_mxfp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
     "x2v_gemm_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_fp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
     "x2v_quant_int8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
@@ -637,6 +641,20 @@ def quant_mxfp8(x):
     return q, sc
 
 
+def quant_mxfp6(x):
+    """bf16 [M, K] → (uint8 [M, 3K/4]: e3m2 codes, the dense little-endian 6-bit string, code j of a row at bits 6j .. 6j+5 of its bytes;
+    e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp6_bf16."""
+    x2 = _row2d(_bf16(x, "x"), "x")
+    M, K = x2.shape
+    q = torch.empty((M, K // 4 * 3), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((max(K // 128, 1), M, 4), dtype=torch.uint8, device=x.device)
+    init()
+    if M == 0:
+        return q, sc
+    _check(_lib.x2v_quant_mxfp6_bf16(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), "quant_mxfp6")
+    return q, sc
+
+
 def mx_scales_rowmajor(sc):
     """[K/128, rows, 4] (kernel layout) → logical [rows, K/32]."""
     return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
@@ -648,47 +666,59 @@ def mx_scales_tiled(sc_rm):
     return sc_rm.reshape(rows, kb // 4, 4).permute(1, 0, 2).contiguous()
 
 
-def gemm_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
-    """alpha * deq(a)[M,K] @ deq(b)[N,K]^T + bias → bf16 [M,N]; scales uint8/e8m0 [K/128, rows, 4] as produced by quant_mxfp8;
-    alpha: fp32 device tensor or None."""
+def _gemm_mx(tag, fp6, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate):
+    """gemm_mxfp8 and gemm_mxfp6_mxfp8: one set of checks, the entries x2v_gemm_<tag>_variant / _epi.  fp6: b is the packed uint8 [N, 3K/4]."""
     M, K = a.shape
     N = b.shape[0]
-    for t, name in ((a, "a"), (b, "b")):
-        if t.dtype not in (torch.float8_e4m3fn, torch.uint8) or not t.is_cuda or t.stride(1) != 1:
-            raise X2VError(f"gemm_mxfp8: {name} must be a CUDA e4m3 (or raw uint8) matrix with unit inner stride")
+    if a.dtype not in (torch.float8_e4m3fn, torch.uint8) or not a.is_cuda or a.stride(1) != 1:
+        raise X2VError(f"gemm_{tag}: a must be a CUDA e4m3 (or raw uint8) matrix with unit inner stride")
+    if b.dtype not in ((torch.uint8,) if fp6 else (torch.float8_e4m3fn, torch.uint8)) or not b.is_cuda or b.stride(1) != 1:
+        raise X2VError(f"gemm_{tag}: b must be a CUDA " + ("uint8 matrix of packed e3m2 codes [N, 3K/4]" if fp6 else "e4m3 (or raw uint8) matrix") + " with unit inner stride")
     for t, name, rows in ((sa, "scales_a", M), (sb, "scales_b", N)):
         if t.element_size() != 1 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (K // 128, rows, 4):
-            raise X2VError(f"gemm_mxfp8: {name} must be the contiguous CUDA byte tensor [K/128, {rows}, 4] of quant_mxfp8, got {tuple(t.shape)}")
-    if b.shape[1] != K or K % 128:
-        raise X2VError(f"gemm_mxfp8: shapes a{tuple(a.shape)} b{tuple(b.shape)} do not agree (K % 128 == 0)")
+            raise X2VError(f"gemm_{tag}: {name} must be the contiguous CUDA byte tensor [K/128, {rows}, 4] of quant_mxfp8, got {tuple(t.shape)}")
+    if b.shape[1] != (K // 4 * 3 if fp6 else K) or K % 128:
+        raise X2VError(f"gemm_{tag}: shapes a{tuple(a.shape)} b{tuple(b.shape)} do not agree (K % 128 == 0" + (", b holds 3K/4 bytes per row)" if fp6 else ")"))
     if alpha is not None and (alpha.dtype != torch.float32 or not alpha.is_cuda):
-        raise X2VError("gemm_mxfp8: alpha must be a float32 CUDA tensor")
+        raise X2VError(f"gemm_{tag}: alpha must be a float32 CUDA tensor")
     if bias is not None:
         bias = _bf16(bias, "bias").reshape(-1)
         if bias.numel() != N:
-            raise X2VError("gemm_mxfp8: bias must have N elements")
+            raise X2VError(f"gemm_{tag}: bias must have N elements")
     if epilogue != EPI_NONE:
         if epilogue == EPI_RESIDUAL:
             out2 = _row2d(resid if out is None else out, "out")
             r2 = _row2d(_bf16(resid, "resid"), "resid")
-            gate = _vec(gate, "gemm_mxfp8 gate", N)
+            gate = _vec(gate, f"gemm_{tag} gate", N)
         else:
             out2 = torch.empty((M, N), dtype=torch.bfloat16, device=a.device) if out is None else _row2d(out, "out")
             r2 = None
         init()
         _check(
-            _lib.x2v_gemm_mxfp8_epi(_p(a), a.stride(0), _p(sa), _p(b), b.stride(0), _p(sb), _p(bias), _p(alpha), _p(out2), out2.stride(0), M, N, K, epilogue, _p(r2),
-                                    0 if r2 is None else r2.stride(0), _p(gate), _stream()),
-            "gemm_mxfp8_epi",
+            getattr(_lib, f"x2v_gemm_{tag}_epi")(_p(a), a.stride(0), _p(sa), _p(b), b.stride(0), _p(sb), _p(bias), _p(alpha), _p(out2), out2.stride(0), M, N, K, epilogue, _p(r2),
+                                                0 if r2 is None else r2.stride(0), _p(gate), _stream()),
+            f"gemm_{tag}_epi",
         )
         return out2
     out2 = torch.empty((M, N), dtype=torch.bfloat16, device=a.device) if out is None else _row2d(out, "out")
     init()
     _check(
-        _lib.x2v_gemm_mxfp8_variant(_p(a), a.stride(0), _p(sa), _p(b), b.stride(0), _p(sb), _p(bias), _p(alpha), _p(out2), out2.stride(0), M, N, K, variant, _stream()),
-        "gemm_mxfp8",
+        getattr(_lib, f"x2v_gemm_{tag}_variant")(_p(a), a.stride(0), _p(sa), _p(b), b.stride(0), _p(sb), _p(bias), _p(alpha), _p(out2), out2.stride(0), M, N, K, variant, _stream()),
+        f"gemm_{tag}",
     )
     return out2
+
+
+def gemm_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
+    """alpha * deq(a)[M,K] @ deq(b)[N,K]^T + bias → bf16 [M,N]; scales uint8/e8m0 [K/128, rows, 4] as produced by quant_mxfp8;
+    alpha: fp32 device tensor or None."""
+    return _gemm_mx("mxfp8", False, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
+
+
+def gemm_mxfp6_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
+    """gemm_mxfp8 with b = the packed e3m2 codes uint8 [N, 3K/4] and scales of quant_mxfp6; a and sa from quant_mxfp8.  variant as gemm_mxfp8 — see
+    include/x2v.h::x2v_gemm_mxfp6_mxfp8."""
+    return _gemm_mx("mxfp6_mxfp8", True, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
 
 
 def _gemm8(kind, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period):

@@ -230,7 +230,9 @@ class MMWeightMxfp8Hip(_Movable):
         w, sw, b = self.weight, self.weight_scale, self.bias
         if row_slice is not None:  # scale table [K/128, N, 4]: slice its row axis; the kernel wants it contiguous
             w, sw, b = w[row_slice], sw[:, row_slice].contiguous(), (None if b is None else b[row_slice])
-        return lib.gemm_mxfp8(xq, sx, w, sw, bias=b, epilogue=epilogue, resid=resid, gate=gate, out=out)
+        return self._gemm(xq, sx, w, sw, bias=b, epilogue=epilogue, resid=resid, gate=gate, out=out)
+
+    _gemm = staticmethod(lib.gemm_mxfp8)  # MMWeightMxfp6Hip: the fp6-weight kernel
 
     def state_dict(self, destination=None):
         destination = {} if destination is None else destination
@@ -239,6 +241,26 @@ class MMWeightMxfp8Hip(_Movable):
         if self.bias is not None:
             destination[self.bias_name] = self.bias.cpu().detach().clone()
         return destination
+
+
+@MM_WEIGHT_REGISTER("W-mxfp6-A-mxfp8-dynamic-Hip")
+class MMWeightMxfp6Hip(MMWeightMxfp8Hip):
+    """MXFP6 weights (e3m2, 4 codes in 3 bytes) x MXFP8 activations: the operator-API form of the reference's `scaled_fp6_quant` +
+    `cutlass_scaled_mxfp6_mxfp8_mm` (lightx2v_kernel/python/lightx2v_kernel/gemm.py:58-88; test_mxfp6_quant.py:20-37).  MMWeightMxfp8Hip's
+    protocol: `quantize_input` stays the MXFP8 quantiser, so a fused driver's shared quantised activation serves both classes; the weight is
+    uint8 [N, 3K/4] with the same e8m0 table [K/128, N, 4] under `<name>_scale`."""
+
+    def load(self, weight_dict):
+        w = weight_dict[self.weight_name]
+        if not w.is_cuda:
+            raise lib.X2VError(f"{self.weight_name}: MXFP6 weights are quantised by the HIP kernel at load — tensor is on {w.device}")
+        if w.dtype == torch.uint8:  # what state_dict wrote: the packed codes with their table
+            self.weight, self.weight_scale = w.contiguous(), weight_dict[self.weight_name + "_scale"].view(torch.uint8).contiguous()
+        else:
+            self.weight, self.weight_scale = lib.quant_mxfp6(w.to(torch.bfloat16).contiguous())
+        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
+
+    _gemm = staticmethod(lib.gemm_mxfp6_mxfp8)
 
 
 @RMS_WEIGHT_REGISTER("hip")

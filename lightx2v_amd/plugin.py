@@ -25,6 +25,7 @@ def register_into_reference():
         (rf.MM_WEIGHT_REGISTER, "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip", ops.MMWeightFp8Hip),
         (rf.MM_WEIGHT_REGISTER, "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip", ops.MMWeightInt8Hip),
         (rf.MM_WEIGHT_REGISTER, "W-mxfp8-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp8Hip),
+        (rf.MM_WEIGHT_REGISTER, "W-mxfp6-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp6Hip),
         (rf.ATTN_WEIGHT_REGISTER, "hip_flash", ops.HipFlashAttnWeight),
         (rf.RMS_WEIGHT_REGISTER, "hip", ops.RMSWeightHip),
         (rf.LN_WEIGHT_REGISTER, "hip", ops.LNWeightHip),
