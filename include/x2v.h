@@ -239,6 +239,18 @@ int x2v_attn_fwd_bf16_vt_batched(const void* q, int64_t ldq, int64_t q_bstride, 
                                  int64_t vt_bstride, void* o, int64_t ldo, int64_t o_bstride, int64_t Sq, int64_t Sk, int H, int B, int head_dim, float scale,
                                  int flags, void* stream);
 
+/* Block-sparse self-attention: x2v_attn_fwd_bf16_vt restricted to a static mask of 128 x 128 (query rows x keys) blocks — replaces
+ * RadialAttnWeight.apply (common/ops/attn/attn_weight.py:129-162 -> attentions/common/radial_attn.py:34-46, the block-sparse wrapper with
+ * R = C = 128 it plans and runs) for one sequence.  Operands, layouts and flags (X2V_ATTN_VT_PRESCALED only) as x2v_attn_fwd_bf16_vt, Sq == Sk.
+ * `plan` is a device table of plan_words 32-bit words built on the host from the mask (lightx2v_amd.lib.attn_block_plan, which also checks it):
+ * plan_wgs = ceil(Sq / 256) records {256-row query block, first entry, entries}, the longest walk first, then the entries
+ * (64-key tile << 2) | (bit 0: rows 0-127 of the query block attend the tile) | (bit 1: rows 128-255 do); the tile that may hold fewer than 64
+ * keys is the last entry of its record and tiles at or beyond ceil(Sk / 64) never appear.  plan_seq is the sequence length the plan was built
+ * for (a mismatch is X2V_E_SHAPE, no launch).  Keys >= Sk are excluded as in the dense kernel: the reference instead zero-pads q / k / v to a
+ * multiple of 128 and attends the padded keys with score 0 (radial_attn.py:21-31); DESIGN.md §5 has the measured difference. */
+int x2v_attn_bsr_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo, int64_t Sq, int64_t Sk,
+                             int H, int head_dim, float scale, int flags, const void* plan, int64_t plan_words, int64_t plan_seq, int plan_wgs, void* stream);
+
 /* Per-token dynamic fp8 quantisation: s[m] = amax(|x[m,:]|)/448, xq = e4m3fn(x / s) — replaces
  * vllm ops.scaled_fp8_quant(use_per_token_if_dynamic=True) / sgl_kernel.sgl_per_token_quant_fp8
  * (mm_weight.py:236-245).  xq [M,K] bytes (ld = ldq), scale fp32 [M]. */

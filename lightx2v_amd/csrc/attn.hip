@@ -330,13 +330,25 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const unsigne
 //     hash, would collide two-fold.  The DMA pieces of a wave are chosen so that h is the same for all of them (one voffset register).
 //   * a query's 64 scores of a tile sit in 4 lanes (the 4 qd of its column): row maxima of both groups cross lanes with 3 swaps
 //     (permlane16_swap, permlane32_swap, permlane16_swap) and 2 max — on the tiles whose sum guard fires only.
-template <int NW, int RESCALE_THR, bool PRESCALED, bool ROT>
+// Block-sparse form (x2v_attn_bsr_fwd_bf16_vt): the same kernel with ONE more argument, the plan table (lightx2v_amd.lib.attn_block_plan writes it): `words` 32-bit
+// words — gridDim.x records of three, heaviest walk first, then the entries.  The dense instantiations take no such argument (an empty pack), so their
+// argument block and their instruction streams are what they were (profiles/attn_bsr_isa.txt).
+struct AttnBsrTable {
+  const unsigned* tab;
+  unsigned words;
+};
+__device__ __forceinline__ AttnBsrTable attn_bsr_table() { return AttnBsrTable{nullptr, 0u}; }
+__device__ __forceinline__ AttnBsrTable attn_bsr_table(AttnBsrTable t) { return t; }
+
+template <int NW, int RESCALE_THR, bool PRESCALED, bool ROT, typename... BSR_T>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned short* __restrict__ Q, int64_t ldq,
                                                                    const unsigned short* __restrict__ Kp, int64_t ldk,
                                                                    const unsigned short* __restrict__ VTp, int64_t ldvt, unsigned short* __restrict__ O,
                                                                    int64_t ldo, int64_t Sq, int64_t Sk, float scale_log2e, unsigned k_bytes,
-                                                                   unsigned v_bytes, AttnBatch bs) {
+                                                                   unsigned v_bytes, AttnBatch bs, BSR_T... bsr_arg) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool BSR = sizeof...(BSR_T) != 0;
+  static_assert(!(BSR && ROT), "the list-driven walk has its own order");
   static_assert(NW == 8, "DMA piece assignment below is written for 4 issuing waves");
   static_assert(RESCALE_THR >= 1 && RESCALE_THR <= 30, "A9_GUARD_T is (1 << RESCALE_THR) as a float");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -351,7 +363,22 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
   // (77 MB, cache-resident) and is not bound by fabric traffic to begin with.  The mapping pays where the heads in flight do fit (Ulysses rank
   // of the same video, 5 heads: +4 %; Wan-1.3B 480p: +1.5 %): the launcher's rule (launch_attn_vt) turns it on exactly there.
   int qblk = blockIdx.x, head = blockIdx.y, seq = blockIdx.z;
-  if (bs.xcd_remap & 1) {
+  // List-driven form (BSR: the instantiations with an AttnBsrTable argument): workgroup x of the grid takes record x of the plan table — {query block, first entry, entries} —
+  // and walks that record's key tiles instead of 0 .. nt - 1.  An entry is (key tile << 2) | member bits: bit 0 = the block's first 128 query rows
+  // (waves 0-3, the early role) attend the tile, bit 1 = its last 128 rows (waves 4-7, the late role) do.  A record that points outside the table or
+  // the query rows is not walked (a stale table must not become a stray store).
+  const unsigned* ent = nullptr;
+  int nt_list = 0;
+  if constexpr (BSR) {
+    const unsigned* const bsr = attn_bsr_table(bsr_arg...).tab;
+    const unsigned bsr_words = attn_bsr_table(bsr_arg...).words;
+    const unsigned w0 = bsr[3 * blockIdx.x], w1 = bsr[3 * blockIdx.x + 1], w2 = bsr[3 * blockIdx.x + 2];
+    if ((int64_t)w0 * (NW * 32) >= Sq || w2 == 0u || w1 < 3u * gridDim.x || (uint64_t)w1 + w2 > bsr_words) return;
+    qblk = (int)w0;
+    ent = bsr + w1;
+    nt_list = (int)w2;
+  }
+  if (!BSR && (bs.xcd_remap & 1)) {
     const unsigned gx = gridDim.x, gy = gridDim.y;
     const unsigned nwg = gx * gy * gridDim.z;
     const unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
@@ -441,7 +468,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
   float lsum[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
   bool force = true;  // first tile: adopt its row max in either direction
   unsigned pw[2][2][4];  // [key group j][query group g]: 8 bf16 probabilities = the B operand of a PV MFMA
-  const int nt = (int)((Sk + AT_KV - 1) / AT_KV);
+  const int nt = BSR ? nt_list : (int)((Sk + AT_KV - 1) / AT_KV);
   // Key-tile walk.  With ROT (flag X2V_ATTN_VT_STAGGER) query block b starts (b mod 8) tiles in: co-resident workgroups then ask for a tile at
   // slightly different times (one takes the L2 miss, its followers hit) instead of all at the same instant: +1.3 % on the plain grid at Wan-14B
   // 720p in 2-step runs, -0.9 % at sustained load (round 4, A-B-A-B step times): opt-in, no driver sets it now.  Only the first nt - 1 (full) tiles rotate — logical tile t < nt - 1 is physical tile (t + rot) mod (nt - 1) — and the physical last
@@ -532,10 +559,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
     }                                                                                                                    \
     if (kt & 1) A9_SB();                                                                                                 \
   }
-#define A9_SOFTMAX(LAST_)                                                                                                \
+#define A9_SOFTMAX(LAST_, TP_) /* TP_: the tile's index among the key tiles (what the key-tail mask of the last tile counts from) */ \
   {                                                                                                                      \
-    if ((LAST_) && (int64_t)(t + 1) * AT_KV > Sk) {                                                                      \
-      const int left = (int)(Sk - (int64_t)t * AT_KV);                                                                   \
+    if ((LAST_) && (int64_t)((TP_) + 1) * AT_KV > Sk) {                                                                  \
+      const int left = (int)(Sk - (int64_t)(TP_) * AT_KV);                                                               \
       _Pragma("unroll") for (int kt = 0; kt < 4; ++kt) _Pragma("unroll") for (int r = 0; r < 4; ++r)                     \
         if (32 * (kt >> 1) + 8 * qd + 4 * (kt & 1) + r >= left) { sc[kt][0][r] = -1e30f; sc[kt][1][r] = -1e30f; }        \
     }                                                                                                                    \
@@ -585,10 +612,21 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
     }                                                                                                                    \
   }
 
+  // list-driven walk: the entries of list positions t .. t + 2 (clamped to the last one) in scalar registers, position t + 3 fetched a step ahead
+  unsigned e0 = 0u, e1 = 0u, e2 = 0u, e3 = 0u;
+  if constexpr (BSR) {
+    e0 = ent[0];
+    e1 = ent[nt > 1 ? 1 : 0];
+    e2 = ent[nt > 2 ? 2 : nt - 1];
+  }
   // ---- prologue: K(0)
   if (wid >= NW / 2) {
-    A9_DMA_K(A9_KOFF(0), 0)
-    A9_NEXT_K()
+    if constexpr (BSR) {
+      A9_DMA_K((e0 >> 2) * k_tile_bytes, 0)
+    } else {
+      A9_DMA_K(A9_KOFF(0), 0)
+      A9_NEXT_K()
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -613,50 +651,146 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
 #define A9_BAR_ODD()                                   \
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     \
   A9_BARRIER()
-  if (wid < NW / 2) {
-    A9_MATRIX(0, 16, 0, 0)
-    A9_BAR_EVEN()
-    while (t < nt - 1) {
-      A9_SOFTMAX(false)
-      A9_BAR_ODD()
-      A9_MATRIX(0, 32, 0, 1)
-      A9_BAR_EVEN()
-      if (++t >= nt - 1) break;
-      A9_SOFTMAX(false)
-      A9_BAR_ODD()
-      A9_MATRIX(0, 32, 1, 0)
-      A9_BAR_EVEN()
-      ++t;
-    }
-    A9_SOFTMAX(true)
-    A9_BAR_ODD()
-    A9_MATRIX(16, 32, t & 1, 0)
-    A9_BAR_EVEN()
-    A9_BAR_ODD()
-  } else {
-    A9_ISSUE(0)
-    A9_BAR_EVEN()
-    A9_MATRIX(0, 16, 0, 0)
-    A9_BAR_ODD()
-    while (t < nt - 1) {
-      A9_ISSUE(t + 1)
-      A9_SOFTMAX(false)
-      A9_BAR_EVEN()
-      A9_MATRIX(0, 32, 0, 1)
-      A9_BAR_ODD()
-      if (++t >= nt - 1) break;
-      A9_ISSUE(t + 1)
-      A9_SOFTMAX(false)
-      A9_BAR_EVEN()
-      A9_MATRIX(0, 32, 1, 0)
-      A9_BAR_ODD()
-      ++t;
-    }
-    A9_SOFTMAX(true)
-    A9_BAR_EVEN()
-    A9_MATRIX(16, 32, t & 1, 0)
-    A9_BAR_ODD()
+  // List-driven walk (BSR): the same two-role half-step protocol over the record's tiles.  Every wave takes every barrier and the late role issues
+  // every tile's DMA.  A wave whose 128 query rows do not attend a tile skips that tile's softmax half-step and hands P = 0 to its PV slots; it skips a
+  // matrix half-step when it attends neither of the step's tiles (QK^T of position t + 1, PV of position t).  When it attends one of the two it runs the
+  // whole half-step: the scores of an unattended tile are never read, the PV of one adds V^T . 0.  (A half-step in three forms — QK^T only, PV only, both —
+  // leaves out exactly the unattended slots and spills 758 registers: profiles/attn_bsr_isa.txt.)  The branches are on scalar registers.  `force` is
+  // cleared by the first softmax a wave actually runs, so each half adopts the maximum of ITS first member tile.  The plan puts the tile that may hold
+  // fewer than 64 keys last in a record: the key mask stays in the final softmax, counted from the entry's tile index.
+#define A9B_MEM(E_) (((E_) & mb) != 0u)
+#define A9B_FETCH() e3 = ent[t + 3 < nt ? t + 3 : nt - 1];
+#define A9B_SHIFT() \
+  e0 = e1;          \
+  e1 = e2;          \
+  e2 = e3;
+#define A9B_ISSUE(TG_, EK_, EV_) /* K of list position TG_ + 1 (entry EK_), V^T of position TG_ (entry EV_) */ \
+  if ((TG_) + 1 < nt) {                                                                                         \
+    A9_DMA_K(((EK_) >> 2) * k_tile_bytes, ((TG_) + 1) & 1)                                                      \
+  }                                                                                                             \
+  if ((TG_) < nt) {                                                                                             \
+    A9_DMA_V(((EV_) >> 2) * (unsigned)AT_K_BYTES, (TG_) & 1)                                                    \
+  }                                                                                                             \
+  A9_SB();
+#define A9B_MATRIX(VB_, KB_) /* QK^T of position t + 1 and PV of position t: one form of the half-step, left out when the wave attends neither tile */ \
+  if (A9B_MEM(e0 | e1)) {                                                                                                                                  \
+    A9_MATRIX(0, 32, VB_, KB_)                                                                                                                             \
   }
+#define A9B_SOFTMAX(LAST_) /* a tile the wave does not attend: no softmax, and P = 0 for the PV slots it may share with the next tile's QK^T */ \
+  if (A9B_MEM(e0)) {                                                                                                                            \
+    A9_SOFTMAX(LAST_, e0 >> 2)                                                                                                                  \
+  } else {                                                                                                                                      \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) _Pragma("unroll") for (int g = 0; g < 2; ++g) _Pragma("unroll") for (int e = 0; e < 4; ++e) pw[j][g][e] = 0u; \
+  }
+#define A9B_STEP_EARLY(VB_, KB_) \
+  A9B_FETCH()                    \
+  A9B_SOFTMAX(false)             \
+  A9_BAR_ODD()                   \
+  A9B_MATRIX(VB_, KB_)           \
+  A9_BAR_EVEN()                  \
+  A9B_SHIFT()
+#define A9B_STEP_LATE(VB_, KB_) \
+  A9B_FETCH()                   \
+  A9B_ISSUE(t + 1, e2, e1)      \
+  A9B_SOFTMAX(false)            \
+  A9_BAR_EVEN()                 \
+  A9B_MATRIX(VB_, KB_)          \
+  A9_BAR_ODD()                  \
+  A9B_SHIFT()
+  if constexpr (BSR) {
+    const unsigned mb = wid < NW / 2 ? 1u : 2u;
+    if (wid < NW / 2) {
+      if (A9B_MEM(e0)) {
+        A9_MATRIX(0, 16, 0, 0)
+      }
+      A9_BAR_EVEN()
+      while (t < nt - 1) {
+        A9B_STEP_EARLY(0, 1)
+        if (++t >= nt - 1) break;
+        A9B_STEP_EARLY(1, 0)
+        ++t;
+      }
+      A9B_SOFTMAX(true)
+      A9_BAR_ODD()
+      if (A9B_MEM(e0)) {
+        A9_MATRIX(16, 32, t & 1, 0)
+      }
+      A9_BAR_EVEN()
+      A9_BAR_ODD()
+    } else {
+      A9B_ISSUE(0, e1, e0)
+      A9_BAR_EVEN()
+      if (A9B_MEM(e0)) {
+        A9_MATRIX(0, 16, 0, 0)
+      }
+      A9_BAR_ODD()
+      while (t < nt - 1) {
+        A9B_STEP_LATE(0, 1)
+        if (++t >= nt - 1) break;
+        A9B_STEP_LATE(1, 0)
+        ++t;
+      }
+      A9B_SOFTMAX(true)
+      A9_BAR_EVEN()
+      if (A9B_MEM(e0)) {
+        A9_MATRIX(16, 32, t & 1, 0)
+      }
+      A9_BAR_ODD()
+    }
+  } else {
+    if (wid < NW / 2) {
+      A9_MATRIX(0, 16, 0, 0)
+      A9_BAR_EVEN()
+      while (t < nt - 1) {
+        A9_SOFTMAX(false, t)
+        A9_BAR_ODD()
+        A9_MATRIX(0, 32, 0, 1)
+        A9_BAR_EVEN()
+        if (++t >= nt - 1) break;
+        A9_SOFTMAX(false, t)
+        A9_BAR_ODD()
+        A9_MATRIX(0, 32, 1, 0)
+        A9_BAR_EVEN()
+        ++t;
+      }
+      A9_SOFTMAX(true, t)
+      A9_BAR_ODD()
+      A9_MATRIX(16, 32, t & 1, 0)
+      A9_BAR_EVEN()
+      A9_BAR_ODD()
+    } else {
+      A9_ISSUE(0)
+      A9_BAR_EVEN()
+      A9_MATRIX(0, 16, 0, 0)
+      A9_BAR_ODD()
+      while (t < nt - 1) {
+        A9_ISSUE(t + 1)
+        A9_SOFTMAX(false, t)
+        A9_BAR_EVEN()
+        A9_MATRIX(0, 32, 0, 1)
+        A9_BAR_ODD()
+        if (++t >= nt - 1) break;
+        A9_ISSUE(t + 1)
+        A9_SOFTMAX(false, t)
+        A9_BAR_EVEN()
+        A9_MATRIX(0, 32, 1, 0)
+        A9_BAR_ODD()
+        ++t;
+      }
+      A9_SOFTMAX(true, t)
+      A9_BAR_EVEN()
+      A9_MATRIX(16, 32, t & 1, 0)
+      A9_BAR_ODD()
+    }
+  }
+#undef A9B_MEM
+#undef A9B_FETCH
+#undef A9B_SHIFT
+#undef A9B_ISSUE
+#undef A9B_MATRIX
+#undef A9B_SOFTMAX
+#undef A9B_STEP_EARLY
+#undef A9B_STEP_LATE
 #undef A9_ISSUE
 #undef A9_NEXT_K
 #undef A9_NEXT_V
@@ -945,7 +1079,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_p9_kernel(const unsigned shor
   if (tc == 0 && have_prev) {                                         \
     P9_HANDOVER()                                                     \
   }                                                                   \
-  A9_SOFTMAX(false)                                                                   \
+  A9_SOFTMAX(false, t)                                                                \
   if (tc == nt - 2 && left > 1) {                                     \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  \
   }                                                                   \
@@ -1003,7 +1137,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_p9_kernel(const unsigned shor
   if (tc == 0 && have_prev) {                                         \
     P9_HANDOVER()                                                     \
   }                                                                   \
-  A9_SOFTMAX(false)                                                   \
+  A9_SOFTMAX(false, t)                                                \
   if (tc == nt - 1) {                                                 \
     P9_NEXT_BLOCK()                                                   \
   }
@@ -1226,6 +1360,36 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt(const
   hipStream_t st = (hipStream_t)stream;
   return (flags & 1) ? launch_attn_vt<8, 8, true>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags)
                      : launch_attn_vt<8, 8, false>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags);
+}
+
+// Block-sparse self-attention: x2v_attn_fwd_bf16_vt's operands plus a plan table in device memory (lightx2v_amd.lib.attn_block_plan builds and
+// checks it on the host; the kernel only refuses records that point outside the table or the query rows).  plan_seq / plan_wgs are what the plan
+// was built for: a plan of another sequence length is an error here, not a launch.
+extern "C" __attribute__((visibility("default"))) int x2v_attn_bsr_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o,
+                                                                               int64_t ldo, int64_t Sq, int64_t Sk, int H, int head_dim, float scale, int flags, const void* plan,
+                                                                               int64_t plan_words, int64_t plan_seq, int plan_wgs, void* stream) {
+  X2V_REQUIRE(q && k && vt && o && plan, X2V_E_ARG, "attn_bsr: null pointer");
+  X2V_REQUIRE(head_dim == AT_D, X2V_E_SHAPE, "attn_bsr: head_dim=%d (only 128 is built)", head_dim);
+  X2V_REQUIRE(Sq > 0 && Sq == Sk && H > 0 && H <= 65535, X2V_E_SHAPE, "attn_bsr: bad shape Sq=%lld Sk=%lld H=%d (self-attention: Sq == Sk)", (long long)Sq, (long long)Sk, H);
+  X2V_REQUIRE(plan_seq == Sq && (int64_t)plan_wgs == (Sq + 255) / 256 && plan_words >= 4ll * plan_wgs && plan_words < (1ll << 32), X2V_E_SHAPE,
+              "attn_bsr: the plan was built for %lld rows (%d query blocks, %lld words), the launch has %lld rows", (long long)plan_seq, plan_wgs, (long long)plan_words,
+              (long long)Sq);
+  X2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 64 == 0 && ldvt >= Sk && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o) &&
+                  ((uintptr_t)plan & 3) == 0,
+              X2V_E_ALIGN, "attn_bsr: rows must be 16-byte aligned, ldvt a multiple of 64");
+  X2V_REQUIRE(ldq >= (int64_t)H * AT_D && ldk >= (int64_t)H * AT_D && ldo >= (int64_t)H * AT_D, X2V_E_SHAPE, "attn_bsr: token stride smaller than H*128");
+  X2V_REQUIRE((flags & ~1) == 0, X2V_E_ARG, "attn_bsr: flags = X2V_ATTN_VT_PRESCALED");
+  if (scale <= 0.f) scale = 0.08838834764831845f;
+  const int64_t kb = (Sk - 1) * ldk * 2 + AT_D * 2, vb = ((Sk + AT_KV - 1) / AT_KV) * (int64_t)AT_D * AT_KV * 2;
+  X2V_REQUIRE(kb < (1ll << 32) - (int64_t)AT_KV * ldk * 2 && vb < (1ll << 32), X2V_E_SHAPE, "attn_bsr: K view / V^T head block spans >= 4 GiB");
+  auto kern = (flags & 1) ? attn_fwd_v9_kernel<8, 8, true, false, AttnBsrTable> : attn_fwd_v9_kernel<8, 8, false, false, AttnBsrTable>;
+  int rc = ensure_dynamic_lds((const void*)kern, 4 * AT_K_BYTES, "attn bsr attr");
+  if (rc != X2V_OK) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)plan_wgs, (unsigned)H), dim3(8 * 64), 4 * AT_K_BYTES, (hipStream_t)stream, (const unsigned short*)q, ldq, (const unsigned short*)k, ldk,
+                     (const unsigned short*)vt, ldvt, (unsigned short*)o, ldo, Sq, Sk, scale * 1.4426950408889634f, (unsigned)kb, (unsigned)vb, AttnBatch{0, 0, 0, 0, 0},
+                     AttnBsrTable{(const unsigned*)plan, (unsigned)plan_words});
+  X2V_LAUNCH_CHECK("attn bsr launch");
+  return X2V_OK;
 }
 
 // B independent sequences in one launch (grid z): sequence b reads q / k / V^T and writes o at b * {q,k,vt,o}_bstride elements from the base

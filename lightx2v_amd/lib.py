@@ -56,6 +56,7 @@ PROTOTYPES = {
     "x2v_attn_vt_launch_plan": [_i64, _i64, _i32, _i32, _i32],
     "x2v_mfma_probe_bf16": [_i32, ctypes.POINTER(_f32), _c_void_p],
     "x2v_attn_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
+    "x2v_attn_bsr_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_variant": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_quant_fp8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
     "x2v_layernorm_quant_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _f32, _c_void_p],
@@ -548,6 +549,100 @@ def attention(q, k, v, num_heads, head_dim=128, scale=0.0, out=None, variant=0, 
     _check(
         _lib.x2v_attn_fwd_bf16_variant(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(v2), v2.stride(0), _p(out2), out2.stride(0), Sq, Sk, num_heads, head_dim, scale, variant, _stream()),
         "attn_fwd",
+    )
+    return out2
+
+
+class AttnBlockPlan:
+    """What x2v_attn_bsr_fwd_bf16_vt walks for one sequence length: `table` (host, uint32) = ceil(S / 256) records {256-row query block, first entry,
+    entries}, the longest walk first, then the entries (64-key tile << 2) | bit 0: the block's rows 0-127 attend the tile | bit 1: its rows 128-255
+    do.  Tiles of a record ascend, so the tile that may hold fewer than 64 keys (the last of the sequence) ends its record, and tiles at or beyond
+    ceil(S / 64) never appear.  `device_table(device)` uploads it once per device."""
+
+    def __init__(self, table, seq_len, n_wgs, kept_blocks, union_tiles):
+        self.table, self.seq_len, self.n_wgs, self.kept_blocks, self.union_tiles = table, seq_len, n_wgs, kept_blocks, union_tiles
+        self._dev = {}
+
+    def device_table(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.table.view("int32")).to(device)
+        return self._dev[key]
+
+    def records(self):
+        """[(query block, [(tile, member bits), ..]), ..] in launch order (host-side reading of the table: tests, tools)."""
+        t = self.table
+        return [(int(t[3 * w]), [(int(e) >> 2, int(e) & 3) for e in t[int(t[3 * w + 1]) : int(t[3 * w + 1]) + int(t[3 * w + 2])]]) for w in range(self.n_wgs)]
+
+
+def attn_block_plan(mask_or_csr, Sq, Sk):
+    """The launch plan of attention_block_sparse for a static block mask: `mask_or_csr` is the bool [ceil(Sq/128), ceil(Sk/128)] block mask (tensor or
+    array), or CSR (indptr, indices) over 128-row x 128-key blocks — what the reference hands to its block-sparse wrapper (radial_attn.py:34-46,
+    R = C = 128).  Host-only (no GPU).  Raises X2VError for Sq != Sk, dimensions that are not ceil(S/128) on both sides, a block row with no
+    entry (softmax over nothing), and CSR indices out of range, unsorted or duplicated."""
+    import numpy as np
+
+    Sq, Sk = int(Sq), int(Sk)
+    if Sq != Sk or Sq <= 0:
+        raise X2VError(f"attn_block_plan: self-attention only (Sq={Sq}, Sk={Sk})")
+    nb, ntile = (Sq + 127) // 128, (Sq + 63) // 64
+    if isinstance(mask_or_csr, (tuple, list)) and len(mask_or_csr) == 2:
+        indptr, indices = (np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a).astype(np.int64).reshape(-1) for a in mask_or_csr)
+        if indptr.shape[0] != nb + 1:
+            raise X2VError(f"attn_block_plan: indptr has {indptr.shape[0]} entries, {nb} block rows need {nb + 1}")
+        if indptr[0] != 0 or indptr[-1] != indices.shape[0] or np.any(np.diff(indptr) < 0):
+            raise X2VError("attn_block_plan: indptr must start at 0, not decrease, and end at len(indices)")
+        if indices.size and (indices.min() < 0 or indices.max() >= nb):
+            raise X2VError(f"attn_block_plan: block index out of range [0, {nb})")
+        rows = np.repeat(np.arange(nb), np.diff(indptr))
+        same_row = rows[1:] == rows[:-1]
+        if np.any(same_row & (np.diff(indices) <= 0)):
+            raise X2VError("attn_block_plan: the block indices of a row must ascend strictly (unsorted or duplicated entry)")
+        mask = np.zeros((nb, nb), dtype=bool)
+        mask[rows, indices] = True
+    else:
+        mask = np.asarray(mask_or_csr.cpu() if isinstance(mask_or_csr, torch.Tensor) else mask_or_csr)
+        if mask.dtype != np.bool_ or mask.shape != (nb, nb):
+            raise X2VError(f"attn_block_plan: the mask must be bool [{nb}, {nb}] for {Sq} rows, got {mask.dtype} {tuple(mask.shape)}")
+    empty = np.flatnonzero(~mask.any(axis=1))
+    if empty.size:
+        raise X2VError(f"attn_block_plan: block row {int(empty[0])} attends no block (softmax over nothing)")
+    n_wgs = (nb + 1) // 2
+    pair = np.zeros((2 * n_wgs, nb), dtype=np.uint32)
+    pair[:nb] = mask
+    bits = pair[0::2] | (pair[1::2] << 1)  # [n_wgs, nb]: member bits per key block
+    tile_bits = np.repeat(bits, 2, axis=1)[:, :ntile]  # key block b = tiles 2b, 2b + 1
+    counts = (tile_bits != 0).sum(axis=1)
+    order = np.argsort(-counts, kind="stable")  # heaviest walk first: the grid's tail is made of the short ones
+    wg, tile = np.nonzero(tile_bits[order])  # row-major: a record's tiles ascend
+    entries = (tile.astype(np.uint32) << 2) | tile_bits[order][wg, tile]
+    starts = 3 * n_wgs + np.concatenate(([0], np.cumsum(counts[order])[:-1]))
+    table = np.empty(3 * n_wgs + entries.shape[0], dtype=np.uint32)
+    table[0 : 3 * n_wgs : 3] = order
+    table[1 : 3 * n_wgs : 3] = starts
+    table[2 : 3 * n_wgs : 3] = counts[order]
+    table[3 * n_wgs :] = entries
+    return AttnBlockPlan(table, Sq, n_wgs, int(mask.sum()), int(counts.sum()))
+
+
+def attention_block_sparse(q, k, vt, num_heads, plan, prescaled=False, out=None, scale=0.0):
+    """Self-attention restricted to the 128 x 128 blocks of `plan` (attn_block_plan) — x2v_attn_bsr_fwd_bf16_vt.  q, k [S, H*128] (any token stride),
+    vt = transpose_heads(v, H) / gemm_vt's V^T [H, ceil(S/64), 128, 64]; prescaled: q already carries scale * log2(e).  Returns out [S, H*128]."""
+    if not isinstance(plan, AttnBlockPlan):
+        raise X2VError("attention_block_sparse: plan must come from attn_block_plan")
+    q2, k2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k, "k"), "k")
+    S = q2.shape[0]
+    out2 = torch.empty((S, num_heads * 128), dtype=torch.bfloat16, device=q.device) if out is None else _row2d(_bf16(out, "out"), "out")
+    if k2.shape[0] != S or out2.shape[0] != S or min(q2.shape[1], k2.shape[1], out2.shape[1]) < num_heads * 128:
+        raise X2VError(f"attention_block_sparse: q {tuple(q2.shape)} k {tuple(k2.shape)} out {tuple(out2.shape)} do not describe one sequence of {num_heads} heads of 128")
+    if vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape) != (num_heads, (S + 63) // 64, 128, 64):
+        raise X2VError(f"attention_block_sparse: vt must be the contiguous bf16 [H, ceil(S/64), 128, 64] tensor of transpose_heads, got {tuple(vt.shape)}")
+    init()
+    tab = plan.device_table(q2.device)
+    _check(
+        _lib.x2v_attn_bsr_fwd_bf16_vt(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(vt), vt.shape[1] * 64, _p(out2), out2.stride(0), S, k2.shape[0], num_heads, 128, scale,
+                                      1 if prescaled else 0, _p(tab), tab.numel(), plan.seq_len, plan.n_wgs, _stream()),
+        "attn_bsr_fwd",
     )
     return out2
 

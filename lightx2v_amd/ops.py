@@ -412,6 +412,56 @@ class HipFlashAttnWeight:
         return {} if destination is None else destination
 
 
+class _PaddedRows:
+    """What MaskMap.queryLogMask needs of the reference's zero-padded query (radial_attn.py:21-27): a length that is a multiple of 128."""
+
+    def __init__(self, rows):
+        self.shape = ((rows + 127) // 128 * 128,)
+
+
+def radial_plan(mask_map, seq_len, sparsity_type="radial", block_size=128, decay_factor=1, model_type="wan"):
+    """The block mask of `mask_map` for a sequence of seq_len rows and its launch plan (lib.attn_block_plan), kept on the mask_map object: both are
+    static per video, like the reference's cached log_mask."""
+    cache = mask_map.__dict__.setdefault("_hip_plans", {})
+    key = (int(seq_len), sparsity_type, block_size, decay_factor, model_type)
+    if key not in cache:
+        mask = mask_map.queryLogMask(_PaddedRows(seq_len), sparsity_type, block_size=block_size, decay_factor=decay_factor, model_type=model_type)
+        cache[key] = lib.attn_block_plan(mask, seq_len, seq_len)
+    return cache[key]
+
+
+def hip_radial(q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, mask_map=None, sparsity_type="radial", block_size=128, decay_factor=1,
+               model_cls="wan"):
+    """Functional form of HipRadialAttnWeight.apply (reference: attentions/common/radial_attn.py:18-58): q, k, v [S, H, 128] of ONE sequence;
+    softmax attention restricted to mask_map's 128 x 128 block mask.  Keys at or beyond S are not attended (the reference attends its zero padding
+    with score 0)."""
+    if mask_map is None:
+        raise lib.X2VError("hip_radial: mask_map is None — the driver owns it (MaskMap(video_token_num, num_frame), lightx2v_amd.radial); the reference crashes here")
+    if q.dim() != 3 or q.shape[2] != 128 or k.shape != q.shape or v.shape != q.shape:
+        raise lib.X2VError(f"hip_radial: q / k / v must be [S, H, 128] of one sequence, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    S, H, d = q.shape
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_kv", cu_seqlens_kv)):
+        seg = _segments(cu)
+        if seg is not None and seg != [0, S]:
+            raise lib.X2VError(f"hip_radial: {name} {seg} — one sequence of {S} rows only")
+    rows = S if max_seqlen_q is None else int(max_seqlen_q)
+    if rows != S:
+        raise lib.X2VError(f"hip_radial: max_seqlen_q={rows} does not reshape a [{S}, {H}, {d}] result")
+    plan = radial_plan(mask_map, S, sparsity_type, block_size, decay_factor, model_cls[:3])
+    as2d = lambda t: t.as_strided((S, H * d), (t.stride(0), 1)) if (t.stride(2) == 1 and t.stride(1) == d) else t.reshape(S, H * d)
+    return lib.attention_block_sparse(as2d(q), as2d(k), lib.transpose_heads(as2d(v), H), H, plan)
+
+
+@ATTN_WEIGHT_REGISTER("hip_radial")
+class HipRadialAttnWeight(HipFlashAttnWeight):
+    """reference: common/ops/attn/attn_weight.py:129-162 (key radial_attn): q, k, v [S, H, 128] -> [max_seqlen_q, H*128], attention restricted to
+    mask_map's block mask (block-sparse kernel x2v_attn_bsr_fwd_bf16_vt)."""
+
+    def apply(self, q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, mask_map=None, sparsity_type="radial", block_size=128, decay_factor=1,
+              model_cls="wan"):
+        return hip_radial(q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, max_seqlen_kv, mask_map, sparsity_type, block_size, decay_factor, model_cls)
+
+
 # ------------------------------------------------------------------------------------------------ tensors / conv
 @TENSOR_REGISTER("Default")
 class DefaultTensor(_Movable):

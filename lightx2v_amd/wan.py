@@ -295,6 +295,11 @@ class WanTransformerInfer:
         self.config = config
         self.task = config["task"]
         self.attention_type = _cfg(config, "attention_type", "hip_flash")
+        # self_attn_1_type "hip_radial": self-attention restricted to radial attention's static block mask.  The driver owns the mask map, as the
+        # reference's does (transformer_infer.py:29,378; only audio_model.py:56-60 ever sets it there, from the same quantities); it is made on
+        # first use from the token grid, and the mask and its launch plan are built once per grid (ops.radial_plan keeps them on the object).
+        self.radial = _cfg(config, "self_attn_1_type", "hip_flash") == "hip_radial"
+        self.mask_map = None
         self.blocks_num = config["num_layers"]
         self.phases_num = 4
         self.num_heads = config["num_heads"]
@@ -354,6 +359,8 @@ class WanTransformerInfer:
         variant = (lib.ATTN_FAST | lib.ATTN_Q_PRESCALED) if fast else 0
         rope_args = dict(s0=self.sp_rank * s_local, eps=weights.self_attn_norm_q.eps, round_mode=self.round_mode, q_out_scale=lib.ATTN_PRESCALE if fast else 1.0)
         pa = self.parallel_attention
+        if self.radial and (pa is not None or self._pair is not None):
+            raise NotImplementedError("self_attn_1_type='hip_radial' with Ulysses (parallel_attn_type) or in the CFG pair pass: the block-sparse kernel runs one whole sequence per launch")
         if pa is not None and hasattr(pa, "attend_blocked") and x.is_cuda and self.blocked_exchange and self._blocked_ok(weights):
             # Ulysses without layout copies: the exchange buffers [N, S/N, (H/N)d] are kernel operands (ulysses.py)
             b = pa.buffers(s_local, x.shape[1], x.dtype, x.device)
@@ -386,7 +393,7 @@ class WanTransformerInfer:
             attn = self._slot_rows_zero_padding(q.new_empty(q.shape), nb, S, Sp)
             lib.attention_batched(q, k, vt, self.num_heads, nb, Sp, S, out=attn, prescaled=True, all_rows_query=False, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
             return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
-        if pa is None and fast and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
+        if pa is None and (fast or self.radial) and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
             v, vt = None, weights.self_attn_v.apply_vt(n1, self.num_heads)  # V^T from the v projection's epilogue (the attention kernel's operand)
         else:
             v, vt = weights.self_attn_v.apply(n1, **mmkw), None
@@ -396,13 +403,26 @@ class WanTransformerInfer:
         lib.rmsnorm_rope_(q, k, weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
         if pa is None:
             # the ping-pong kernel reads V^T; transposed outside the timed launch so the hook times the attention kernel alone
-            if vt is None and fast:
+            if vt is None and (fast or self.radial):
                 vt = lib.transpose_heads(v, self.num_heads)
+            if self.radial:
+                plan = self._radial_plan(grid, s_local)
+                attn = self._timed("self", lambda: lib.attention_block_sparse(q, k, vt, self.num_heads, plan, prescaled=fast))
+                return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
             # single GPU: the same key-walk form as the pair pass (SELF_ATTN_STAGGER above), so the launch forms stay bit-identical
             attn = self._timed("self", lambda: lib.attention(q, k, v, self.num_heads, self.head_dim, variant=variant | (lib.ATTN_STAGGER if (fast and SELF_ATTN_STAGGER) else 0), vt=vt))
         else:
             attn = pa(q=q, k=k, v=v if v_pending is None else v_pending, num_heads=self.num_heads, head_dim=self.head_dim, timer=self._timed, variant=variant)
         return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
+
+    def _radial_plan(self, grid, seq_len):
+        """The block-sparse launch plan of this token grid (f, h, w): mask_map = MaskMap(f * h * w, f) on first use or when the grid changes."""
+        from . import ops, radial
+
+        f, tokens = grid[0], grid[0] * grid[1] * grid[2]
+        if self.mask_map is None or (self.mask_map.video_token_num, self.mask_map.num_frame) != (tokens, f):
+            self.mask_map = radial.MaskMap(tokens, f)
+        return ops.radial_plan(self.mask_map, seq_len, "radial", 128, _cfg(self.config, "radial_decay_factor", 1), str(_cfg(self.config, "model_cls", "wan"))[:3])
 
     @staticmethod
     def _slot_rows_zero_padding(t, slots, S, Sp):
@@ -731,6 +751,8 @@ class WanModel:
         if pat:
             if pat != "ulysses":
                 raise NotImplementedError(f"parallel_attn_type={pat}: only 'ulysses' is built (the north star's SP scheme)")
+            if _cfg(config, "self_attn_1_type") == "hip_radial":
+                raise NotImplementedError("self_attn_1_type='hip_radial' with parallel_attn_type='ulysses': radial attention under Ulysses is not built")
             from . import ulysses
 
             ulysses.parallelize_wan(self)
@@ -796,7 +818,7 @@ class WanModel:
             # pair only when one forward's self-attention already fills the chip many times over (lib.attention_batched's rule)
             want = cfg_form_by_size(self.scheduler.seq_len, tr.num_heads) == "pair"
         return (bool(want) and type(tr) is WanTransformerInfer and tr.parallel_attention is None and tr.round_mode == lib.ROUND_FP32
-                and tr.attention_type == "hip_flash" and self.scheduler.latents.is_cuda)
+                and tr.attention_type == "hip_flash" and not tr.radial and self.scheduler.latents.is_cuda)
 
     def _pair_inputs(self, inputs):
         """What the pair pass starts from: (embed, grid_sizes, (x_cond, x_uncond), embed0, seq_lens, freqs, (ctx_cond, ctx_uncond)).  The two forwards

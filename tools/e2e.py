@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--tiny-vae-ckpt", default=None, help="--tiny-vae: the released taew2_1.pth (default: seeded synthetic weights)")
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--radial", type=int, default=0, metavar="ROUNDS", help='time ROUNDS denoise steps with "self_attn_1_type": "hip_radial" next to ROUNDS dense steps (A-B-A-B, same model, same process) and print that instead of a full run; single GPU')
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
     ap.add_argument("--clip-ckpt", default=None, help="i2v with --image / --encode: CLIP checkpoint (.pth / .safetensors) for the HIP image tower (default: seeded synthetic weights)")
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
@@ -145,6 +146,36 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    if a.radial:
+        # One model, two self-attention forms: the driver's switch is flipped between steps (with it on, the CFG forwards run one after the other —
+        # the pair pass is dense-only — so each column is the step a user of that configuration gets).  Every step is step 0 of the schedule.
+        if world > 1:
+            raise SystemExit("--radial: single GPU (radial attention under Ulysses is not built)")
+        tr, ms = model.transformer_infer, {False: [], True: []}
+        for on in (False, True):  # warm both forms (the mask and its plan are built here)
+            tr.radial = on
+            sch.step_pre(0)
+            model.infer(inputs)
+        fence()
+        for _ in range(a.radial):
+            for on in (False, True):
+                tr.radial = on
+                sch.step_pre(0)
+                fence()
+                t0 = time.perf_counter()
+                model.infer(inputs)
+                fence()
+                ms[on].append((time.perf_counter() - t0) * 1e3)
+        med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+        plan = next(iter(tr.mask_map._hip_plans.values()))
+        tr.radial = False
+        dense_form = "single forward" if not cfg["enable_cfg"] else "CFG pair pass" if model._pair_ok(inputs) else "two forwards (the size rule's form for this shape)"
+        nb = (plan.seq_len + 127) // 128
+        print(json.dumps({"workload": a.workload, "rounds": a.radial, "cfg": bool(cfg["enable_cfg"]), "dense_step_ms": med[False], "dense_step_ms_all": ms[False],
+                          "radial_step_ms": med[True], "radial_step_ms_all": ms[True], "radial_over_dense": med[True] / med[False], "mask_density": plan.kept_blocks / float(nb * nb),
+                          "dense_step_form": dense_form, "radial_step_form": "two forwards, one after the other" if cfg["enable_cfg"] else "single forward",
+                          "data": "synthetic weights / latents / text embeddings"}))
+        return
     fence()
     tt = time.perf_counter()
     if a.t5:  # WanRunner.run_text_encoder (wan_runner.py:178-191): both prompts in one packed pass
