@@ -251,6 +251,53 @@ int x2v_attn_fwd_bf16_vt_batched(const void* q, int64_t ldq, int64_t q_bstride, 
 int x2v_attn_bsr_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo, int64_t Sq, int64_t Sk,
                              int H, int head_dim, float scale, int flags, const void* plan, int64_t plan_words, int64_t plan_seq, int plan_wgs, void* stream);
 
+/* ---- Block-scaled fp8 self-attention (attention type "hip_mxfp8", attn_mx.hip): the slot the reference fills with sage_attn2 (8-bit QK^T, fp8 PV),
+ * with this project's own numerics; one sequence, head dim 128.  Three preparation steps and the forward; tests/attn_mx_ref.py restates all of
+ * it in float64 / NumPy.
+ *
+ * Arithmetic.  Inputs bf16 q [Sq, H*128], k, v [Sk, H*128] (any token stride).
+ *   kmean   x2v_attn_mx_kmean_f32: kmean[col] = fl32(T / (float)Sk), T = the fp32 sum over the 256-token chunks, in chunk order, of the fp32 sum of
+ *           k[token, col] over the chunk's tokens in token order (chunk c = tokens 256 c .. 256 c + 255; chunk sums start from the first token,
+ *           T from the first chunk's sum).  The order is part of the contract: the result does not depend on the launch.
+ *   Q^, K^  x2v_attn_mx_quant_qk: x' = fl32(fl32(x - mean[col]) * scale) (mean taken as 0 unless `smooth`; q is quantised with smooth = 0 and
+ *           scale = softmax scale * log2(e), or 1.0f when q already carries it; k with scale = 1.0f and, for smoothing, kmean: softmax does not
+ *           change when a per-query constant q.kmean is taken off a row of scores).  MXFP8 along the head dimension with the rule of
+ *           x2v_quant_mxfp8_bf16: per token, head and 32-channel block one e8m0 byte = the smallest power of two >= amax / 448 (fp32 quotient,
+ *           an all-zero block -> byte 0), codes = e4m3fn_rne(x' * 2^(127 - byte)).
+ *           codes: bytes [H][S_pad][128]; scales: bytes [H][S_pad][4] (one dword per token and head, byte b = channels 32 b .. 32 b + 31).
+ *           Rows S .. S_pad - 1 are written as code 0 / scale byte 0.  q: S_pad = Sq; k: S_pad = ceil(Sk / 128) * 128.
+ *   V^T^    x2v_attn_mx_quant_vt: per head and dv row one e8m0 byte per 32 consecutive keys, blocks starting at key 0, same scale rule over the
+ *           block's keys < Sk (x' = v); keys >= Sk up to the end of the last 128-key tile are code 0 and do not enter the block's amax (a block
+ *           with no key < Sk has byte 0).  No scale byte written is 0xFF (the rule saturates at 254).
+ *           codes: bytes [H][NT][128 dv][128 keys], NT = ceil(Sk / 128), keys of a tile in their natural order; scales: bytes [H][NT][128 dv][4]
+ *           (byte b = keys 32 b .. 32 b + 31 of the tile).
+ *   scores  s = Q^ . K^^T in fp32 from v_mfma_scale_f32_16x16x128_f8f6f4 (one instruction spans the head dimension and applies both operands'
+ *           scale bytes), accumulated onto C = -m, m the row's running max before the tile; keys >= Sk are excluded (score -1e30, P = 0).
+ *   P       Running max: exact, no lazy threshold (threshold 2^0).  After a tile's scores s - m_old are known, d = max(0, row max of them);
+ *           m_new = fl32(m_old + d) (the first tile adopts its row max, whatever its sign), the tile's scores become fl32(s' - d) and l and o are
+ *           multiplied by exp2(-d) wherever some row of the wave has d > 0.  P = exp2(s - m_new) <= 1 always (v_exp_f32).  l accumulates the fp32
+ *           P.  For P.V, P^ = e4m3fn_rne(P * 2^8) with operand scale byte 127 - 8 = 119: the largest P the rule allows, 1.0, is code value 256
+ *           (of 448), the smallest positive code is 2^-9, i.e. P = 2^-17, and P < 2^-18 (ties included) is flushed to 0: 17 binades of tail.
+ *           A lazy threshold of 2^T would cost T of them; T = 0 was chosen, and the rescale multiplications it adds run only in tiles where a
+ *           row maximum grows.
+ *   o       (sum over keys of P^ . V^^)/l in fp32 (MFMA accumulation, 128 keys per instruction), one rounding to bf16.
+ * Sq != Sk is allowed; Sq == 0 is a no-op; Sk == 0 is X2V_E_SHAPE. */
+
+/* Host-only: sizes[0..6] = bytes of {q codes, q scales, k codes, k scales, V^T codes, V^T scales, kmean buffer} for (Sq, Sk, H).  The kmean
+ * buffer is H*128 floats (the mean) followed by the chunk sums the two-pass reduction keeps (ceil(Sk / 256) * H*128 floats). */
+int x2v_attn_mx_sizes(int64_t Sq, int64_t Sk, int H, int64_t* sizes);
+/* kmean (see above): k bf16 [Sk, H*128], token stride ldk (even, 4-byte aligned rows); kmean: the buffer of sizes[6] bytes. */
+int x2v_attn_mx_kmean_f32(const void* k, int64_t ldk, float* kmean, int64_t Sk, int H, void* stream);
+/* Q^ / K^ (see above): x bf16 [S, H*128] (ldx % 8 == 0, 16-byte aligned); mean fp32 [H*128] (used, and required, when smooth != 0). */
+int x2v_attn_mx_quant_qk(const void* x, int64_t ldx, const float* mean, int smooth, float scale, void* codes, void* scales, int64_t S, int64_t S_pad, int H,
+                         void* stream);
+/* V^T^ (see above): v bf16 [Sk, H*128] (ldv % 8 == 0, 16-byte aligned). */
+int x2v_attn_mx_quant_vt(const void* v, int64_t ldv, void* codes, void* scales, int64_t Sk, int H, void* stream);
+/* The forward on the prepared operands (buffers of x2v_attn_mx_sizes for the same Sq, Sk, H, 16-byte aligned); o bf16 [Sq, H*128], ldo % 4 == 0,
+ * 8-byte aligned rows. */
+int x2v_attn_mx_fwd(const void* q_codes, const void* q_scales, const void* k_codes, const void* k_scales, const void* vt_codes, const void* vt_scales, void* o,
+                    int64_t ldo, int64_t Sq, int64_t Sk, int H, void* stream);
+
 /* Per-token dynamic fp8 quantisation: s[m] = amax(|x[m,:]|)/448, xq = e4m3fn(x / s) — replaces
  * vllm ops.scaled_fp8_quant(use_per_token_if_dynamic=True) / sgl_kernel.sgl_per_token_quant_fp8
  * (mm_weight.py:236-245).  xq [M,K] bytes (ld = ldq), scale fp32 [M]. */

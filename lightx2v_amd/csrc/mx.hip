@@ -28,14 +28,7 @@ namespace x2v {
 //   vecMax = max |x|;  SF = vecMax / 448;  scale byte = e8m0(SF) rounded towards +inf (smallest power of two >= SF), saturating;
 //   q = e4m3fn_rne(x * 2^-(byte-127))   — |x| * 2^-e <= 448 by construction, so the conversion never saturates.
 // An all-zero block gives byte 0 (2^-127) and zero elements (the reference's 0 * rcp(flushed denormal) = NaN there is not reproduced).
-__device__ __forceinline__ unsigned e8m0_ceil(float sf) {
-  const unsigned bits = __float_as_uint(sf);
-  const unsigned ex = bits >> 23, man = bits & 0x7fffffu;
-  unsigned byte;
-  if (ex == 0) byte = man > 0x400000u ? 1u : 0u;  // denormal SF: 2^-127 covers (0, 2^-127], 2^-126 the rest
-  else byte = ex + (man != 0u ? 1u : 0u);
-  return byte > 254u ? 254u : byte;
-}
+// e8m0_ceil lives in x2v_common.h (attn_mx.hip's quantisers use the same rule).
 
 __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const unsigned short* __restrict__ x, int64_t ldx, unsigned char* __restrict__ q, int64_t ldq,
                                                           unsigned* __restrict__ sc, int64_t M, int K) {

@@ -104,6 +104,22 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// ---- MX block scale (mx.hip's quantisers, attn_mx.hip's) ------------------------------------------------
+// e8m0 byte of the smallest power of two >= sf (sf >= 0, fp32 with denormals), saturating at 254: the scale rule of x2v_quant_mxfp8_bf16.
+__device__ __forceinline__ unsigned e8m0_ceil(float sf) {
+  const unsigned bits = __float_as_uint(sf);
+  const unsigned ex = bits >> 23, man = bits & 0x7fffffu;
+  unsigned byte;
+  if (ex == 0) byte = man > 0x400000u ? 1u : 0u;  // denormal SF: 2^-127 covers (0, 2^-127], 2^-126 the rest
+  else byte = ex + (man != 0u ? 1u : 0u);
+  return byte > 254u ? 254u : byte;
+}
+// 2^(127 - byte) as an fp32 (2^-127, a denormal, for byte 254): what a block's values are multiplied by in front of the code conversion
+__device__ __forceinline__ float e8m0_inv(unsigned byte) {
+  const unsigned e = 254u - byte;
+  return __uint_as_float(e >= 1u ? (e << 23) : 0x00400000u);
+}
+
 // ---- activations (fp32 math on a bf16-rounded input, as torch does for bf16 tensors) ------------------
 __device__ __forceinline__ float gelu_tanh_f(float x) {
   // torch: 0.5*x*(1+tanh(sqrt(2/pi)*(x+0.044715 x^3)))

@@ -58,6 +58,11 @@ PROTOTYPES = {
     "x2v_attn_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_bsr_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_variant": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
+    "x2v_attn_mx_sizes": [_i64, _i64, _i32, ctypes.POINTER(_i64)],
+    "x2v_attn_mx_kmean_f32": [_c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_attn_mx_quant_qk": [_c_void_p, _i64, _c_void_p, _i32, _f32, _c_void_p, _c_void_p, _i64, _i64, _i32, _c_void_p],
+    "x2v_attn_mx_quant_vt": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_attn_mx_fwd": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_quant_fp8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
     "x2v_layernorm_quant_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _f32, _c_void_p],
     "x2v_quant_mxfp8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
@@ -644,6 +649,76 @@ def attention_block_sparse(q, k, vt, num_heads, plan, prescaled=False, out=None,
                                       1 if prescaled else 0, _p(tab), tab.numel(), plan.seq_len, plan.n_wgs, _stream()),
         "attn_bsr_fwd",
     )
+    return out2
+
+
+def attention_mx_sizes(Sq, Sk, num_heads):
+    """Bytes of (q codes, q scales, k codes, k scales, V^T codes, V^T scales, kmean buffer) for one sequence — x2v_attn_mx_sizes (host-only)."""
+    sizes = (_i64 * 7)()
+    rc = _lib.x2v_attn_mx_sizes(Sq, Sk, num_heads, sizes)
+    if rc != 0:
+        raise X2VError(f"attention_mx_sizes failed ({rc}): {_lib.x2v_last_error().decode()}")
+    return tuple(int(s) for s in sizes)
+
+
+class AttnMxOperands:
+    """The quantised operands of attention_mx for one sequence (layouts: include/x2v.h): q_codes [H, Sq, 128], q_scales [H, Sq, 4], k_codes
+    [H, Sk_pad, 128], k_scales [H, Sk_pad, 4], vt_codes [H, NT, 128 dv, 128 keys], vt_scales [H, NT, 128 dv, 4], all uint8; kmean fp32 [H*128]
+    (None without smoothing), a view of kmean_buf, which also keeps the chunk sums of the two-pass reduction."""
+
+    def __init__(self, Sq, Sk, H, q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, kmean, kmean_buf):
+        self.Sq, self.Sk, self.H = Sq, Sk, H
+        self.q_codes, self.q_scales, self.k_codes, self.k_scales, self.vt_codes, self.vt_scales = q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales
+        self.kmean, self.kmean_buf = kmean, kmean_buf
+
+
+def attention_mx_prepare(q, k, v, num_heads, prescaled=False, smooth_k=True, scale=0.0):
+    """The three preparation steps of attention_mx: the fp32 column mean of k (x2v_attn_mx_kmean_f32, when smooth_k), MXFP8 q and k - kmean along the
+    head dimension (x2v_attn_mx_quant_qk; q is multiplied by scale * log2(e) in fp32 unless `prescaled` says it carries it already) and MXFP8 V^T
+    along the keys (x2v_attn_mx_quant_vt).  q [Sq, H*128], k, v [Sk, H*128] bf16, any token stride that is a multiple of 8.  Returns AttnMxOperands."""
+    q2, k2, v2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k, "k"), "k"), _row2d(_bf16(v, "v"), "v")
+    H, Sq, Sk = int(num_heads), q2.shape[0], k2.shape[0]
+    if H <= 0 or v2.shape[0] != Sk or min(q2.shape[1], k2.shape[1], v2.shape[1]) < H * 128:
+        raise X2VError(f"attention_mx: q {tuple(q2.shape)} k {tuple(k2.shape)} v {tuple(v2.shape)} do not describe one sequence of {H} heads of 128")
+    if Sk == 0:
+        raise X2VError("attention_mx: no keys (softmax over an empty set)")
+    attention_mx_sizes(Sq, Sk, H)  # the shape limits, before anything is allocated
+    init()
+    dev, u8 = q2.device, torch.uint8
+    nt = (Sk + 127) // 128
+    ops = AttnMxOperands(Sq, Sk, H, torch.empty((H, Sq, 128), dtype=u8, device=dev), torch.empty((H, Sq, 4), dtype=u8, device=dev),
+                         torch.empty((H, nt * 128, 128), dtype=u8, device=dev), torch.empty((H, nt * 128, 4), dtype=u8, device=dev),
+                         torch.empty((H, nt, 128, 128), dtype=u8, device=dev), torch.empty((H, nt, 128, 4), dtype=u8, device=dev), None, None)
+    st = _stream()
+    if smooth_k:
+        ops.kmean_buf = torch.empty((1 + (Sk + 255) // 256, H * 128), dtype=torch.float32, device=dev)
+        ops.kmean = ops.kmean_buf[0]
+        _check(_lib.x2v_attn_mx_kmean_f32(_p(k2), k2.stride(0), _p(ops.kmean_buf), Sk, H, st), "attn_mx_kmean")
+    if Sq > 0:
+        qs = 1.0 if prescaled else (scale * 1.4426950408889634 if scale > 0 else ATTN_PRESCALE)  # handed over as the nearest fp32
+        _check(_lib.x2v_attn_mx_quant_qk(_p(q2), q2.stride(0), None, 0, qs, _p(ops.q_codes), _p(ops.q_scales), Sq, Sq, H, st), "attn_mx_quant_qk (q)")
+    _check(_lib.x2v_attn_mx_quant_qk(_p(k2), k2.stride(0), _p(ops.kmean), 1 if smooth_k else 0, 1.0, _p(ops.k_codes), _p(ops.k_scales), Sk, nt * 128, H, st),
+           "attn_mx_quant_qk (k)")
+    _check(_lib.x2v_attn_mx_quant_vt(_p(v2), v2.stride(0), _p(ops.vt_codes), _p(ops.vt_scales), Sk, H, st), "attn_mx_quant_vt")
+    return ops
+
+
+def attention_mx(q, k, v, num_heads, prescaled=False, smooth_k=True, scale=0.0, out=None, prepared=None):
+    """Block-scaled fp8 self-attention of one sequence at head dim 128 (x2v_attn_mx_fwd; the contract is in include/x2v.h): q [Sq, H*128], k, v
+    [Sk, H*128] bf16 -> out [Sq, H*128] bf16.  prepared: the AttnMxOperands of attention_mx_prepare for the same tensors (q, k, v are then not read)."""
+    H = int(num_heads)
+    ops = attention_mx_prepare(q, k, v, H, prescaled, smooth_k, scale) if prepared is None else prepared
+    if not isinstance(ops, AttnMxOperands) or ops.H != H:
+        raise X2VError("attention_mx: prepared must come from attention_mx_prepare with the same number of heads")
+    Sq = ops.Sq
+    out2 = torch.empty((Sq, H * 128), dtype=torch.bfloat16, device=ops.k_codes.device) if out is None else _row2d(_bf16(out, "out"), "out")
+    if out2.shape[0] != Sq or out2.shape[1] < H * 128:
+        raise X2VError(f"attention_mx: out {tuple(out2.shape)} does not hold {Sq} rows of {H} heads of 128")
+    init()
+    if Sq == 0:
+        return out2
+    _check(_lib.x2v_attn_mx_fwd(_p(ops.q_codes), _p(ops.q_scales), _p(ops.k_codes), _p(ops.k_scales), _p(ops.vt_codes), _p(ops.vt_scales), _p(out2), out2.stride(0), Sq,
+                                ops.Sk, H, _stream()), "attn_mx_fwd")
     return out2
 
 

@@ -462,6 +462,34 @@ class HipRadialAttnWeight(HipFlashAttnWeight):
         return hip_radial(q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, max_seqlen_kv, mask_map, sparsity_type, block_size, decay_factor, model_cls)
 
 
+def hip_mxfp8(q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, model_cls=None, mask_map=None):
+    """Functional form of HipMxfp8AttnWeight.apply: q [Sq, H, 128], k, v [Sk, H, 128] of ONE sequence -> [Sq, H*128] by block-scaled fp8 attention
+    (lib.attention_mx: MXFP8 q and k - mean(k) along the head dimension, MXFP8 V^T along the keys, e4m3 P; the contract is in include/x2v.h).
+    It fills the slot of the reference's sage_attn2 (attn_weight.py:165-206) with this project's numerics, not the sageattention package's."""
+    if q.dim() != 3 or q.shape[2] != 128 or k.dim() != 3 or k.shape[1:] != q.shape[1:] or v.shape != k.shape:
+        raise lib.X2VError(f"hip_mxfp8: q [Sq, H, 128] and k / v [Sk, H, 128] of one sequence, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    (Sq, H, d), Sk = q.shape, k.shape[0]
+    for name, cu, S in (("cu_seqlens_q", cu_seqlens_q, Sq), ("cu_seqlens_kv", cu_seqlens_kv, Sk)):
+        seg = _segments(cu)
+        if seg is not None and seg != [0, S]:
+            raise lib.X2VError(f"hip_mxfp8: {name} {seg} — one sequence of {S} rows only")
+    rows = Sq if max_seqlen_q is None else int(max_seqlen_q)
+    if rows != Sq:
+        raise lib.X2VError(f"hip_mxfp8: max_seqlen_q={rows} does not reshape a [{Sq}, {H}, {d}] result")
+    as2d = lambda t: t.as_strided((t.shape[0], H * d), (t.stride(0), 1)) if (t.stride(2) == 1 and t.stride(1) == d) else t.reshape(t.shape[0], H * d)
+    return lib.attention_mx(as2d(q), as2d(k), as2d(v), H)
+
+
+@ATTN_WEIGHT_REGISTER("hip_mxfp8")
+class HipMxfp8AttnWeight(HipFlashAttnWeight):
+    """Block-scaled fp8 self-attention (x2v_attn_mx_*): q, k, v [S, H, 128] of one sequence -> [max_seqlen_q, H*128].  The opt-in counterpart of
+    the reference's key sage_attn2 (common/ops/attn/attn_weight.py:165-206); not registered under that key because the numerics are this
+    project's (include/x2v.h), not the package's."""
+
+    def apply(self, q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, model_cls=None, mask_map=None):
+        return hip_mxfp8(q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, max_seqlen_kv, model_cls, mask_map)
+
+
 # ------------------------------------------------------------------------------------------------ tensors / conv
 @TENSOR_REGISTER("Default")
 class DefaultTensor(_Movable):

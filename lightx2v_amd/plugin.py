@@ -11,6 +11,7 @@ After that an unchanged LightX2V config selects the HIP path by string:
     "mm_config": {"mm_type": "Hip-bf16"}   (or "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip" / "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip")
     "self_attn_1_type": "hip_flash", "cross_attn_1_type": "hip_flash", "attention_type": "hip_flash"
     "self_attn_1_type": "hip_radial"       (radial attention's block mask on the block-sparse HIP kernel; replaces the key "radial_attn")
+    "self_attn_1_type": "hip_mxfp8"        (block-scaled fp8 self-attention; fills the slot of the key "sage_attn2" with this project's numerics)
 """
 from . import hunyuan, ops, wan
 
@@ -29,6 +30,7 @@ def register_into_reference():
         (rf.MM_WEIGHT_REGISTER, "W-mxfp6-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp6Hip),
         (rf.ATTN_WEIGHT_REGISTER, "hip_flash", ops.HipFlashAttnWeight),
         (rf.ATTN_WEIGHT_REGISTER, "hip_radial", ops.HipRadialAttnWeight),
+        (rf.ATTN_WEIGHT_REGISTER, "hip_mxfp8", ops.HipMxfp8AttnWeight),
         (rf.RMS_WEIGHT_REGISTER, "hip", ops.RMSWeightHip),
         (rf.LN_WEIGHT_REGISTER, "hip", ops.LNWeightHip),
         (rf.CONV3D_WEIGHT_REGISTER, "hip_patch", ops.PatchEmbedConv3dHip),
@@ -47,6 +49,8 @@ def register_into_reference():
                 return ops.hip_flash(*args, **kwargs)
             if attention_type == "hip_radial":
                 return ops.hip_radial(*args, **kwargs)
+            if attention_type == "hip_mxfp8":
+                return ops.hip_mxfp8(*args, **kwargs)
             return _orig(attention_type, *args, **kwargs)
 
         attention._x2v_wrapped = True

@@ -300,6 +300,9 @@ class WanTransformerInfer:
         # first use from the token grid, and the mask and its launch plan are built once per grid (ops.radial_plan keeps them on the object).
         self.radial = _cfg(config, "self_attn_1_type", "hip_flash") == "hip_radial"
         self.mask_map = None
+        # self_attn_1_type "hip_mxfp8": block-scaled fp8 self-attention (lib.attention_mx) on the single-sequence path; q comes from the norm+RoPE
+        # kernel with its scale folded in, v from the plain projection.  Cross-attention stays bf16.
+        self.mx_attn = _cfg(config, "self_attn_1_type", "hip_flash") == "hip_mxfp8"
         self.blocks_num = config["num_layers"]
         self.phases_num = 4
         self.num_heads = config["num_heads"]
@@ -361,6 +364,8 @@ class WanTransformerInfer:
         pa = self.parallel_attention
         if self.radial and (pa is not None or self._pair is not None):
             raise NotImplementedError("self_attn_1_type='hip_radial' with Ulysses (parallel_attn_type) or in the CFG pair pass: the block-sparse kernel runs one whole sequence per launch")
+        if self.mx_attn and (pa is not None or self._pair is not None or self.radial):
+            raise NotImplementedError("self_attn_1_type='hip_mxfp8' with Ulysses (parallel_attn_type), in the CFG pair pass or with radial attention: the block-scaled fp8 kernel runs one whole dense sequence per launch")
         if pa is not None and hasattr(pa, "attend_blocked") and x.is_cuda and self.blocked_exchange and self._blocked_ok(weights):
             # Ulysses without layout copies: the exchange buffers [N, S/N, (H/N)d] are kernel operands (ulysses.py)
             b = pa.buffers(s_local, x.shape[1], x.dtype, x.device)
@@ -393,7 +398,7 @@ class WanTransformerInfer:
             attn = self._slot_rows_zero_padding(q.new_empty(q.shape), nb, S, Sp)
             lib.attention_batched(q, k, vt, self.num_heads, nb, Sp, S, out=attn, prescaled=True, all_rows_query=False, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
             return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
-        if pa is None and (fast or self.radial) and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
+        if pa is None and (fast or self.radial) and not self.mx_attn and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
             v, vt = None, weights.self_attn_v.apply_vt(n1, self.num_heads)  # V^T from the v projection's epilogue (the attention kernel's operand)
         else:
             v, vt = weights.self_attn_v.apply(n1, **mmkw), None
@@ -402,6 +407,10 @@ class WanTransformerInfer:
         k = weights.self_attn_k.apply(n1, **mmkw)
         lib.rmsnorm_rope_(q, k, weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
         if pa is None:
+            if self.mx_attn:  # the quantisers run outside the timed launch, as the transposition below does
+                prepared = lib.attention_mx_prepare(q, k, v, self.num_heads, prescaled=fast)
+                attn = self._timed("self", lambda: lib.attention_mx(q, k, v, self.num_heads, prepared=prepared))
+                return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
             # the ping-pong kernel reads V^T; transposed outside the timed launch so the hook times the attention kernel alone
             if vt is None and (fast or self.radial):
                 vt = lib.transpose_heads(v, self.num_heads)
@@ -753,6 +762,8 @@ class WanModel:
                 raise NotImplementedError(f"parallel_attn_type={pat}: only 'ulysses' is built (the north star's SP scheme)")
             if _cfg(config, "self_attn_1_type") == "hip_radial":
                 raise NotImplementedError("self_attn_1_type='hip_radial' with parallel_attn_type='ulysses': radial attention under Ulysses is not built")
+            if _cfg(config, "self_attn_1_type") == "hip_mxfp8":
+                raise NotImplementedError("self_attn_1_type='hip_mxfp8' with parallel_attn_type='ulysses': block-scaled fp8 attention under Ulysses is not built")
             from . import ulysses
 
             ulysses.parallelize_wan(self)
@@ -818,7 +829,7 @@ class WanModel:
             # pair only when one forward's self-attention already fills the chip many times over (lib.attention_batched's rule)
             want = cfg_form_by_size(self.scheduler.seq_len, tr.num_heads) == "pair"
         return (bool(want) and type(tr) is WanTransformerInfer and tr.parallel_attention is None and tr.round_mode == lib.ROUND_FP32
-                and tr.attention_type == "hip_flash" and not tr.radial and self.scheduler.latents.is_cuda)
+                and tr.attention_type == "hip_flash" and not tr.radial and not tr.mx_attn and self.scheduler.latents.is_cuda)
 
     def _pair_inputs(self, inputs):
         """What the pair pass starts from: (embed, grid_sizes, (x_cond, x_uncond), embed0, seq_lens, freqs, (ctx_cond, ctx_uncond)).  The two forwards

@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--radial", type=int, default=0, metavar="ROUNDS", help='time ROUNDS denoise steps with "self_attn_1_type": "hip_radial" next to ROUNDS dense steps (A-B-A-B, same model, same process) and print that instead of a full run; single GPU')
+    ap.add_argument("--mx-attn", type=int, nargs="?", const=5, default=0, metavar="ROUNDS", help='time ROUNDS (default 5) denoise steps with "self_attn_1_type": "hip_mxfp8" (block-scaled fp8 self-attention) next to ROUNDS dense steps (A-B-A-B, same model, same process) and print that instead of a full run; single GPU')
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
     ap.add_argument("--clip-ckpt", default=None, help="i2v with --image / --encode: CLIP checkpoint (.pth / .safetensors) for the HIP image tower (default: seeded synthetic weights)")
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
@@ -174,6 +175,36 @@ def main():
         print(json.dumps({"workload": a.workload, "rounds": a.radial, "cfg": bool(cfg["enable_cfg"]), "dense_step_ms": med[False], "dense_step_ms_all": ms[False],
                           "radial_step_ms": med[True], "radial_step_ms_all": ms[True], "radial_over_dense": med[True] / med[False], "mask_density": plan.kept_blocks / float(nb * nb),
                           "dense_step_form": dense_form, "radial_step_form": "two forwards, one after the other" if cfg["enable_cfg"] else "single forward",
+                          "data": "synthetic weights / latents / text embeddings"}))
+        return
+    if a.mx_attn:
+        # As --radial: one model, the driver's switch flipped between steps.  With hip_mxfp8 on, the CFG forwards never take the pair pass (it is dense-only);
+        # they run on two streams or one after the other by the size rule, so each column is the step a user of that configuration gets.  Every step is
+        # step 0 of the schedule.
+        if world > 1:
+            raise SystemExit("--mx-attn: single GPU (block-scaled fp8 attention under Ulysses is not built)")
+        tr, ms = model.transformer_infer, {False: [], True: []}
+        for on in (False, True):
+            tr.mx_attn = on
+            sch.step_pre(0)
+            model.infer(inputs)
+        fence()
+        for _ in range(a.mx_attn):
+            for on in (False, True):
+                tr.mx_attn = on
+                sch.step_pre(0)
+                fence()
+                t0 = time.perf_counter()
+                model.infer(inputs)
+                fence()
+                ms[on].append((time.perf_counter() - t0) * 1e3)
+        med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+        tr.mx_attn = False
+        two = "two forwards on two compute streams" if wan.cfg_form_by_size(sch.seq_len, tr.num_heads) == "streams" else "two forwards, one after the other"
+        dense_form = "single forward" if not cfg["enable_cfg"] else "CFG pair pass" if model._pair_ok(inputs) else two
+        print(json.dumps({"workload": a.workload, "rounds": a.mx_attn, "cfg": bool(cfg["enable_cfg"]), "dense_step_ms": med[False], "dense_step_ms_all": ms[False],
+                          "mx_step_ms": med[True], "mx_step_ms_all": ms[True], "mx_over_dense": med[True] / med[False], "box_mfma_tflops": lib.mfma_probe(500),
+                          "dense_step_form": dense_form, "mx_step_form": two if cfg["enable_cfg"] else "single forward",
                           "data": "synthetic weights / latents / text embeddings"}))
         return
     fence()
