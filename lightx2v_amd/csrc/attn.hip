@@ -1286,13 +1286,20 @@ static int attn_vt_plan(int64_t Sq, int64_t Sk, int H, int B, bool stagger, int 
   return (map_mode ? 1 : 0) | (rot_mode ? 0x100 : 0);
 }
 
+// Buffer ranges of the pre-transposed-V kernels, from a head's (and sequence's) first element: the K rows of the sequence and the V^T blocks of its
+// ceil(Sk/64) key tiles.  Buffer descriptors address 32 bits: both stay below 4 GiB, K with one key tile of rows to spare.
+static int attn_vt_spans(const char* who, int64_t Sk, int64_t ldk, int64_t* kb, int64_t* vb) {
+  *kb = (Sk - 1) * ldk * 2 + AT_D * 2, *vb = ((Sk + AT_KV - 1) / AT_KV) * (int64_t)AT_D * AT_KV * 2;
+  X2V_REQUIRE(*kb < (1ll << 32) - (int64_t)AT_KV * ldk * 2 && *vb < (1ll << 32), X2V_E_SHAPE, "%s: K view / V^T head block spans >= 4 GiB", who);
+  return X2V_OK;
+}
+
 template <int NW, int THR, bool PRESCALED>
 static int launch_attn_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo, int64_t Sq, int64_t Sk,
                           int H, float scale, hipStream_t st, int flags, int B = 1, AttnBatch bs = AttnBatch{0, 0, 0, 0, 0}) {
   const bool stagger = (flags & 2) != 0;
-  // buffer ranges from a head's (and sequence's) first element: K rows of this sequence, the V^T blocks of its ceil(Sk/64) key tiles
-  const int64_t kb = (Sk - 1) * ldk * 2 + AT_D * 2, vb = ((Sk + AT_KV - 1) / AT_KV) * (int64_t)AT_D * AT_KV * 2;
-  X2V_REQUIRE(kb < (1ll << 32) - (int64_t)AT_KV * ldk * 2 && vb < (1ll << 32), X2V_E_SHAPE, "attn: K view / V^T head block spans >= 4 GiB");
+  int64_t kb, vb;
+  if (int rc = attn_vt_spans("attn", Sk, ldk, &kb, &vb)) return rc;
   dim3 grid((unsigned)((Sq + NW * 32 - 1) / (NW * 32)), (unsigned)H, (unsigned)B);
   // Work mapping and key-walk rotation (see the kernels), measured on MI355X (profiles/r03_attn_v9_map_rot_matrix_and_pmc.txt):
   //   * the XCD-aware head-major mapping lifts the L2 hit rate from 73-79 % to 96 % and cuts the L2<->fabric traffic 6-8x at every shape, but it
@@ -1346,17 +1353,25 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_vt_launch_plan(in
   return attn_vt_plan(Sq, Sk, H, B, (flags & 2) != 0, 8 * 32, (flags & 4) != 0);
 }
 
+// What the three pre-transposed-V entries ask of q, k, V^T and o alike (X2V_OK = 0 when met); `who` is the entry's prefix in the messages, flag_mask the
+// X2V_ATTN_VT_* bits it takes.  batched: the sequences share one V^T, so the entry itself checks ldvt against all of them.
+static int check_attn_vt_args(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* o, int64_t ldo, int64_t Sq,
+                              int64_t Sk, int H, int head_dim, int flags, int flag_mask, bool batched) {
+  X2V_REQUIRE(q && k && vt && o, X2V_E_ARG, "%s: null pointer", who);
+  X2V_REQUIRE(head_dim == AT_D, X2V_E_SHAPE, "%s: head_dim=%d (only 128 is built)", who, head_dim);
+  X2V_REQUIRE(Sq > 0 && Sk > 0 && H > 0 && H <= 65535, X2V_E_SHAPE, "%s: bad shape Sq=%lld Sk=%lld H=%d", who, (long long)Sq, (long long)Sk, H);
+  X2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 64 == 0 && (batched || ldvt >= Sk) && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o),
+              X2V_E_ALIGN, "%s: rows must be 16-byte aligned, ldvt a multiple of 64", who);
+  X2V_REQUIRE(ldq >= (int64_t)H * AT_D && ldk >= (int64_t)H * AT_D && ldo >= (int64_t)H * AT_D, X2V_E_SHAPE, "%s: token stride smaller than H*128", who);
+  X2V_REQUIRE((flags & ~flag_mask) == 0, X2V_E_ARG, "%s: flags = X2V_ATTN_VT_PRESCALED%s", who, flag_mask == 7 ? " | X2V_ATTN_VT_STAGGER | X2V_ATTN_VT_ONE_WALK" : "");
+  return X2V_OK;
+}
+
 extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo,
                                                                            int64_t Sq, int64_t Sk, int H, int head_dim, float scale, int flags, void* stream) {
   if (Sq == 0 && Sk > 0 && H > 0) return X2V_OK;  // no query rows: nothing to write (empty shard)
-  X2V_REQUIRE(q && k && vt && o, X2V_E_ARG, "attn_vt: null pointer");
-  X2V_REQUIRE(head_dim == AT_D, X2V_E_SHAPE, "attn_vt: head_dim=%d (only 128 is built)", head_dim);
-  X2V_REQUIRE(Sq > 0 && Sk > 0 && H > 0 && H <= 65535, X2V_E_SHAPE, "attn_vt: bad shape Sq=%lld Sk=%lld H=%d", (long long)Sq, (long long)Sk, H);
-  X2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 64 == 0 && ldvt >= Sk && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o), X2V_E_ALIGN,
-              "attn_vt: rows must be 16-byte aligned, ldvt a multiple of 64");
-  X2V_REQUIRE(ldq >= (int64_t)H * AT_D && ldk >= (int64_t)H * AT_D && ldo >= (int64_t)H * AT_D, X2V_E_SHAPE, "attn_vt: token stride smaller than H*128");
+  if (int rc = check_attn_vt_args("attn_vt", q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, head_dim, flags, 7, false)) return rc;
   if (scale <= 0.f) scale = 0.08838834764831845f;
-  X2V_REQUIRE((flags & ~7) == 0, X2V_E_ARG, "attn_vt: flags = X2V_ATTN_VT_PRESCALED | X2V_ATTN_VT_STAGGER | X2V_ATTN_VT_ONE_WALK");
   hipStream_t st = (hipStream_t)stream;
   return (flags & 1) ? launch_attn_vt<8, 8, true>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags)
                      : launch_attn_vt<8, 8, false>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags);
@@ -1368,20 +1383,16 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt(const
 extern "C" __attribute__((visibility("default"))) int x2v_attn_bsr_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o,
                                                                                int64_t ldo, int64_t Sq, int64_t Sk, int H, int head_dim, float scale, int flags, const void* plan,
                                                                                int64_t plan_words, int64_t plan_seq, int plan_wgs, void* stream) {
-  X2V_REQUIRE(q && k && vt && o && plan, X2V_E_ARG, "attn_bsr: null pointer");
-  X2V_REQUIRE(head_dim == AT_D, X2V_E_SHAPE, "attn_bsr: head_dim=%d (only 128 is built)", head_dim);
-  X2V_REQUIRE(Sq > 0 && Sq == Sk && H > 0 && H <= 65535, X2V_E_SHAPE, "attn_bsr: bad shape Sq=%lld Sk=%lld H=%d (self-attention: Sq == Sk)", (long long)Sq, (long long)Sk, H);
+  if (int rc = check_attn_vt_args("attn_bsr", q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, head_dim, flags, 1, false)) return rc;
+  X2V_REQUIRE(plan, X2V_E_ARG, "attn_bsr: null pointer");
+  X2V_REQUIRE(((uintptr_t)plan & 3) == 0, X2V_E_ALIGN, "attn_bsr: the plan must be 4-byte aligned");
+  X2V_REQUIRE(Sq == Sk, X2V_E_SHAPE, "attn_bsr: bad shape Sq=%lld Sk=%lld (self-attention: Sq == Sk)", (long long)Sq, (long long)Sk);
   X2V_REQUIRE(plan_seq == Sq && (int64_t)plan_wgs == (Sq + 255) / 256 && plan_words >= 4ll * plan_wgs && plan_words < (1ll << 32), X2V_E_SHAPE,
               "attn_bsr: the plan was built for %lld rows (%d query blocks, %lld words), the launch has %lld rows", (long long)plan_seq, plan_wgs, (long long)plan_words,
               (long long)Sq);
-  X2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 64 == 0 && ldvt >= Sk && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o) &&
-                  ((uintptr_t)plan & 3) == 0,
-              X2V_E_ALIGN, "attn_bsr: rows must be 16-byte aligned, ldvt a multiple of 64");
-  X2V_REQUIRE(ldq >= (int64_t)H * AT_D && ldk >= (int64_t)H * AT_D && ldo >= (int64_t)H * AT_D, X2V_E_SHAPE, "attn_bsr: token stride smaller than H*128");
-  X2V_REQUIRE((flags & ~1) == 0, X2V_E_ARG, "attn_bsr: flags = X2V_ATTN_VT_PRESCALED");
   if (scale <= 0.f) scale = 0.08838834764831845f;
-  const int64_t kb = (Sk - 1) * ldk * 2 + AT_D * 2, vb = ((Sk + AT_KV - 1) / AT_KV) * (int64_t)AT_D * AT_KV * 2;
-  X2V_REQUIRE(kb < (1ll << 32) - (int64_t)AT_KV * ldk * 2 && vb < (1ll << 32), X2V_E_SHAPE, "attn_bsr: K view / V^T head block spans >= 4 GiB");
+  int64_t kb, vb;
+  if (int rc = attn_vt_spans("attn_bsr", Sk, ldk, &kb, &vb)) return rc;
   auto kern = (flags & 1) ? attn_fwd_v9_kernel<8, 8, true, false, AttnBsrTable> : attn_fwd_v9_kernel<8, 8, false, false, AttnBsrTable>;
   int rc = ensure_dynamic_lds((const void*)kern, 4 * AT_K_BYTES, "attn bsr attr");
   if (rc != X2V_OK) return rc;
@@ -1399,15 +1410,11 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt_batch
                                                                                    const void* vt, int64_t ldvt, int64_t vt_bstride, void* o, int64_t ldo, int64_t o_bstride,
                                                                                    int64_t Sq, int64_t Sk, int H, int B, int head_dim, float scale, int flags, void* stream) {
   if (Sq == 0 && Sk > 0 && H > 0 && B > 0) return X2V_OK;
-  X2V_REQUIRE(q && k && vt && o, X2V_E_ARG, "attn_vt_batched: null pointer");
-  X2V_REQUIRE(head_dim == AT_D, X2V_E_SHAPE, "attn_vt_batched: head_dim=%d (only 128 is built)", head_dim);
-  X2V_REQUIRE(Sq > 0 && Sk > 0 && H > 0 && H <= 65535 && B > 0 && B <= 65535, X2V_E_SHAPE, "attn_vt_batched: bad shape Sq=%lld Sk=%lld H=%d B=%d", (long long)Sq, (long long)Sk, H, B);
-  X2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 64 == 0 && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o) && q_bstride % 8 == 0 &&
-                  k_bstride % 8 == 0 && vt_bstride % (64 * AT_D) == 0 && o_bstride % 8 == 0,
-              X2V_E_ALIGN, "attn_vt_batched: rows must be 16-byte aligned, ldvt a multiple of 64, vt_bstride whole 64-key blocks");
-  X2V_REQUIRE(ldq >= (int64_t)H * AT_D && ldk >= (int64_t)H * AT_D && ldo >= (int64_t)H * AT_D && ldvt >= (B - 1) * (vt_bstride / AT_D) + Sk, X2V_E_SHAPE,
-              "attn_vt_batched: token stride smaller than H*128, or ldvt smaller than the stacked sequences");
-  X2V_REQUIRE((flags & ~7) == 0, X2V_E_ARG, "attn_vt_batched: flags = X2V_ATTN_VT_PRESCALED | X2V_ATTN_VT_STAGGER | X2V_ATTN_VT_ONE_WALK");
+  if (int rc = check_attn_vt_args("attn_vt_batched", q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, head_dim, flags, 7, true)) return rc;
+  X2V_REQUIRE(B > 0 && B <= 65535, X2V_E_SHAPE, "attn_vt_batched: bad shape B=%d", B);
+  X2V_REQUIRE(q_bstride % 8 == 0 && k_bstride % 8 == 0 && vt_bstride % (64 * AT_D) == 0 && o_bstride % 8 == 0, X2V_E_ALIGN,
+              "attn_vt_batched: sequence strides must keep rows 16-byte aligned, vt_bstride whole 64-key blocks");
+  X2V_REQUIRE(ldvt >= (B - 1) * (vt_bstride / AT_D) + Sk, X2V_E_SHAPE, "attn_vt_batched: ldvt smaller than the stacked sequences");
   if (scale <= 0.f) scale = 0.08838834764831845f;
   const AttnBatch bs{q_bstride, k_bstride, vt_bstride, o_bstride, 0};
   hipStream_t st = (hipStream_t)stream;

@@ -95,20 +95,12 @@ __global__ __launch_bounds__(256) void mx_quant_qk_kernel(const unsigned short* 
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
     amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
     amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-    const unsigned byte = e8m0_ceil(amax / 448.0f);
-    const float inv = e8m0_inv(byte);
-    unsigned lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, hi, true);
+    unsigned w[2];
+    const unsigned byte = mxfp8_block<8>(v, amax, w);
     const int head = c >> 4, c16 = c & 15;
     const int64_t orow = (int64_t)head * S_pad + row;
-    *reinterpret_cast<uint2*>(q + orow * 128 + c16 * 8) = make_uint2(lo, hi);
-    unsigned dw = byte;
-    dw |= (unsigned)__shfl_down((int)byte, 4, 64) << 8;
-    dw |= (unsigned)__shfl_down((int)byte, 8, 64) << 16;
-    dw |= (unsigned)__shfl_down((int)byte, 12, 64) << 24;
+    *reinterpret_cast<uint2*>(q + orow * 128 + c16 * 8) = make_uint2(w[0], w[1]);
+    const unsigned dw = e8m0_gather4(byte, 4);
     if (c16 == 0) sc[orow] = dw;
   }
 }
@@ -139,16 +131,8 @@ __global__ __launch_bounds__(256) void mx_quant_vt_kernel(const unsigned short* 
       f[j] = bf2f(tile[(32 * blk + j) * 128 + dv]);
       amax = fmaxf(amax, fabsf(f[j]));
     }
-    const unsigned byte = e8m0_ceil(amax / 448.0f);
-    const float inv = e8m0_inv(byte);
     unsigned w[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      unsigned d = 0;
-      d = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * j] * inv, f[4 * j + 1] * inv, d, false);
-      d = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * j + 2] * inv, f[4 * j + 3] * inv, d, true);
-      w[j] = d;
-    }
+    const unsigned byte = mxfp8_block<32>(f, amax, w);
     unsigned char* dst = q + (trow + dv) * 128 + blk * 32;
     *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
     *reinterpret_cast<uint4*>(dst + 16) = make_uint4(w[4], w[5], w[6], w[7]);

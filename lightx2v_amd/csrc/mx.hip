@@ -49,20 +49,11 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const unsigned short* 
     amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
     amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
     if (!ok) continue;
-    const unsigned byte = e8m0_ceil(amax / 448.0f);
-    const unsigned e = 254u - byte;
-    const float inv = __uint_as_float(e >= 1u ? (e << 23) : 0x00400000u);  // 2^(127 - byte)
-    unsigned lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, hi, true);
-    *reinterpret_cast<uint2*>(q + row * ldq + c * 8) = make_uint2(lo, hi);
-    // the 4 scale bytes of a row's K-tile sit in lanes c, c+4, c+8, c+12 (16 lanes = 128 elements): gather them into one dword
-    unsigned dw = byte;
-    dw |= (unsigned)__shfl_down((int)byte, 4, 64) << 8;
-    dw |= (unsigned)__shfl_down((int)byte, 8, 64) << 16;
-    dw |= (unsigned)__shfl_down((int)byte, 12, 64) << 24;
+    unsigned w[2];
+    const unsigned byte = mxfp8_block<8>(v, amax, w);
+    *reinterpret_cast<uint2*>(q + row * ldq + c * 8) = make_uint2(w[0], w[1]);
+    // the 4 scale bytes of a row's K-tile sit in lanes c, c+4, c+8, c+12 (16 lanes = 128 elements)
+    const unsigned dw = e8m0_gather4(byte, 4);
     if ((c & 15) == 0) sc[(int64_t)(c >> 4) * M + row] = dw;
   }
 }
@@ -100,8 +91,7 @@ __global__ __launch_bounds__(256) void quant_mxfp6_kernel(const unsigned short* 
     for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(v[j]));
     amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
     const unsigned byte = e8m0_ceil(amax / 28.0f);
-    const unsigned e = 254u - byte;
-    const float inv = __uint_as_float(e >= 1u ? (e << 23) : 0x00400000u);  // 2^(127 - byte)
+    const float inv = e8m0_inv(byte);
     unsigned t[4];  // 4 codes = 24 bits
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -110,11 +100,8 @@ __global__ __launch_bounds__(256) void quant_mxfp6_kernel(const unsigned short* 
     dst[0] = t[0] | (t[1] << 24);
     dst[1] = (t[1] >> 8) | (t[2] << 16);
     dst[2] = (t[2] >> 16) | (t[3] << 8);
-    // the 4 scale bytes of a row's K-tile sit in lanes c, c+2, c+4, c+6 (8 lanes = 128 elements): gather them into one dword
-    unsigned dw = byte;
-    dw |= (unsigned)__shfl_down((int)byte, 2, 64) << 8;
-    dw |= (unsigned)__shfl_down((int)byte, 4, 64) << 16;
-    dw |= (unsigned)__shfl_down((int)byte, 6, 64) << 24;
+    // the 4 scale bytes of a row's K-tile sit in lanes c, c+2, c+4, c+6 (8 lanes = 128 elements)
+    const unsigned dw = e8m0_gather4(byte, 2);
     if ((c & 7) == 0) sc[(int64_t)(c >> 3) * M + row] = dw;
   }
 }

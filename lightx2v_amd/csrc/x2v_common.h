@@ -119,6 +119,25 @@ __device__ __forceinline__ float e8m0_inv(unsigned byte) {
   const unsigned e = 254u - byte;
   return __uint_as_float(e >= 1u ? (e << 23) : 0x00400000u);
 }
+// The MXFP8 block step on N values of a block whose max |x| is amax: returns the block's scale byte e8m0_ceil(amax / 448) and writes the values times
+// 2^(127 - byte) as e4m3 codes (RNE; never saturating, since |x| * 2^(127 - byte) <= 448), value j in byte j of the N / 4 dwords w.
+template <int N>
+__device__ __forceinline__ unsigned mxfp8_block(const float* v, float amax, unsigned* w) {
+  const unsigned byte = e8m0_ceil(amax / 448.0f);
+  const float inv = e8m0_inv(byte);
+#pragma unroll
+  for (int j = 0; j < N / 4; ++j) {
+    unsigned d = 0;
+    d = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, d, false);
+    d = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, d, true);
+    w[j] = d;
+  }
+  return byte;
+}
+// The scale bytes of lanes c, c + s, c + 2 s, c + 3 s (the 4 scale blocks of a row's 128-element K-tile) as one dword in lane c
+__device__ __forceinline__ unsigned e8m0_gather4(unsigned byte, int s) {
+  return byte | (unsigned)__shfl_down((int)byte, s, 64) << 8 | (unsigned)__shfl_down((int)byte, 2 * s, 64) << 16 | (unsigned)__shfl_down((int)byte, 3 * s, 64) << 24;
+}
 
 // ---- activations (fp32 math on a bf16-rounded input, as torch does for bf16 tensors) ------------------
 __device__ __forceinline__ float gelu_tanh_f(float x) {

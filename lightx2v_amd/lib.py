@@ -192,6 +192,19 @@ def _bf16(t, name):
     return t
 
 
+def _vt_operand(vt, who, num_heads, rows):  # vt as an attention operand: the V^T of transpose_heads / gemm_vt over `rows` key rows
+    if vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape) != (num_heads, (rows + 63) // 64, 128, 64):
+        raise X2VError(f"{who}: vt must be the contiguous bf16 [H, ceil(rows/64), 128, 64] tensor of transpose_heads over {rows} rows, got {tuple(vt.shape)}")
+    return vt
+
+
+def _attn_out(out, who, rows, width, device):  # an attention call's bf16 result [rows, width]: `out` checked (its token stride may be longer), or a new tensor
+    out2 = torch.empty((rows, width), dtype=torch.bfloat16, device=device) if out is None else _row2d(_bf16(out, "out"), "out")
+    if out2.shape[0] != rows or out2.shape[1] < width:
+        raise X2VError(f"{who}: out is {tuple(out2.shape)}, expected {rows} rows of at least {width} elements")
+    return out2
+
+
 def _vec(t, name, n=None, dtype=torch.bfloat16):
     """A per-channel operand (bias / norm weight / gate / scale row): None passes through; otherwise a contiguous device vector of
     `dtype` with `n` elements (any leading unit dims) — the C side only sees a pointer, so a wrong dtype would be silent."""
@@ -439,11 +452,8 @@ def attention_batched(q, k, vt, num_heads, batch, rows_per_seq, seq_len, out=Non
     rows = batch * rows_per_seq
     if rows_per_seq % 64 or not 0 < seq_len <= rows_per_seq or q2.shape[0] != rows or k2.shape[0] != rows or min(q2.shape[1], k2.shape[1]) < num_heads * 128:
         raise X2VError(f"attention_batched: q {tuple(q2.shape)} k {tuple(k2.shape)} do not hold {batch} sequences of {rows_per_seq} (multiple of 64) rows x {num_heads} heads")
-    if vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape) != (num_heads, rows // 64, 128, 64):
-        raise X2VError(f"attention_batched: vt must be the contiguous bf16 [H, rows/64, 128, 64] tensor over the stacked rows, got {tuple(vt.shape)}")
-    out2 = torch.empty((rows, num_heads * 128), dtype=torch.bfloat16, device=q.device) if out is None else _row2d(_bf16(out, "out"), "out")
-    if out2.shape[0] != rows or out2.shape[1] < num_heads * 128:
-        raise X2VError(f"attention_batched: out is {tuple(out2.shape)}")
+    _vt_operand(vt, "attention_batched", num_heads, rows)  # over the stacked rows
+    out2 = _attn_out(out, "attention_batched", rows, num_heads * 128, q.device)
     init()
     sq = rows_per_seq if all_rows_query else seq_len
     if one_launch is None:
@@ -532,19 +542,16 @@ def attention(q, k, v, num_heads, head_dim=128, scale=0.0, out=None, variant=0, 
         v = k
     q2, k2, v2 = as2d(q, "q"), as2d(k, "k"), as2d(v, "v")
     Sq, Sk = q2.shape[0], k2.shape[0]
-    out2 = torch.empty((Sq, num_heads * head_dim), dtype=torch.bfloat16, device=q.device) if out is None else _row2d(_bf16(out, "out"), "out")
-    if out2.shape[0] != Sq or v2.shape[0] != Sk or min(q2.shape[1], k2.shape[1], v2.shape[1], out2.shape[1]) < num_heads * head_dim:
-        raise X2VError(f"attention: q {tuple(q2.shape)} k {tuple(k2.shape)} v {tuple(v2.shape)} out {tuple(out2.shape)} do not describe {num_heads} heads of {head_dim}")
+    out2 = _attn_out(out, "attention", Sq, num_heads * head_dim, q.device)
+    if v2.shape[0] != Sk or min(q2.shape[1], k2.shape[1], v2.shape[1]) < num_heads * head_dim:
+        raise X2VError(f"attention: q {tuple(q2.shape)} k {tuple(k2.shape)} v {tuple(v2.shape)} do not describe {num_heads} heads of {head_dim}")
     if Sk == 0:
         raise X2VError("attention: no keys (softmax over an empty set)")
     init()
     if Sq == 0:
         return out2
     if (variant & 0xFF) == ATTN_FAST:
-        if vt is None:
-            vt = transpose_heads(v2, num_heads)
-        elif vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape) != (num_heads, (Sk + 63) // 64, 128, 64):
-            raise X2VError(f"attention: vt must be the contiguous bf16 [H, ceil(Sk/64), 128, 64] tensor of transpose_heads, got {tuple(vt.shape)}")
+        vt = transpose_heads(v2, num_heads) if vt is None else _vt_operand(vt, "attention", num_heads, Sk)
         _check(
             _lib.x2v_attn_fwd_bf16_vt(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(vt), vt.shape[1] * 64, _p(out2), out2.stride(0), Sq, Sk, num_heads, head_dim, scale,
                                       (1 if (variant & ATTN_Q_PRESCALED) else 0) | (2 if (variant & ATTN_STAGGER) else 0) | (4 if (variant & ATTN_ONE_WALK) else 0), _stream()),
@@ -637,11 +644,10 @@ def attention_block_sparse(q, k, vt, num_heads, plan, prescaled=False, out=None,
         raise X2VError("attention_block_sparse: plan must come from attn_block_plan")
     q2, k2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k, "k"), "k")
     S = q2.shape[0]
-    out2 = torch.empty((S, num_heads * 128), dtype=torch.bfloat16, device=q.device) if out is None else _row2d(_bf16(out, "out"), "out")
-    if k2.shape[0] != S or out2.shape[0] != S or min(q2.shape[1], k2.shape[1], out2.shape[1]) < num_heads * 128:
-        raise X2VError(f"attention_block_sparse: q {tuple(q2.shape)} k {tuple(k2.shape)} out {tuple(out2.shape)} do not describe one sequence of {num_heads} heads of 128")
-    if vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape) != (num_heads, (S + 63) // 64, 128, 64):
-        raise X2VError(f"attention_block_sparse: vt must be the contiguous bf16 [H, ceil(S/64), 128, 64] tensor of transpose_heads, got {tuple(vt.shape)}")
+    out2 = _attn_out(out, "attention_block_sparse", S, num_heads * 128, q.device)
+    if k2.shape[0] != S or min(q2.shape[1], k2.shape[1]) < num_heads * 128:
+        raise X2VError(f"attention_block_sparse: q {tuple(q2.shape)} k {tuple(k2.shape)} do not describe one sequence of {num_heads} heads of 128")
+    _vt_operand(vt, "attention_block_sparse", num_heads, S)
     init()
     tab = plan.device_table(q2.device)
     _check(
@@ -711,9 +717,7 @@ def attention_mx(q, k, v, num_heads, prescaled=False, smooth_k=True, scale=0.0, 
     if not isinstance(ops, AttnMxOperands) or ops.H != H:
         raise X2VError("attention_mx: prepared must come from attention_mx_prepare with the same number of heads")
     Sq = ops.Sq
-    out2 = torch.empty((Sq, H * 128), dtype=torch.bfloat16, device=ops.k_codes.device) if out is None else _row2d(_bf16(out, "out"), "out")
-    if out2.shape[0] != Sq or out2.shape[1] < H * 128:
-        raise X2VError(f"attention_mx: out {tuple(out2.shape)} does not hold {Sq} rows of {H} heads of 128")
+    out2 = _attn_out(out, "attention_mx", Sq, H * 128, ops.k_codes.device)
     init()
     if Sq == 0:
         return out2

@@ -430,6 +430,23 @@ def radial_plan(mask_map, seq_len, sparsity_type="radial", block_size=128, decay
     return cache[key]
 
 
+def _one_sequence_2d(fn, q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, self_attention=False):
+    """The operator contract of hip_radial and hip_mxfp8: q [Sq, H, 128], k, v [Sk, H, 128] of ONE sequence (self_attention: Sq == Sk), which is also what
+    cu_seqlens and max_seqlen_q must say where given.  Returns the 2-D views [S, H*128] of q, k, v (no copy where the heads are packed)."""
+    if q.dim() != 3 or q.shape[2] != 128 or k.dim() != 3 or k.shape[1:] != q.shape[1:] or v.shape != k.shape or (self_attention and k.shape != q.shape):
+        raise lib.X2VError(f"{fn}: q [Sq, H, 128] and k / v [Sk, H, 128] of one sequence{' with Sq == Sk' if self_attention else ''}, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    (Sq, H, d), Sk = q.shape, k.shape[0]
+    for name, cu, S in (("cu_seqlens_q", cu_seqlens_q, Sq), ("cu_seqlens_kv", cu_seqlens_kv, Sk)):
+        seg = _segments(cu)
+        if seg is not None and seg != [0, S]:
+            raise lib.X2VError(f"{fn}: {name} {seg} — one sequence of {S} rows only")
+    rows = Sq if max_seqlen_q is None else int(max_seqlen_q)
+    if rows != Sq:
+        raise lib.X2VError(f"{fn}: max_seqlen_q={rows} does not reshape a [{Sq}, {H}, {d}] result")
+    as2d = lambda t: t.as_strided((t.shape[0], H * d), (t.stride(0), 1)) if (t.stride(2) == 1 and t.stride(1) == d) else t.reshape(t.shape[0], H * d)
+    return as2d(q), as2d(k), as2d(v)
+
+
 def hip_radial(q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, mask_map=None, sparsity_type="radial", block_size=128, decay_factor=1,
                model_cls="wan"):
     """Functional form of HipRadialAttnWeight.apply (reference: attentions/common/radial_attn.py:18-58): q, k, v [S, H, 128] of ONE sequence;
@@ -437,19 +454,10 @@ def hip_radial(q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None
     with score 0)."""
     if mask_map is None:
         raise lib.X2VError("hip_radial: mask_map is None — the driver owns it (MaskMap(video_token_num, num_frame), lightx2v_amd.radial); the reference crashes here")
-    if q.dim() != 3 or q.shape[2] != 128 or k.shape != q.shape or v.shape != q.shape:
-        raise lib.X2VError(f"hip_radial: q / k / v must be [S, H, 128] of one sequence, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
-    S, H, d = q.shape
-    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_kv", cu_seqlens_kv)):
-        seg = _segments(cu)
-        if seg is not None and seg != [0, S]:
-            raise lib.X2VError(f"hip_radial: {name} {seg} — one sequence of {S} rows only")
-    rows = S if max_seqlen_q is None else int(max_seqlen_q)
-    if rows != S:
-        raise lib.X2VError(f"hip_radial: max_seqlen_q={rows} does not reshape a [{S}, {H}, {d}] result")
+    q2, k2, v2 = _one_sequence_2d("hip_radial", q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, self_attention=True)
+    S, H = q.shape[:2]
     plan = radial_plan(mask_map, S, sparsity_type, block_size, decay_factor, model_cls[:3])
-    as2d = lambda t: t.as_strided((S, H * d), (t.stride(0), 1)) if (t.stride(2) == 1 and t.stride(1) == d) else t.reshape(S, H * d)
-    return lib.attention_block_sparse(as2d(q), as2d(k), lib.transpose_heads(as2d(v), H), H, plan)
+    return lib.attention_block_sparse(q2, k2, lib.transpose_heads(v2, H), H, plan)
 
 
 @ATTN_WEIGHT_REGISTER("hip_radial")
@@ -466,18 +474,7 @@ def hip_mxfp8(q, k, v, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None,
     """Functional form of HipMxfp8AttnWeight.apply: q [Sq, H, 128], k, v [Sk, H, 128] of ONE sequence -> [Sq, H*128] by block-scaled fp8 attention
     (lib.attention_mx: MXFP8 q and k - mean(k) along the head dimension, MXFP8 V^T along the keys, e4m3 P; the contract is in include/x2v.h).
     It fills the slot of the reference's sage_attn2 (attn_weight.py:165-206) with this project's numerics, not the sageattention package's."""
-    if q.dim() != 3 or q.shape[2] != 128 or k.dim() != 3 or k.shape[1:] != q.shape[1:] or v.shape != k.shape:
-        raise lib.X2VError(f"hip_mxfp8: q [Sq, H, 128] and k / v [Sk, H, 128] of one sequence, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
-    (Sq, H, d), Sk = q.shape, k.shape[0]
-    for name, cu, S in (("cu_seqlens_q", cu_seqlens_q, Sq), ("cu_seqlens_kv", cu_seqlens_kv, Sk)):
-        seg = _segments(cu)
-        if seg is not None and seg != [0, S]:
-            raise lib.X2VError(f"hip_mxfp8: {name} {seg} — one sequence of {S} rows only")
-    rows = Sq if max_seqlen_q is None else int(max_seqlen_q)
-    if rows != Sq:
-        raise lib.X2VError(f"hip_mxfp8: max_seqlen_q={rows} does not reshape a [{Sq}, {H}, {d}] result")
-    as2d = lambda t: t.as_strided((t.shape[0], H * d), (t.stride(0), 1)) if (t.stride(2) == 1 and t.stride(1) == d) else t.reshape(t.shape[0], H * d)
-    return lib.attention_mx(as2d(q), as2d(k), as2d(v), H)
+    return lib.attention_mx(*_one_sequence_2d("hip_mxfp8", q, k, v, cu_seqlens_q, cu_seqlens_kv, max_seqlen_q), q.shape[1])
 
 
 @ATTN_WEIGHT_REGISTER("hip_mxfp8")

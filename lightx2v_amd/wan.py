@@ -351,7 +351,6 @@ class WanTransformerInfer:
         # norm1 has no affine (transformer_weights.py:127-129); quantised operator classes get n1 quantised once for q, k and v
         n1, mmkw = _ln_then_mm_input(weights.self_attn_q, x, scale=scale_msa, shift=shift_msa, eps=weights.norm1.eps)
         grid = tuple(int(g) for g in grid_sizes[0].tolist())
-        s_local = x.shape[0]
         if freqs.is_complex():  # driven by the reference's WanPreInfer: complex128 [1024, 64] (pre_infer.py:12-19)
             if self._rope_cs is None or self._rope_cs.device != x.device:
                 self._rope_cs = torch.stack([freqs.real, freqs.imag], dim=-1).to(torch.float32).contiguous().to(x.device)
@@ -360,69 +359,91 @@ class WanTransformerInfer:
         # its one rounding, and the attention kernel variant that expects that skips the per-score FMA (x2v.h)
         fast = self.round_mode == lib.ROUND_FP32
         variant = (lib.ATTN_FAST | lib.ATTN_Q_PRESCALED) if fast else 0
-        rope_args = dict(s0=self.sp_rank * s_local, eps=weights.self_attn_norm_q.eps, round_mode=self.round_mode, q_out_scale=lib.ATTN_PRESCALE if fast else 1.0)
+        rope_args = dict(s0=self.sp_rank * x.shape[0], eps=weights.self_attn_norm_q.eps, round_mode=self.round_mode, q_out_scale=lib.ATTN_PRESCALE if fast else 1.0)
+        self._refuse_unbuilt_self_attn()
+        attn = getattr(self, "_self_attn_" + self._self_attn_route(weights, x))(weights, x, n1, mmkw, freqs, grid, fast, variant, rope_args)
+        return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)  # "ulysses_blocked": K-blocked attn
+
+    def _refuse_unbuilt_self_attn(self):
+        """Per call, not once: radial, _pair and parallel_attention are plain attributes that a caller may set on a live object."""
         pa = self.parallel_attention
         if self.radial and (pa is not None or self._pair is not None):
             raise NotImplementedError("self_attn_1_type='hip_radial' with Ulysses (parallel_attn_type) or in the CFG pair pass: the block-sparse kernel runs one whole sequence per launch")
         if self.mx_attn and (pa is not None or self._pair is not None or self.radial):
             raise NotImplementedError("self_attn_1_type='hip_mxfp8' with Ulysses (parallel_attn_type), in the CFG pair pass or with radial attention: the block-scaled fp8 kernel runs one whole dense sequence per launch")
+
+    def _self_attn_route(self, weights, x):
+        """Which _self_attn_<route> serves this call; no side effects.  "single": one sequence per launch on one GPU, or Ulysses in its row-major form."""
+        pa = self.parallel_attention
         if pa is not None and hasattr(pa, "attend_blocked") and x.is_cuda and self.blocked_exchange and self._blocked_ok(weights):
-            # Ulysses without layout copies: the exchange buffers [N, S/N, (H/N)d] are kernel operands (ulysses.py)
-            b = pa.buffers(s_local, x.shape[1], x.dtype, x.device)
-            weights.self_attn_v.apply(n1, out=b["sv"], **mmkw)  # v needs no norm / RoPE: projected first, straight into its send buffer,
-            v_pending = pa.begin_exchange_blocked(b["sv"], b["rv"])  # and exchanged under the q / k projections and the norm+RoPE kernel
-            q = weights.self_attn_q.apply(n1, **mmkw)
-            k = weights.self_attn_k.apply(n1, **mmkw)
-            lib.rmsnorm_rope_blocked(q, k, weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, b["sq"], b["sk"], **rope_args)
-            attn = pa.attend_blocked(b, self.num_heads, self.head_dim, timer=self._timed, variant=variant, v_pending=v_pending)
-            return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)  # K-blocked x
-        # Ulysses, row-major form: v is projected first and its seq→head exchange runs on the communication stream under the q and k
-        # projections and the norm+RoPE kernel
-        if self._pair is not None:
-            # both CFG forwards in one pass: projections and row kernels run on the stacked rows, the two self-attentions are one launch
-            # (block 0 of the CFG-shared front: one slot, one self-attention — the same batched entry and key walk, so a row's bits do not change)
-            S, Sp = self._pair
-            nb = s_local // Sp
-            if not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
-                vt = weights.self_attn_v.apply_vt(n1, self.num_heads)
-            else:
-                vt = lib.transpose_heads(weights.self_attn_v.apply(n1, **mmkw), self.num_heads)
-            q = weights.self_attn_q.apply(n1, **mmkw)
-            k = weights.self_attn_k.apply(n1, **mmkw)
-            for b in range(nb):  # token b*Sp + i of either forward sits at grid position i
-                rows = slice(b * Sp, b * Sp + S)
-                lib.rmsnorm_rope_(q[rows], k[rows], weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
-            # Only the S token rows of a slot are queries, as in a separate forward: the attention kernel decides its lazy O rescale per WAVE
-            # (attn.hip: `__any` over the wave's rows), so a padding row that was a query could switch the rescale on for the token rows sharing
-            # its wave and change their low bits.  The padding rows of the output are zero-filled instead (finite: they become V^T columns).
-            attn = self._slot_rows_zero_padding(q.new_empty(q.shape), nb, S, Sp)
-            lib.attention_batched(q, k, vt, self.num_heads, nb, Sp, S, out=attn, prescaled=True, all_rows_query=False, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
-            return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
-        if pa is None and (fast or self.radial) and not self.mx_attn and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
-            v, vt = None, weights.self_attn_v.apply_vt(n1, self.num_heads)  # V^T from the v projection's epilogue (the attention kernel's operand)
+            return "ulysses_blocked"
+        return "pair" if self._pair is not None else "single"
+
+    # "vt_epilogue": V^T from the v projection's epilogue (the attention kernel's operand); "vt_transposed": row-major v, transposed after norm+RoPE
+    # (the ping-pong kernel reads V^T); "row_major": v as projected
+    def _v_source(self, weights, mmkw, fast):
+        """Where the "single" route's V operand comes from; no side effects."""
+        wants_vt = self.parallel_attention is None and not self.mx_attn and (fast or self.radial)
+        if wants_vt and not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
+            return "vt_epilogue"
+        return "vt_transposed" if wants_vt else "row_major"
+
+    def _project_qk(self, weights, n1, mmkw):
+        return weights.self_attn_q.apply(n1, **mmkw), weights.self_attn_k.apply(n1, **mmkw)
+
+    def _self_attn_ulysses_blocked(self, weights, x, n1, mmkw, freqs, grid, fast, variant, rope_args):
+        """Ulysses without layout copies: the exchange buffers [N, S/N, (H/N)d] are kernel operands (ulysses.py)."""
+        pa = self.parallel_attention
+        b = pa.buffers(x.shape[0], x.shape[1], x.dtype, x.device)
+        weights.self_attn_v.apply(n1, out=b["sv"], **mmkw)  # v needs no norm / RoPE: projected first, straight into its send buffer,
+        v_pending = pa.begin_exchange_blocked(b["sv"], b["rv"])  # and exchanged under the q / k projections and the norm+RoPE kernel
+        q, k = self._project_qk(weights, n1, mmkw)
+        lib.rmsnorm_rope_blocked(q, k, weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, b["sq"], b["sk"], **rope_args)
+        return pa.attend_blocked(b, self.num_heads, self.head_dim, timer=self._timed, variant=variant, v_pending=v_pending)
+
+    def _self_attn_pair(self, weights, x, n1, mmkw, freqs, grid, fast, variant, rope_args):
+        """Both CFG forwards in one pass: projections and row kernels run on the stacked rows, the two self-attentions are one launch."""
+        # (block 0 of the CFG-shared front: one slot, one self-attention — the same batched entry and key walk, so a row's bits do not change)
+        S, Sp = self._pair
+        nb = x.shape[0] // Sp
+        if not mmkw and hasattr(weights.self_attn_v, "apply_vt"):
+            vt = weights.self_attn_v.apply_vt(n1, self.num_heads)
+        else:
+            vt = lib.transpose_heads(weights.self_attn_v.apply(n1, **mmkw), self.num_heads)
+        q, k = self._project_qk(weights, n1, mmkw)
+        for b in range(nb):  # token b*Sp + i of either forward sits at grid position i
+            rows = slice(b * Sp, b * Sp + S)
+            lib.rmsnorm_rope_(q[rows], k[rows], weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
+        # Only the S token rows of a slot are queries, as in a separate forward: the attention kernel decides its lazy O rescale per WAVE
+        # (attn.hip: `__any` over the wave's rows), so a padding row that was a query could switch the rescale on for the token rows sharing
+        # its wave and change their low bits.  The padding rows of the output are zero-filled instead (finite: they become V^T columns).
+        attn = self._slot_rows_zero_padding(q.new_empty(q.shape), nb, S, Sp)
+        return lib.attention_batched(q, k, vt, self.num_heads, nb, Sp, S, out=attn, prescaled=True, all_rows_query=False, stagger=SELF_ATTN_STAGGER, timed=lambda fn: self._timed("self", fn))
+
+    def _self_attn_single(self, weights, x, n1, mmkw, freqs, grid, fast, variant, rope_args):
+        """One sequence per launch: dense, radial or mxfp8 on one GPU, or Ulysses in the reference's row-major form."""
+        # Ulysses: v is projected first and its seq→head exchange runs on the communication stream under the q and k projections and the norm+RoPE kernel
+        pa, src = self.parallel_attention, self._v_source(weights, mmkw, fast)
+        if src == "vt_epilogue":
+            v, vt = None, weights.self_attn_v.apply_vt(n1, self.num_heads)
         else:
             v, vt = weights.self_attn_v.apply(n1, **mmkw), None
         v_pending = pa.begin_exchange(v) if hasattr(pa, "begin_exchange") else None
-        q = weights.self_attn_q.apply(n1, **mmkw)
-        k = weights.self_attn_k.apply(n1, **mmkw)
+        q, k = self._project_qk(weights, n1, mmkw)
         lib.rmsnorm_rope_(q, k, weights.self_attn_norm_q.weight, weights.self_attn_norm_k.weight, freqs, grid, self.num_heads, **rope_args)
-        if pa is None:
-            if self.mx_attn:  # the quantisers run outside the timed launch, as the transposition below does
-                prepared = lib.attention_mx_prepare(q, k, v, self.num_heads, prescaled=fast)
-                attn = self._timed("self", lambda: lib.attention_mx(q, k, v, self.num_heads, prepared=prepared))
-                return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
-            # the ping-pong kernel reads V^T; transposed outside the timed launch so the hook times the attention kernel alone
-            if vt is None and (fast or self.radial):
-                vt = lib.transpose_heads(v, self.num_heads)
-            if self.radial:
-                plan = self._radial_plan(grid, s_local)
-                attn = self._timed("self", lambda: lib.attention_block_sparse(q, k, vt, self.num_heads, plan, prescaled=fast))
-                return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
-            # single GPU: the same key-walk form as the pair pass (SELF_ATTN_STAGGER above), so the launch forms stay bit-identical
-            attn = self._timed("self", lambda: lib.attention(q, k, v, self.num_heads, self.head_dim, variant=variant | (lib.ATTN_STAGGER if (fast and SELF_ATTN_STAGGER) else 0), vt=vt))
-        else:
-            attn = pa(q=q, k=k, v=v if v_pending is None else v_pending, num_heads=self.num_heads, head_dim=self.head_dim, timer=self._timed, variant=variant)
-        return weights.self_attn_o.apply(attn, epilogue=lib.EPI_RESIDUAL, resid=x, gate=gate_msa)
+        if pa is not None:
+            return pa(q=q, k=k, v=v if v_pending is None else v_pending, num_heads=self.num_heads, head_dim=self.head_dim, timer=self._timed, variant=variant)
+        # the quantisers and the transposition run outside the timed launch, so the hook times the attention kernel alone
+        if self.mx_attn:
+            prepared = lib.attention_mx_prepare(q, k, v, self.num_heads, prescaled=fast)
+            return self._timed("self", lambda: lib.attention_mx(q, k, v, self.num_heads, prepared=prepared))
+        if src == "vt_transposed":
+            vt = lib.transpose_heads(v, self.num_heads)
+        if self.radial:
+            plan = self._radial_plan(grid, x.shape[0])
+            return self._timed("self", lambda: lib.attention_block_sparse(q, k, vt, self.num_heads, plan, prescaled=fast))
+        # single GPU: the same key-walk form as the pair pass (SELF_ATTN_STAGGER above), so the launch forms stay bit-identical
+        return self._timed("self", lambda: lib.attention(q, k, v, self.num_heads, self.head_dim, variant=variant | (lib.ATTN_STAGGER if (fast and SELF_ATTN_STAGGER) else 0), vt=vt))
 
     def _radial_plan(self, grid, seq_len):
         """The block-sparse launch plan of this token grid (f, h, w): mask_map = MaskMap(f * h * w, f) on first use or when the grid changes."""
@@ -760,10 +781,9 @@ class WanModel:
         if pat:
             if pat != "ulysses":
                 raise NotImplementedError(f"parallel_attn_type={pat}: only 'ulysses' is built (the north star's SP scheme)")
-            if _cfg(config, "self_attn_1_type") == "hip_radial":
-                raise NotImplementedError("self_attn_1_type='hip_radial' with parallel_attn_type='ulysses': radial attention under Ulysses is not built")
-            if _cfg(config, "self_attn_1_type") == "hip_mxfp8":
-                raise NotImplementedError("self_attn_1_type='hip_mxfp8' with parallel_attn_type='ulysses': block-scaled fp8 attention under Ulysses is not built")
+            unbuilt = {"hip_radial": "radial attention", "hip_mxfp8": "block-scaled fp8 attention"}.get(_cfg(config, "self_attn_1_type"))
+            if unbuilt:
+                raise NotImplementedError(f"self_attn_1_type='{_cfg(config, 'self_attn_1_type')}' with parallel_attn_type='ulysses': {unbuilt} under Ulysses is not built")
             from . import ulysses
 
             ulysses.parallelize_wan(self)
