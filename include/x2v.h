@@ -222,6 +222,39 @@ int x2v_transpose_heads_bf16(const void* v, int64_t ldv, void* vt, int64_t ldvt,
 int x2v_attn_fwd_bf16_vt(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo, int64_t Sq, int64_t Sk,
                          int H, int head_dim, float scale, int flags, void* stream);
 
+/* Carry form of x2v_attn_fwd_bf16_vt: a launch that can start from, and leave behind, the running softmax state of its query rows, so that attention
+ * over all keys is a chain of launches over key chunks with one rounding to bf16 at the end — the kernel layer of ring attention
+ * (attentions/distributed/ring/attn.py:25-63 `_update_out_and_lse`, 99-193: bf16 block outputs merged by four fp32 elementwise passes per step; here
+ * the merge is the epilogue of the attention kernel) and the library's attention-with-LSE.  q / k / V^T / o: operands, layouts and checks as
+ * x2v_attn_fwd_bf16_vt (Sq != Sk allowed, head_dim 128).  State: acc fp32 [Sq, H*128], row stride ldacc elements (ldacc % 4 == 0, acc 16-byte
+ * aligned), head h at column h*128; lse fp32 [H][ldlse], ldlse >= Sq, row r of head h at lse[h*ldlse + r].
+ * flags: X2V_ATTN_VT_PRESCALED, plus
+ *   X2V_ATTN_CARRY_IN   the launch continues from the state in acc / lse (which a CARRY_OUT launch over other keys of the same q left there);
+ *   X2V_ATTN_CARRY_OUT  the launch leaves its state in acc / lse and does not write o (o may be null).
+ * Without CARRY_OUT it writes bf16 o and does not write acc / lse.  With neither bit it is x2v_attn_fwd_bf16_vt with X2V_ATTN_VT_ONE_WALK (same
+ * kernel, same bits; acc / lse are not looked at).  CARRY_OUT alone is attention with LSE: o = bf16(acc), lse = base-2 log-sum-exp.
+ * Always one workgroup per 256-row query block (never the persistent short-walk form), the key walk starts at tile 0, and the XCD-aware work mapping
+ * follows x2v_attn_vt_launch_plan(Sq, Sk, H, 1, X2V_ATTN_VT_ONE_WALK) (it only renumbers workgroups).
+ *
+ * Arithmetic.  The walk over the launch's keys is the dense kernel's, unchanged; scores s are in base 2 (q carries scale*log2(e)).  At its end a
+ * query row has the kernel's running reference m, the fp32 row sum l of 2^(s - m) (the four partial sums of the row's lanes added as
+ * ((p0 + p1) + (p2 + p3)) pairwise across lanes, as in the dense kernel) and the unnormalised fp32 accumulator a[0..127].  Then, all in fp32,
+ * exp2 / log2 the hardware's v_exp_f32 / v_log_f32 (1 ulp), every line one rounding:
+ *   1.  Lb = m + log2(l)
+ *   without CARRY_IN:  2.  L' = Lb      3.  w = 1 / l      4.  A'[d] = a[d] * w          (the dense kernel's own normalisation)
+ *   with CARRY_IN, (A, L) read from acc / lse:
+ *   2.  M  = max(L, Lb)
+ *   3.  L' = M + log2(exp2(L - M) + exp2(Lb - M))
+ *   4.  wA = exp2(L - L'),  wa = exp2(m - L')
+ *   5.  A'[d] = fma(A[d], wA, a[d] * wa)           (a[d] * wa rounded first; the unnormalised accumulator is weighted directly, no division by l)
+ *   6.  CARRY_OUT: acc <- A' (fp32), lse <- L'; else o <- bf16(A') (round to nearest even).
+ * lse is in base-2 units of the scaled scores: the natural-log value of softmax(scale * q k^T) is lse * ln 2.  tests/attn_carry_ref.py restates
+ * steps 1-6 in float64. */
+#define X2V_ATTN_CARRY_IN 8
+#define X2V_ATTN_CARRY_OUT 16
+int x2v_attn_fwd_bf16_vt_carry(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o, int64_t ldo, void* acc,
+                               int64_t ldacc, void* lse, int64_t ldlse, int64_t Sq, int64_t Sk, int H, int head_dim, float scale, int flags, void* stream);
+
 /* Which launch form x2v_attn_fwd_bf16_vt / _batched takes for a shape (host-only, no GPU needed): bit 0 = the XCD-aware head-major work mapping
  * (on while the K / V^T streams of the <= 8 heads in flight fit the Infinity Cache and the launch has >= 512 workgroups — e.g. the Ulysses
  * rank's 5 heads x 75 600 keys; off for 40 heads at 720p), bit 8 = the staggered key walk (X2V_ATTN_VT_STAGGER and Sk >= 16 tiles), bit 9 = the

@@ -339,6 +339,32 @@ struct AttnBsrTable {
 };
 __device__ __forceinline__ AttnBsrTable attn_bsr_table() { return AttnBsrTable{nullptr, 0u}; }
 __device__ __forceinline__ AttnBsrTable attn_bsr_table(AttnBsrTable t) { return t; }
+// Carry form (x2v_attn_fwd_bf16_vt_carry): the same kernel with ONE more argument of another type, the running softmax state of the query rows — the
+// fp32 output so far `acc` [Sq, H*128] and its base-2 log-sum-exp `lse` [H][ldlse] — and the X2V_ATTN_CARRY_* bits that say whether the launch starts
+// from it and whether it leaves it behind.  Selected like the block-sparse form, by the type in the trailing pack; the K loop is the dense one and only
+// the epilogue differs (x2v.h has the arithmetic and its order).  The dense and block-sparse instantiations keep their argument blocks and their
+// instruction streams.
+struct AttnCarryState {
+  float* acc;
+  int64_t ldacc;
+  float* lse;
+  int64_t ldlse;
+  unsigned flags;  // X2V_ATTN_CARRY_IN | X2V_ATTN_CARRY_OUT
+};
+__device__ __forceinline__ AttnCarryState attn_carry_state() { return AttnCarryState{nullptr, 0, nullptr, 0, 0u}; }
+__device__ __forceinline__ AttnCarryState attn_carry_state(AttnCarryState c) { return c; }
+template <typename... T>
+struct AttnPackIs {
+  static constexpr bool bsr = false, carry = false;
+};
+template <>
+struct AttnPackIs<AttnBsrTable> {
+  static constexpr bool bsr = true, carry = false;
+};
+template <>
+struct AttnPackIs<AttnCarryState> {
+  static constexpr bool bsr = false, carry = true;
+};
 
 template <int NW, int RESCALE_THR, bool PRESCALED, bool ROT, typename... BSR_T>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned short* __restrict__ Q, int64_t ldq,
@@ -347,7 +373,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
                                                                    int64_t ldo, int64_t Sq, int64_t Sk, float scale_log2e, unsigned k_bytes,
                                                                    unsigned v_bytes, AttnBatch bs, BSR_T... bsr_arg) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr bool BSR = sizeof...(BSR_T) != 0;
+  static_assert(sizeof...(BSR_T) <= 1, "the trailing pack is empty (dense), an AttnBsrTable or an AttnCarryState");
+  constexpr bool BSR = AttnPackIs<BSR_T...>::bsr, CARRY = AttnPackIs<BSR_T...>::carry;
+  static_assert(sizeof...(BSR_T) == 0 || BSR || CARRY, "unknown trailing argument");
   static_assert(!(BSR && ROT), "the list-driven walk has its own order");
   static_assert(NW == 8, "DMA piece assignment below is written for 4 issuing waves");
   static_assert(RESCALE_THR >= 1 && RESCALE_THR <= 30, "A9_GUARD_T is (1 << RESCALE_THR) as a float");
@@ -801,6 +829,53 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v9_kernel(const unsigned 
 #undef A9_BAR_ODD
   // (A9_SOFTMAX with A9_EXP_TILE and A9_GUARD_T, A9_MATRIX, A9_FRAG, A9_SB, A9_DMA_K, A9_DMA_V stay defined for the persistent form below)
 
+  // Carry epilogue (x2v.h, x2v_attn_fwd_bf16_vt_carry, steps 1-6 in this order; tests/attn_carry_ref.py restates it).  A lane holds 4 x 8 consecutive
+  // fp32 values of its row per group: the state moves as 16-byte loads and stores.  The state's kernel arguments are read here only.
+  if constexpr (CARRY) {
+    const AttnCarryState cs = attn_carry_state(bsr_arg...);
+    const bool cin = (cs.flags & 8u) != 0u, cout = (cs.flags & 16u) != 0u;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      float l_run = lsum[g][0] + lsum[g][1];
+      l_run += __shfl_xor(l_run, 16, 64);
+      l_run += __shfl_xor(l_run, 32, 64);
+      const int64_t qrow = q0 + 16 * g + c16;
+      if (qrow >= Sq) continue;
+      float* const lp = cs.lse + (int64_t)head * cs.ldlse + qrow;
+      float* const ap = cs.acc + qrow * cs.ldacc + (int64_t)head * AT_D + 4 * qd;
+      float L_new = m_run[g] + __builtin_amdgcn_logf(l_run);  // v_log_f32: base 2
+      float w_old = 0.f, w_new = 1.0f / l_run;
+      if (cin) {
+        const float L_old = *lp;
+        const float M = fmaxf(L_old, L_new);
+        const float e_old = __builtin_amdgcn_exp2f(L_old - M), e_new = __builtin_amdgcn_exp2f(L_new - M);
+        L_new = M + __builtin_amdgcn_logf(e_old + e_new);
+        w_old = __builtin_amdgcn_exp2f(L_old - L_new);
+        w_new = __builtin_amdgcn_exp2f(m_run[g] - L_new);
+      }
+#pragma unroll
+      for (int T = 0; T < 8; ++T) {
+        f32x4_t a = oacc[T][g];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] *= w_new;
+        if (cin) {
+          const f32x4_t A = *reinterpret_cast<const f32x4_t*>(ap + 16 * T);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) a[e] = __builtin_fmaf(A[e], w_old, a[e]);
+        }
+        if (cout) {
+          *reinterpret_cast<f32x4_t*>(ap + 16 * T) = a;
+        } else {
+          uint2 pk;
+          pk.x = pack_bf2(a[0], a[1]);
+          pk.y = pack_bf2(a[2], a[3]);
+          *reinterpret_cast<uint2*>(O + qrow * ldo + (int64_t)head * AT_D + 4 * qd + 16 * T) = pk;
+        }
+      }
+      if (cout && qd == 0) *lp = L_new;
+    }
+    return;
+  }
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     float l_run = lsum[g][0] + lsum[g][1];
@@ -1375,6 +1450,38 @@ extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt(const
   hipStream_t st = (hipStream_t)stream;
   return (flags & 1) ? launch_attn_vt<8, 8, true>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags)
                      : launch_attn_vt<8, 8, false>(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, scale, st, flags);
+}
+
+// Carry form: x2v_attn_fwd_bf16_vt's operands plus the running softmax state (x2v.h).  Always one workgroup per 256-row query block, walk from tile 0;
+// the work mapping follows launch_attn_vt's rule for the shape.  With neither carry bit it IS the dense one-walk launch.
+extern "C" __attribute__((visibility("default"))) int x2v_attn_fwd_bf16_vt_carry(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, void* o,
+                                                                                 int64_t ldo, void* acc, int64_t ldacc, void* lse, int64_t ldlse, int64_t Sq, int64_t Sk, int H,
+                                                                                 int head_dim, float scale, int flags, void* stream) {
+  const int carry = flags & (X2V_ATTN_CARRY_IN | X2V_ATTN_CARRY_OUT);
+  const bool writes_o = !(carry & X2V_ATTN_CARRY_OUT);
+  if (Sq == 0 && Sk > 0 && H > 0) return X2V_OK;  // no query rows: nothing to write (empty shard)
+  X2V_REQUIRE(q && k && vt && (o || !writes_o), X2V_E_ARG, "attn_vt_carry: null pointer");
+  if (int rc = check_attn_vt_args("attn_vt_carry", q, ldq, k, ldk, vt, ldvt, writes_o ? o : q, writes_o ? ldo : ldq, Sq, Sk, H, head_dim, flags & ~carry, 1, false)) return rc;
+  if (carry) {
+    X2V_REQUIRE(acc && lse, X2V_E_ARG, "attn_vt_carry: null pointer (acc / lse with a carry bit set)");
+    X2V_REQUIRE(ldacc % 4 == 0 && aligned16(acc) && ((uintptr_t)lse & 3) == 0, X2V_E_ALIGN, "attn_vt_carry: acc rows must be 16-byte aligned, lse 4-byte aligned");
+    X2V_REQUIRE(ldacc >= (int64_t)H * AT_D && ldlse >= Sq, X2V_E_SHAPE, "attn_vt_carry: ldacc=%lld smaller than H*128 or ldlse=%lld smaller than Sq=%lld", (long long)ldacc,
+                (long long)ldlse, (long long)Sq);
+  }
+  if (!carry) return x2v_attn_fwd_bf16_vt(q, ldq, k, ldk, vt, ldvt, o, ldo, Sq, Sk, H, head_dim, scale, (flags & 1) | X2V_ATTN_VT_ONE_WALK, stream);
+  if (scale <= 0.f) scale = 0.08838834764831845f;
+  int64_t kb, vb;
+  if (int rc = attn_vt_spans("attn_vt_carry", Sk, ldk, &kb, &vb)) return rc;
+  AttnBatch bs{0, 0, 0, 0, 0};
+  bs.xcd_remap = attn_vt_plan(Sq, Sk, H, 1, false, 8 * 32, true) & 1;
+  auto kern = (flags & 1) ? attn_fwd_v9_kernel<8, 8, true, false, AttnCarryState> : attn_fwd_v9_kernel<8, 8, false, false, AttnCarryState>;
+  int rc = ensure_dynamic_lds((const void*)kern, 4 * AT_K_BYTES, "attn carry attr");
+  if (rc != X2V_OK) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((Sq + 255) / 256), (unsigned)H), dim3(8 * 64), 4 * AT_K_BYTES, (hipStream_t)stream, (const unsigned short*)q, ldq,
+                     (const unsigned short*)k, ldk, (const unsigned short*)vt, ldvt, (unsigned short*)o, ldo, Sq, Sk, scale * 1.4426950408889634f, (unsigned)kb, (unsigned)vb, bs,
+                     AttnCarryState{(float*)acc, ldacc, (float*)lse, ldlse, (unsigned)carry});
+  X2V_LAUNCH_CHECK("attn carry launch");
+  return X2V_OK;
 }
 
 // Block-sparse self-attention: x2v_attn_fwd_bf16_vt's operands plus a plan table in device memory (lightx2v_amd.lib.attn_block_plan builds and

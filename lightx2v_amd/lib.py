@@ -56,6 +56,8 @@ PROTOTYPES = {
     "x2v_attn_vt_launch_plan": [_i64, _i64, _i32, _i32, _i32],
     "x2v_mfma_probe_bf16": [_i32, ctypes.POINTER(_f32), _c_void_p],
     "x2v_attn_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
+    "x2v_attn_fwd_bf16_vt_carry": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32,
+                                   _c_void_p],
     "x2v_attn_bsr_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_variant": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_mx_sizes": [_i64, _i64, _i32, ctypes.POINTER(_i64)],
@@ -563,6 +565,82 @@ def attention(q, k, v, num_heads, head_dim=128, scale=0.0, out=None, variant=0, 
         "attn_fwd",
     )
     return out2
+
+
+ATTN_CARRY_IN = 8  # x2v.h X2V_ATTN_CARRY_IN: the launch continues from the state in acc / lse
+ATTN_CARRY_OUT = 16  # x2v.h X2V_ATTN_CARRY_OUT: the launch leaves its state in acc / lse and does not write o
+
+
+class AttnCarryState:
+    """The running softmax state of a chain of attention_carry launches over key chunks: `acc` fp32 [Sq, >= H*128] (the output so far; any
+    16-byte-aligned row stride) and `lse` fp32 [H, >= Sq] (its base-2 log-sum-exp), plus how many launches have left their result in it.
+    `AttnCarryState.alloc` makes one for a shape; a chain owns it until its last launch has written the bf16 output."""
+
+    def __init__(self, acc, lse, steps=0):
+        if acc.dtype != torch.float32 or lse.dtype != torch.float32 or acc.dim() != 2 or lse.dim() != 2 or acc.stride(1) != 1 or lse.stride(1) != 1:
+            raise X2VError(f"AttnCarryState: acc / lse are 2-D float32 tensors with unit inner stride, got {acc.dtype} {tuple(acc.shape)} / {lse.dtype} {tuple(lse.shape)}")
+        if not (acc.is_cuda and lse.is_cuda):
+            raise X2VError("AttnCarryState: tensors are not on a HIP device; the x2v HIP path has no CPU fallback")
+        self.acc, self.lse, self.steps = acc, lse, steps
+
+    @classmethod
+    def alloc(cls, rows, num_heads, device):
+        return cls(torch.empty((rows, num_heads * 128), dtype=torch.float32, device=device), torch.empty((num_heads, rows), dtype=torch.float32, device=device))
+
+    def reset(self):
+        self.steps = 0
+        return self
+
+
+def attention_carry(q, k, vt, num_heads, state=None, last=False, prescaled=False, out=None, scale=0.0):
+    """One launch of a chain over key chunks (x2v_attn_fwd_bf16_vt_carry): q [Sq, H*128], this chunk's k [Sk, H*128] (any token stride) and its
+    V^T (transpose_heads over the chunk's Sk rows).  `state`: None or a fresh AttnCarryState (steps == 0) starts a chain, one that earlier launches
+    wrote (steps > 0) continues it.  Not `last`: the launch leaves the state behind (allocated here when None) and returns it; `last`: it writes the
+    chain's bf16 result (one rounding of the fp32 state) into `out` / a new tensor and returns that — the state is then spent (steps back to 0).
+    A chain of one launch (no state, last) is the dense one-walk launch: same bits as attention(..., ATTN_FAST | ATTN_ONE_WALK)."""
+    q2, k2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k, "k"), "k")
+    Sq, Sk = q2.shape[0], k2.shape[0]
+    if min(q2.shape[1], k2.shape[1]) < num_heads * 128:
+        raise X2VError(f"attention_carry: q {tuple(q2.shape)} k {tuple(k2.shape)} do not describe {num_heads} heads of 128")
+    if Sk == 0:
+        raise X2VError("attention_carry: no keys (softmax over an empty set)")
+    _vt_operand(vt, "attention_carry", num_heads, Sk)
+    flags = int(bool(prescaled))
+    if state is not None and state.steps > 0:
+        flags |= ATTN_CARRY_IN
+    if not last:
+        flags |= ATTN_CARRY_OUT
+        if state is None:
+            state = AttnCarryState.alloc(Sq, num_heads, q.device)
+    if state is not None and (state.acc.shape[0] != Sq or state.acc.shape[1] < num_heads * 128 or state.lse.shape[0] != num_heads or state.lse.shape[1] < Sq):
+        raise X2VError(f"attention_carry: the state (acc {tuple(state.acc.shape)}, lse {tuple(state.lse.shape)}) was not made for {Sq} rows x {num_heads} heads")
+    out2 = _attn_out(out, "attention_carry", Sq, num_heads * 128, q.device) if last else None
+    init()
+    if Sq > 0:
+        carry = flags & (ATTN_CARRY_IN | ATTN_CARRY_OUT)
+        acc, lse = (state.acc, state.lse) if carry else (None, None)
+        _check(
+            _lib.x2v_attn_fwd_bf16_vt_carry(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(vt), vt.shape[1] * 64, _p(out2), 0 if out2 is None else out2.stride(0), _p(acc),
+                                            0 if acc is None else acc.stride(0), _p(lse), 0 if lse is None else lse.stride(0), Sq, Sk, num_heads, 128, scale, flags, _stream()),
+            "attn_fwd_vt_carry",
+        )
+    if last:
+        if state is not None:
+            state.steps = 0
+        return out2
+    state.steps += 1
+    return state
+
+
+def attention_lse(q, k, v, num_heads, vt=None, prescaled=False, scale=0.0):
+    """Attention with its log-sum-exp, as flash-attention callers expect it: (out bf16 [Sq, H*128], lse fp32 [H, Sq]) with
+    lse[h, r] = ln sum_j exp(scale * q_r . k_j) in natural-log units.  One CARRY_OUT launch (x2v.h): the kernel works in base 2 on scores
+    that carry scale * log2(e), so its value L2 = log2 sum_j 2^(scale * log2(e) * q_r . k_j) and lse = L2 * ln 2; `out` is the fp32 state rounded
+    to bf16 once (round to nearest even, what the kernel's own bf16 store does).  v may be None when `vt` is given."""
+    if vt is None:
+        vt = transpose_heads(v, num_heads)
+    state = attention_carry(q, k, vt, num_heads, prescaled=prescaled, scale=scale)
+    return state.acc.to(torch.bfloat16), state.lse * math.log(2.0)
 
 
 class AttnBlockPlan:

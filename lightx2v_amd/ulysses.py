@@ -128,40 +128,10 @@ class CommTimer:
         return sum(a.elapsed_time(b) for a, b in self.comm), sum(a.elapsed_time(b) for a, b in self.exposed), len(self.comm)
 
 
-class UlyssesAttention:
-    """Callable injected as `transformer_infer.parallel_attention` (reference hook: transformer_infer.py:381-388)."""
-
-    def __init__(self, group=None, attn_fn=None, overlap=True):
-        self.group = group
-        self._default_attn = attn_fn is None
-        self.attn_fn = attn_fn or (lambda q, k, v, h, d, variant=0: lib.attention(q, k, v, h, d, variant=variant))
-        self.overlap = overlap and torch.cuda.is_available()
-        self.comm_stream = None
-        self._buffers = {}
-        self.copies = 0  # layout copies made by the row-major entry (the blocked entry makes none): asserted by the tests
-        self.split_head2seq = self.split_head2seq_default  # head->seq in two halves (all_to_all_single with split sizes) under the second half's attention
-        self.comm_timer = None  # bench.py: a CommTimer (shared by both CFG branches) while the timed region runs
-
-    split_head2seq_default = True
-
-    class _Pending:
-        """An exchange already issued on the communication stream (result valid once the compute stream has joined it)."""
-
-        def __init__(self, src, out):
-            self.src, self.out = src, out
-
-    # ---- the fused driver's path: exchange buffers are kernel operands ---------------------------------------------------
-    def buffers(self, s_local, hd, dtype, device):
-        """The six [N, S/N, hd/N] exchange buffers of one attention (send q/k/v, receive q/k/v), the attention output (= head->seq
-        send buffer) and its receive buffer.  Allocated once per shape and reused by every layer: stream order makes that safe
-        (a layer's exchanges have been joined by the compute stream before the next layer's kernels write the buffers)."""
-        n, _ = _world(self.group)
-        key = (s_local, hd, dtype, str(device))
-        b = self._buffers.get(key)
-        if b is None:
-            mk = lambda: torch.empty((n, s_local, hd // n), dtype=dtype, device=device)  # noqa: E731
-            b = self._buffers[key] = {name: mk() for name in ("sq", "sk", "sv", "rq", "rk", "rv", "o", "ro")}
-        return b
+class CommStreams:
+    """The stream mechanics of a sequence-parallel attention driver (UlyssesAttention, ring.RingAttention): ONE communication stream per object,
+    stream-ordered issue of collectives on it, joins of a compute stream behind it, and the CommTimer brackets around both.  A subclass sets
+    `overlap`, `comm_stream` (None until first use) and `comm_timer`."""
 
     def _comm(self):
         if self.comm_stream is None:
@@ -200,6 +170,42 @@ class UlyssesAttention:
         src.record_stream(cs)   # produced under the compute stream, read by the collective
         out.record_stream(cur)  # allocated under the communication stream, read by the compute stream
         return out
+
+
+class UlyssesAttention(CommStreams):
+    """Callable injected as `transformer_infer.parallel_attention` (reference hook: transformer_infer.py:381-388)."""
+
+    def __init__(self, group=None, attn_fn=None, overlap=True):
+        self.group = group
+        self._default_attn = attn_fn is None
+        self.attn_fn = attn_fn or (lambda q, k, v, h, d, variant=0: lib.attention(q, k, v, h, d, variant=variant))
+        self.overlap = overlap and torch.cuda.is_available()
+        self.comm_stream = None
+        self._buffers = {}
+        self.copies = 0  # layout copies made by the row-major entry (the blocked entry makes none): asserted by the tests
+        self.split_head2seq = self.split_head2seq_default  # head->seq in two halves (all_to_all_single with split sizes) under the second half's attention
+        self.comm_timer = None  # bench.py: a CommTimer (shared by both CFG branches) while the timed region runs
+
+    split_head2seq_default = True
+
+    class _Pending:
+        """An exchange already issued on the communication stream (result valid once the compute stream has joined it)."""
+
+        def __init__(self, src, out):
+            self.src, self.out = src, out
+
+    # ---- the fused driver's path: exchange buffers are kernel operands ---------------------------------------------------
+    def buffers(self, s_local, hd, dtype, device):
+        """The six [N, S/N, hd/N] exchange buffers of one attention (send q/k/v, receive q/k/v), the attention output (= head->seq
+        send buffer) and its receive buffer.  Allocated once per shape and reused by every layer: stream order makes that safe
+        (a layer's exchanges have been joined by the compute stream before the next layer's kernels write the buffers)."""
+        n, _ = _world(self.group)
+        key = (s_local, hd, dtype, str(device))
+        b = self._buffers.get(key)
+        if b is None:
+            mk = lambda: torch.empty((n, s_local, hd // n), dtype=dtype, device=device)  # noqa: E731
+            b = self._buffers[key] = {name: mk() for name in ("sq", "sk", "sv", "rq", "rk", "rv", "o", "ro")}
+        return b
 
     def begin_exchange_blocked(self, send, recv):
         """seq->head of one blocked send buffer [N, S/N, hd/N] into `recv` (same shape; viewed as row-major [S, hd/N] by the attention),

@@ -779,14 +779,20 @@ class WanModel:
         self._init_infer()
         pat = _cfg(config, "parallel_attn_type")
         if pat:
-            if pat != "ulysses":
-                raise NotImplementedError(f"parallel_attn_type={pat}: only 'ulysses' is built (the north star's SP scheme)")
+            if pat not in ("ulysses", "ring"):
+                raise NotImplementedError(f"parallel_attn_type={pat}: only 'ulysses' (the north star's SP scheme) and 'ring' are built")
             unbuilt = {"hip_radial": "radial attention", "hip_mxfp8": "block-scaled fp8 attention"}.get(_cfg(config, "self_attn_1_type"))
             if unbuilt:
-                raise NotImplementedError(f"self_attn_1_type='{_cfg(config, 'self_attn_1_type')}' with parallel_attn_type='ulysses': {unbuilt} under Ulysses is not built")
-            from . import ulysses
+                scheme = "Ulysses" if pat == "ulysses" else "ring attention"
+                raise NotImplementedError(f"self_attn_1_type='{_cfg(config, 'self_attn_1_type')}' with parallel_attn_type='{pat}': {unbuilt} under {scheme} is not built")
+            if pat == "ring":
+                from . import ring
 
-            ulysses.parallelize_wan(self)
+                ring.parallelize_wan(self)
+            else:
+                from . import ulysses
+
+                ulysses.parallelize_wan(self)
 
     def _init_infer_class(self):
         fc = _cfg(self.config, "feature_caching", "NoCaching")  # reference: wan/model.py:61-75
@@ -896,6 +902,8 @@ class WanModel:
                 # (bench.py at N > 1 times both forms and sets the key explicitly); on one GPU: by size
                 want = il is None and cfg_form_by_size(self.scheduler.seq_len, self.transformer_infer.num_heads) == "streams"
             want = bool(want) and self.scheduler.latents.is_cuda
+            if il is None and self.transformer_infer.parallel_attention is not None:
+                want = False  # ring attention installs no interleave: `il is None` means "one GPU" only without a parallel attention
             if want and il is None:
                 il = self._cfg_interleave = CfgBranchStreams(self)
             if want and il.usable(inputs):

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--tiny-vae-ckpt", default=None, help="--tiny-vae: the released taew2_1.pth (default: seeded synthetic weights)")
     ap.add_argument("--teacache", type=float, default=0.0, help="TeaCache threshold (0 = off); uses the released 14B 720p coefficients")
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--ring", action="store_true", help='with --gpus N: parallel_attn_type="ring" (ring attention: no num_heads %% N constraint) instead of "ulysses"')
     ap.add_argument("--radial", type=int, default=0, metavar="ROUNDS", help='time ROUNDS denoise steps with "self_attn_1_type": "hip_radial" next to ROUNDS dense steps (A-B-A-B, same model, same process) and print that instead of a full run; single GPU')
     ap.add_argument("--mx-attn", type=int, nargs="?", const=5, default=0, metavar="ROUNDS", help='time ROUNDS (default 5) denoise steps with "self_attn_1_type": "hip_mxfp8" (block-scaled fp8 self-attention) next to ROUNDS dense steps (A-B-A-B, same model, same process) and print that instead of a full run; single GPU')
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
@@ -80,9 +81,11 @@ def main():
         extra.update(feature_caching="Tea", teacache_thresh=a.teacache, use_ret_steps=False,
                      coefficients=[[8.10705460e03, 2.13393892e03, -3.72934672e02, 1.66203073e01, -4.17769401e-02],
                                    [-114.36346466, 65.26524496, -18.82220707, 4.91518089, -0.23412683]])
-    if world > 1:
+    if world > 1 and a.ring:
+        extra["parallel_attn_type"] = "ring"
+    elif world > 1:
         if dims["num_heads"] % world:
-            raise SystemExit(f"Ulysses needs num_heads % N == 0 ({dims['num_heads']} heads, N={world})")
+            raise SystemExit(f"Ulysses needs num_heads % N == 0 ({dims['num_heads']} heads, N={world}); --ring has no such constraint")
         extra["parallel_attn_type"] = "ulysses"
     _, overrides, wd, lat, inputs = synth.workload_setup(a.workload, seed=0, device="cuda")  # i2v: the i2v checkpoint + seeded CLIP / VAE-encode stand-ins
     extra = {**overrides, **extra}
@@ -229,7 +232,7 @@ def main():
     t2 = time.perf_counter()
     assert torch.isfinite(video).all() and torch.isfinite(sch.latents).all()
     frames = wl["frames"]
-    rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"ulysses-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp6xmxfp8" if a.mxfp6 else "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
+    rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"{'ring' if a.ring else 'ulysses'}-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp6xmxfp8" if a.mxfp6 else "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
            "teacache_thresh": a.teacache, "vae_conv_operands": "bf16 (tiny VAE / TAEHV)" if a.tiny_vae else "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "tiny_vae": bool(a.tiny_vae), "vae_tiling": bool(a.tiling_vae and world == 1), "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
            "frames": frames, "video_shape": list(video.shape), "fps_denoise_only": frames / (t1 - t0), "fps_with_vae": frames / (t2 - t0),
            "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}
