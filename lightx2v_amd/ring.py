@@ -15,19 +15,19 @@ log-sum-exp.  What the reference pays beyond that is removed:
     communication stream under step s's attention, into the other of two buffer pairs allocated once per shape; the order is by stream
     joins in both directions — a receive buffer is overwritten only after the launch that read it has been ordered before the receive, and a
     launch reads a buffer only after joining the receive.
-The stream / timer mechanics are ulysses.CommStreams, shared with UlyssesAttention.
+The stream discipline (one communication stream, `_enqueue` behind the compute stream, `_join` before a read, the CommTimer brackets) is
+ulysses.CommStreams, shared with the Ulysses drivers and described there; the wrapper round the Wan block stack is ulysses.shard_wan_block_stack.
 """
 import torch
 import torch.distributed as dist
 
 from . import lib
-from .ulysses import CommStreams, post_process, pre_process
+from .ulysses import CommStreams, shard_wan_block_stack
 
 
-def _world(group=None):
-    if not (dist.is_available() and dist.is_initialized()):
-        return 1, 0  # no process group: a ring of one (the single launch)
-    return dist.get_world_size(group), dist.get_rank(group)
+def _no_group():
+    """No process group: a ring of one (the single launch), with nothing to shard or gather."""
+    return not (dist.is_available() and dist.is_initialized())
 
 
 def transpose_heads_host(v, num_heads):
@@ -48,16 +48,15 @@ class RingAttention(CommStreams):
     last call), `calls`, and `host_syncs` (host synchronisations the driver itself made inside a call: none)."""
 
     def __init__(self, group=None, attn_fn=None, overlap=True):
-        self.group = group
+        super().__init__(group, overlap)
         self._default_attn = attn_fn is None
         self.attn_fn = attn_fn or lib.attention_carry
-        self.overlap = overlap and torch.cuda.is_available()
-        self.comm_stream = None
-        self.comm_timer = None
-        self._buffers = {}
         self._states = {}
         self.launches, self.calls, self.host_syncs = [], 0, 0
         self.bytes_sent = 0  # by this rank in the last call
+
+    def world(self):
+        return (1, 0) if _no_group() else super().world()
 
     def buffers(self, k, vt):
         """Two (K chunk, V^T chunk) receive pairs, allocated once per shape and reused by every layer (stream order makes that safe: a call's
@@ -96,7 +95,7 @@ class RingAttention(CommStreams):
         self.bytes_sent += sum(s.numel() * s.element_size() for s in send)
 
     def __call__(self, q, k, v, num_heads, head_dim=128, timer=None, variant=0):
-        n, r = _world(self.group)
+        n, r = self.world()
         if head_dim != 128:
             raise lib.X2VError(f"ring attention: head_dim={head_dim} (only 128 is built)")
         prescaled = bool(variant & lib.ATTN_Q_PRESCALED)
@@ -120,43 +119,24 @@ class RingAttention(CommStreams):
         to, frm = self._peers(n, r)
         kc = k if k.is_contiguous() else k.contiguous()  # a view of a fused projection: the message is the chunk alone
         pairs = self.buffers(kc, vt)
-        use_streams = self.overlap and q.is_cuda
-        if use_streams:
-            cur, cs = torch.cuda.current_stream(), self._comm()
-            cs.wait_stream(cur)  # the local chunk is complete — and so is every earlier launch that read the receive buffers
-            self._issue(cs, lambda: self._transfer((kc, vt), pairs[0], to, frm))
-            kc.record_stream(cs)
-            vt.record_stream(cs)
+        # Each hop is enqueued one step ahead of the launch that reads it.  Enqueueing orders it behind what the compute stream holds: the local
+        # chunk is complete, and so is every earlier launch that read the receive buffers.  Without streams (host tensors under gloo, or
+        # overlap off) these are the same hops in the same order, each completed where it is enqueued.
+        self._enqueue(lambda: self._transfer((kc, vt), pairs[0], to, frm), q)
+        if self._streams(q):
+            kc.record_stream(self.comm_stream)
+            vt.record_stream(self.comm_stream)
         out = launch(k, vt, 0)
         for s in range(1, n):
             have, nxt = pairs[(s - 1) % 2], pairs[s % 2]
-            if use_streams:
-                self._join(cur, cs)  # the chunk of step s has arrived
-                if s + 1 < n:
-                    cs.wait_stream(cur)  # launch s-1, the last reader of `nxt`, is ordered before the receive that overwrites it
-                    self._issue(cs, lambda have=have, nxt=nxt: self._transfer(have, nxt, to, frm))
-            else:
-                # no streams (host tensors under gloo, or overlap off): the same hops, each completed before its chunk is read
-                self._transfer((kc, vt) if s == 1 else pairs[s % 2], have, to, frm)
+            self._join(q)  # the chunk of step s has arrived
+            if s + 1 < n:  # launch s-1, the last reader of `nxt`, is ordered before the receive that overwrites it
+                self._enqueue(lambda: self._transfer(have, nxt, to, frm), q)
             out = launch(have[0], have[1], s)
         return out
 
 
 def parallelize_wan(wan_model, group=None, attn_fn=None):
-    """reference: ring/wrap.py:53-71 — swap the attention, shard x around the block stack (the same pre/post_process as Ulysses; the RoPE
-    row offset follows tr.sp_rank).  With CFG the two forwards run one after the other: no CFG-branch interleave is installed for the ring."""
-    tr = wan_model.transformer_infer
-    n, r = _world(group)
-    tr.parallel_attention = RingAttention(group, attn_fn)
-    tr.sp_rank, tr.sp_world = r, n
-    original_infer = tr.infer
-
-    def new_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks=None):
-        if not (dist.is_available() and dist.is_initialized()):  # no process group: nothing to shard or gather
-            return original_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
-        x = pre_process(x, group)
-        x = original_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
-        return tr.parallel_attention.on_comm(lambda: post_process(x, group), x)
-
-    tr.infer = new_infer
-    return wan_model
+    """reference: ring/wrap.py:53-71 — swap the attention, shard x around the block stack (the same wrapper as Ulysses).  With CFG the two
+    forwards run one after the other: no CFG-branch interleave is installed for the ring."""
+    return shard_wan_block_stack(wan_model, RingAttention(group, attn_fn), passthrough=_no_group)

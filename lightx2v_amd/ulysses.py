@@ -20,6 +20,9 @@ node: xGMI is a full mesh of point-to-point links, so an all-to-all puts one mes
     issued in two halves (destination ranks [0, N/2) and [N/2, N)), the first under the attention of the second half's query rows.
 `seq2head` / `head2seq` / calling the object with row-major 2-D q, k, v keep the reference's functional forms (bit-equal to its
 all2all_* functions in the gloo tests) for callers that hold row-major tensors (the reference's op-by-op loop).
+
+The stream discipline of every sequence-parallel driver (UlyssesAttention, UlyssesHunyuanAttention, ring.RingAttention) is written ONCE, in
+`CommStreams` below: its `_enqueue` and `_join` are the only places that order the communication stream and a compute stream behind one another.
 """
 import torch
 import torch.distributed as dist
@@ -129,64 +132,100 @@ class CommTimer:
 
 
 class CommStreams:
-    """The stream mechanics of a sequence-parallel attention driver (UlyssesAttention, ring.RingAttention): ONE communication stream per object,
-    stream-ordered issue of collectives on it, joins of a compute stream behind it, and the CommTimer brackets around both.  A subclass sets
-    `overlap`, `comm_stream` (None until first use) and `comm_timer`."""
+    """The stream discipline of a sequence-parallel attention driver (UlyssesAttention, UlyssesHunyuanAttention, ring.RingAttention), in one place:
+    ONE communication stream per object; EVERY collective is enqueued on it, ordered behind what the compute stream has enqueued (`_enqueue`); the
+    compute stream waits for it before it reads a result (`_join`); a CommTimer, when attached, brackets both.  When the driver does not overlap
+    (`overlap=False`, host tensors under gloo) `_enqueue` calls the collectives directly and `_join` does nothing, so a call site is written once.
+    Both look the compute stream up per call: inside one driver call the current stream does not change, also under wan.CfgBranchStreams, which
+    enters `torch.cuda.stream(st)` around a whole block."""
+
+    def __init__(self, group=None, overlap=True):
+        self.group = group
+        self.overlap = overlap and torch.cuda.is_available()
+        self.comm_stream = None  # created at first use (`_comm`); CfgBranchStreams hands branch A's to branch B
+        self.comm_timer = None  # bench.py: a CommTimer (shared by both CFG branches) while the timed region runs
+        self._buffers = {}
+
+    def world(self):
+        return _world(self.group)
 
     def _comm(self):
         if self.comm_stream is None:
             self.comm_stream = torch.cuda.Stream()
         return self.comm_stream
 
-    def _issue(self, cs, fn):
-        """fn() = one or more collectives, enqueued on the communication stream `cs` (already ordered behind the compute stream by the caller)."""
-        t = self.comm_timer
+    def _streams(self, t):
+        """Does an exchange of the tensor `t` go through the communication stream?"""
+        return self.overlap and t.is_cuda
+
+    def _enqueue(self, fn, t):
+        """fn() = one or more collectives on tensors that live where `t` does: run on the communication stream, behind everything the current
+        stream has enqueued so far.  Returns fn()'s result, valid for the current stream after `_join`."""
+        if not self._streams(t):
+            return fn()
+        cs, tm = self._comm(), self.comm_timer
+        cs.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(cs):
-            done = t.bracket("comm", cs) if (t is not None and t.enabled) else None
+            done = tm.bracket("comm", cs) if (tm is not None and tm.enabled) else None
             out = fn()
             if done is not None:
                 done()
         return out
 
-    def _join(self, cur, cs):
-        """The compute stream `cur` waits for everything enqueued on the communication stream so far."""
-        t = self.comm_timer
-        done = t.bracket("exposed", cur) if (t is not None and t.enabled) else None
-        cur.wait_stream(cs)
+    def _join(self, t):
+        """The current stream waits for everything enqueued on the communication stream so far."""
+        if not self._streams(t):
+            return
+        cur, tm = torch.cuda.current_stream(), self.comm_timer
+        done = tm.bracket("exposed", cur) if (tm is not None and tm.enabled) else None
+        cur.wait_stream(self._comm())
         if done is not None:
             done()
 
     def on_comm(self, fn, src):
-        """Run the collective `fn()` (which reads `src` and returns a fresh tensor) on the communication stream, ordered behind what the current
-        stream has enqueued, and join the current stream behind it.  EVERY collective of this driver goes through the one communication stream
-        With synchronous collectives running on the calling stream, a gather issued from a compute stream would put kernels of the
-        same RCCL communicator on several streams at once and leave their order to RCCL's internals."""
-        if not (self.overlap and src.is_cuda):
-            return fn()
-        cur, cs = torch.cuda.current_stream(), self._comm()
-        cs.wait_stream(cur)
-        out = self._issue(cs, fn)
-        self._join(cur, cs)
-        src.record_stream(cs)   # produced under the compute stream, read by the collective
-        out.record_stream(cur)  # allocated under the communication stream, read by the compute stream
+        """Run the collective `fn()` (which reads `src` and returns a fresh tensor) on the communication stream and join the current stream behind
+        it.  With synchronous collectives running on the calling stream, a gather issued from a compute stream would put kernels of the same RCCL
+        communicator on several streams at once and leave their order to RCCL's internals."""
+        out = self._enqueue(fn, src)
+        self._join(src)
+        if self._streams(src):
+            src.record_stream(self.comm_stream)  # produced under the compute stream, read by the collective
+            out.record_stream(torch.cuda.current_stream())  # allocated under the communication stream, read by the compute stream
         return out
 
 
-class UlyssesAttention(CommStreams):
+class _UlyssesDriver(CommStreams):
+    """What the Wan and the Hunyuan driver share beyond the streams: the head count per rank and the form of the head->seq exchange."""
+
+    split_head2seq_default = True
+
+    def __init__(self, group=None, overlap=True):
+        super().__init__(group, overlap)
+        self.copies = 0  # layout copies made by the row-major entry (the blocked entry makes none): asserted by the tests
+        self.split_head2seq = self.split_head2seq_default  # head->seq in two halves (all_to_all_single with split sizes) under the second half's attention
+
+    def _heads(self, num_heads):
+        """(N, rank, heads per rank)"""
+        n, r = self.world()
+        if num_heads % n != 0:
+            raise lib.X2VError(f"Ulysses needs num_heads % world_size == 0 (H={num_heads}, N={n})")
+        return n, r, num_heads // n
+
+    def _head2seq_plan(self, rows_per_rank, device):
+        """The `_split_plan` of an attention output with `rows_per_rank` rows per destination.  A `split_head2seq` of True is probed once
+        (`split_form_ok`) and, where the build rejects the split-size form, downgraded to False for good."""
+        if self.split_head2seq is True and not split_form_ok(self.group, device):
+            self.split_head2seq = False
+        return _split_plan(*self.world(), rows_per_rank, self.split_head2seq)
+
+
+class UlyssesAttention(_UlyssesDriver):
     """Callable injected as `transformer_infer.parallel_attention` (reference hook: transformer_infer.py:381-388)."""
 
     def __init__(self, group=None, attn_fn=None, overlap=True):
-        self.group = group
+        super().__init__(group, overlap)
         self._default_attn = attn_fn is None
         self.attn_fn = attn_fn or (lambda q, k, v, h, d, variant=0: lib.attention(q, k, v, h, d, variant=variant))
-        self.overlap = overlap and torch.cuda.is_available()
-        self.comm_stream = None
-        self._buffers = {}
-        self.copies = 0  # layout copies made by the row-major entry (the blocked entry makes none): asserted by the tests
-        self.split_head2seq = self.split_head2seq_default  # head->seq in two halves (all_to_all_single with split sizes) under the second half's attention
-        self.comm_timer = None  # bench.py: a CommTimer (shared by both CFG branches) while the timed region runs
-
-    split_head2seq_default = True
 
     class _Pending:
         """An exchange already issued on the communication stream (result valid once the compute stream has joined it)."""
@@ -199,7 +238,7 @@ class UlyssesAttention(CommStreams):
         """The six [N, S/N, hd/N] exchange buffers of one attention (send q/k/v, receive q/k/v), the attention output (= head->seq
         send buffer) and its receive buffer.  Allocated once per shape and reused by every layer: stream order makes that safe
         (a layer's exchanges have been joined by the compute stream before the next layer's kernels write the buffers)."""
-        n, _ = _world(self.group)
+        n, _ = self.world()
         key = (s_local, hd, dtype, str(device))
         b = self._buffers.get(key)
         if b is None:
@@ -209,52 +248,32 @@ class UlyssesAttention(CommStreams):
 
     def begin_exchange_blocked(self, send, recv):
         """seq->head of one blocked send buffer [N, S/N, hd/N] into `recv` (same shape; viewed as row-major [S, hd/N] by the attention),
-        on the communication stream when overlapping, stream-ordered after what the compute stream has enqueued so far."""
-        if self.overlap and send.is_cuda:
-            cs = self._comm()
-            cs.wait_stream(torch.cuda.current_stream())
-            self._issue(cs, lambda: dist.all_to_all_single(recv, send, group=self.group))
-        else:
-            dist.all_to_all_single(recv, send, group=self.group)
+        stream-ordered after what the compute stream has enqueued so far."""
+        self._enqueue(lambda: dist.all_to_all_single(recv, send, group=self.group), send)
         return self._Pending(send, recv)
 
     def attend_blocked(self, bufs, num_heads, head_dim=128, timer=None, variant=0, v_pending=None):
         """q/k/v are in bufs["sq"/"sk"/"sv"] (v possibly already in flight: `v_pending`).  Returns bufs["ro"]: the received head->seq
         buffer [N, S/N, hd/N] = the output projection's K-blocked input."""
-        n, r = _world(self.group)
-        if num_heads % n != 0:
-            raise lib.X2VError(f"Ulysses needs num_heads % world_size == 0 (H={num_heads}, N={n})")
-        hl = num_heads // n
+        n, _, hl = self._heads(num_heads)
         s_local, hdn = bufs["sq"].shape[1], bufs["sq"].shape[2]
         S = n * s_local
-        use_streams = self.overlap and bufs["sq"].is_cuda
-        if use_streams:
-            cur, cs = torch.cuda.current_stream(), self._comm()
-            cs.wait_stream(cur)
 
-            def qkv():
-                dist.all_to_all_single(bufs["rq"], bufs["sq"], group=self.group)
-                dist.all_to_all_single(bufs["rk"], bufs["sk"], group=self.group)
-                if v_pending is None:
-                    dist.all_to_all_single(bufs["rv"], bufs["sv"], group=self.group)
-
-            self._issue(cs, qkv)
-            self._join(cur, cs)
-        else:
+        def qkv():
             dist.all_to_all_single(bufs["rq"], bufs["sq"], group=self.group)
             dist.all_to_all_single(bufs["rk"], bufs["sk"], group=self.group)
             if v_pending is None:
                 dist.all_to_all_single(bufs["rv"], bufs["sv"], group=self.group)
+
+        self._enqueue(qkv, bufs["sq"])
+        self._join(bufs["sq"])
         qh, kh, vh = (bufs[x].view(S, hdn) for x in ("rq", "rk", "rv"))
         o = bufs["o"].view(S, hdn)
         fast = self._default_attn and (variant & 0xFF) == lib.ATTN_FAST
         vt = lib.transpose_heads(vh, hl) if fast else None  # the ping-pong kernel reads V^T (1/N of the single-GPU transposition)
-        # head->seq in two pieces by destination rank: rows of ranks [0, N/2) first, exchanged under the attention of the second piece
-        split = self.split_head2seq
-        if split is True and not split_form_ok(self.group, o.device):
-            split = self.split_head2seq = False
         ro = bufs["ro"].view(S, hdn)
-        for _, rows, in_split, out_split, rrows in _split_plan(n, r, s_local, split):
+        # head->seq in two pieces by destination rank: rows of ranks [0, N/2) first, exchanged under the attention of the second piece
+        for _, rows, in_split, out_split, rrows in self._head2seq_plan(s_local, o.device):
 
             def fn(rows=rows):
                 if fast:
@@ -265,60 +284,44 @@ class UlyssesAttention(CommStreams):
                 return o[rows]
 
             timer("self", fn) if timer is not None else fn()
-            if use_streams:
-                cs.wait_stream(cur)
-                self._issue(cs, lambda rows=rows, rrows=rrows, out_split=out_split, in_split=in_split: dist.all_to_all_single(ro[rrows], o[rows], out_split, in_split, group=self.group))
-            else:
-                dist.all_to_all_single(ro[rrows], o[rows], out_split, in_split, group=self.group)
-        if use_streams:
-            self._join(cur, cs)
+            self._enqueue(lambda: dist.all_to_all_single(ro[rrows], o[rows], out_split, in_split, group=self.group), o)
+        self._join(o)
         return bufs["ro"]
 
     # ---- row-major entry (the reference's functional form) -----------------------------------------------------------------
     def begin_exchange(self, x):
         """Start seq→head of a row-major `x` [S/N, H*d] on the communication stream now (stream-ordered after what has been enqueued
         on the compute stream so far); the caller keeps enqueueing independent work and hands the result to __call__."""
-        if not (self.overlap and x.is_cuda):
+        if not self._streams(x):
             return None
-        cs = self._comm()
-        cs.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cs):
-            out = seq2head(x, self.group)
-        x.record_stream(cs)
-        out.record_stream(cs)
+        out = self._enqueue(lambda: seq2head(x, self.group), x)
+        x.record_stream(self.comm_stream)
+        out.record_stream(self.comm_stream)
         return self._Pending(x, out)
 
     def __call__(self, q, k, v, num_heads, head_dim=128, timer=None, variant=0):
-        n, _ = _world(self.group)
-        if num_heads % n != 0:
-            raise lib.X2VError(f"Ulysses needs num_heads % world_size == 0 (H={num_heads}, N={n})")
+        _, _, hl = self._heads(num_heads)
         self.copies += 4  # three transposing sends + the gather of the received output
-        if self.overlap and q.is_cuda:
-            cs = self._comm()
-            cur = torch.cuda.current_stream()
-            cs.wait_stream(cur)
-            with torch.cuda.stream(cs):
-                qh, kh = seq2head(q, self.group), seq2head(k, self.group)
-                vh = v.out if isinstance(v, self._Pending) else seq2head(v, self.group)
-            for t in (q, k) + (() if isinstance(v, self._Pending) else (v,)):
-                t.record_stream(cs)  # produced on the compute stream, read by the exchange
-            cur.wait_stream(cs)
+        pending = isinstance(v, self._Pending) and self._streams(q)  # v's exchange is already on the communication stream (begin_exchange)
+        if isinstance(v, self._Pending) and not pending:
+            v = v.src
+        qh, kh, vh = self._enqueue(lambda: (seq2head(q, self.group), seq2head(k, self.group), v.out if pending else seq2head(v, self.group)), q)
+        self._join(q)
+        if self._streams(q):
+            for t in (q, k) + (() if pending else (v,)):
+                t.record_stream(self.comm_stream)  # produced on the compute stream, read by the exchange
             for t in (qh, kh, vh):
-                t.record_stream(cur)  # allocated under the communication stream, read by the attention kernel
-        else:
-            if isinstance(v, self._Pending):
-                v = v.src
-            qh, kh, vh = seq2head(q, self.group), seq2head(k, self.group), seq2head(v, self.group)
+                t.record_stream(torch.cuda.current_stream())  # allocated under the communication stream, read by the attention kernel
         if self._default_attn and (variant & 0xFF) == lib.ATTN_FAST:
             # the ping-pong kernel reads V^T: transposed before the timed launch, as on the single-GPU path (wan.py)
-            vt = lib.transpose_heads(vh, num_heads // n)
-            fn = lambda: lib.attention(qh, kh, vh, num_heads // n, head_dim, variant=variant, vt=vt)
+            vt = lib.transpose_heads(vh, hl)
+            fn = lambda: lib.attention(qh, kh, vh, hl, head_dim, variant=variant, vt=vt)
         elif variant:
-            fn = lambda: self.attn_fn(qh, kh, vh, num_heads // n, head_dim, variant=variant)
+            fn = lambda: self.attn_fn(qh, kh, vh, hl, head_dim, variant=variant)
         else:
-            fn = lambda: self.attn_fn(qh, kh, vh, num_heads // n, head_dim)
+            fn = lambda: self.attn_fn(qh, kh, vh, hl, head_dim)
         o = timer("self", fn) if timer is not None else fn()
-        return head2seq(o, self.group)
+        return head2seq(o, self.group)  # on the calling stream, as it always was: a candidate for a later change of behaviour, not this one's
 
 
 def pre_process(x, group=None):
@@ -338,23 +341,32 @@ def post_process(x, group=None):
     return out
 
 
-def parallelize_wan(wan_model, group=None, attn_fn=None):
-    """reference: ulysses/wrap.py:53-71 — swap the attention, shard x around the block stack.  Beyond the reference: with CFG the two
-    forwards of a step CAN be driven block by block on two compute streams (config `cfg_branch_streams=True`) so that one branch's
-    kernels run while the other waits for an exchange.  That form has only ever run on one GPU (gloo plumbing) — it is off by default ("auto" =
-    one forward after the other under Ulysses) until a multi-GPU run has shown it safe and faster; bench.py times both forms at N > 1."""
+def shard_wan_block_stack(wan_model, pa, passthrough=lambda: False):
+    """reference: ulysses/wrap.py:53-71 and ring/wrap.py:53-71 — install the attention object `pa` (a CommStreams) and shard x around the
+    block stack: this rank's rows in (the RoPE row offset follows tr.sp_rank), all rows out through `on_comm`.  While `passthrough()` holds
+    the block stack runs unsharded."""
     tr = wan_model.transformer_infer
-    n, r = _world(group)
-    tr.parallel_attention = UlyssesAttention(group, attn_fn)
-    tr.sp_rank, tr.sp_world = r, n
+    tr.sp_world, tr.sp_rank = pa.world()
+    tr.parallel_attention = pa
     original_infer = tr.infer
 
     def new_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks=None):
-        x = pre_process(x, group)
+        if passthrough():
+            return original_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
+        x = pre_process(x, pa.group)
         x = original_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
-        return tr.parallel_attention.on_comm(lambda: post_process(x, group), x)
+        return tr.parallel_attention.on_comm(lambda: post_process(x, pa.group), x)
 
     tr.infer = new_infer
+    return wan_model
+
+
+def parallelize_wan(wan_model, group=None, attn_fn=None):
+    """Ulysses around the Wan block stack.  Beyond the reference: with CFG the two forwards of a step CAN be driven block by block on two
+    compute streams (config `cfg_branch_streams=True`) so that one branch's kernels run while the other waits for an exchange.
+    That form has only ever run on one GPU (gloo plumbing) — it is off by default ("auto" = one forward after the other under Ulysses) until
+    a multi-GPU run has shown it safe and faster; bench.py times both forms at N > 1."""
+    shard_wan_block_stack(wan_model, UlyssesAttention(group, attn_fn))
     wan_model._cfg_interleave = CfgBranchStreams(wan_model, group, attn_fn)
     return wan_model
 
@@ -435,7 +447,7 @@ def hunyuan_post_process(output, split_dim, group=None):
     return torch.cat(list(out.chunk(n, dim=0)), dim=split_dim)
 
 
-class UlyssesHunyuanAttention:
+class UlyssesHunyuanAttention(_UlyssesDriver):
     """reference: attentions/distributed/ulysses/attn.py:7-91 for the joint img+txt attention: image q/k/v go seq→head by
     all-to-all, the (replicated) text q/k/v contribute this rank's heads, one attention over [all image tokens ; text]
     with H/N heads, image output head→seq by all-to-all, text output all-gathered over heads.  No host synchronisation
@@ -443,14 +455,8 @@ class UlyssesHunyuanAttention:
     the joint attention operands, so there is no torch.cat."""
 
     def __init__(self, group=None, attn_fn=None, overlap=True):
-        self.group = group
+        super().__init__(group, overlap)  # `copies` counts image-row layout copies here; `comm_timer`: tools/hunyuan_bench.py at N > 1
         self.attn_fn = attn_fn
-        self.overlap = overlap and torch.cuda.is_available()
-        self.comm_stream = None
-        self._buffers = {}
-        self.copies = 0  # image-row layout copies made by the row-major entry (the blocked entry makes none): asserted by the tests
-        self.comm_timer = None  # tools/hunyuan_bench.py at N > 1: a CommTimer while the timed region runs (None: no events are recorded)
-        self.split_head2seq = True
 
     # ---- the fused driver's path: exchange buffers are kernel operands ---------------------------------------------------
     def buffers(self, n_img, n_txt, hd, mlp, dtype, device):
@@ -464,7 +470,7 @@ class UlyssesHunyuanAttention:
                                          receive head->seq (image) / the all-gather over heads (text); the further blocks hold the MLP branch
                                          of a single block (written N-blocked by linear1's GELU GEMM), so that linear2 reads
                                          cat(attn, mlp) (transformer_infer.py:377) without anybody assembling it."""
-        n, _ = _world(self.group)
+        n, _ = self.world()
         key = (n_img, n_txt, hd, mlp, dtype, str(device))
         b = self._buffers.get(key)
         if b is None:
@@ -474,79 +480,28 @@ class UlyssesHunyuanAttention:
                                           a_img=e(n + mlp // hdn, n_img, hdn), a_txt=e(n + mlp // hdn, n_txt, hdn))
         return b
 
-    def on_comm(self, fn, src):
-        """As UlyssesAttention.on_comm: every collective of the driver on the one communication stream."""
-        if not (self.overlap and src.is_cuda):
-            return fn()
-        if self.comm_stream is None:
-            self.comm_stream = torch.cuda.Stream()
-        cur, cs = torch.cuda.current_stream(), self.comm_stream
-        cs.wait_stream(cur)
-        t = self.comm_timer if (self.comm_timer is not None and self.comm_timer.enabled) else None  # CommTimer accounting as in UlyssesAttention
-        with torch.cuda.stream(cs):
-            done = t.bracket("comm", cs) if t is not None else None
-            out = fn()
-            if done is not None:
-                done()
-        done = t.bracket("exposed", cur) if t is not None else None
-        cur.wait_stream(cs)
-        if done is not None:
-            done()
-        src.record_stream(cs)
-        out.record_stream(cur)
-        return out
-
     def blocked_ok(self, hd, mlp):
         """K-blocked GEMM operands advance in whole 64-element K tiles."""
-        n, _ = _world(self.group)
+        n, _ = self.world()
         return hd % n == 0 and (hd // n) % 128 == 0 and mlp % (hd // n) == 0
 
     def attend_blocked(self, bufs, txt_qkv, segs_txt, num_heads, variant=0):
         """Image q/k/v are in bufs["snd"] (head-blocked), text q/k/v in the row-major views `txt_qkv` [n_txt, H*128] each.
         Returns (a_img, a_txt) whose first N blocks hold the attention output of this rank's image rows / of the text rows, all heads."""
-        n, r = _world(self.group)
-        if num_heads % n != 0:
-            raise lib.X2VError(f"Ulysses needs num_heads % world_size == 0 (H={num_heads}, N={n})")
+        n, r, hl = self._heads(num_heads)
         snd, joint, o, a_img, a_txt = (bufs[x] for x in ("snd", "joint", "o", "a_img", "a_txt"))
         n_img, hdn = snd.shape[2], snd.shape[3]
         n_txt, tot = a_txt.shape[1], n * snd.shape[2]
         n_valid = segs_txt[0]
-        hl = num_heads // n
-        use_streams = self.overlap and snd.is_cuda
-        cur = cs = None
-        if use_streams:
-            if self.comm_stream is None:
-                self.comm_stream = torch.cuda.Stream()
-            cur, cs = torch.cuda.current_stream(), self.comm_stream
-
-        tm = self.comm_timer if (use_streams and self.comm_timer is not None and self.comm_timer.enabled) else None
-
-        def on_comm(fn):
-            if use_streams:
-                cs.wait_stream(cur)
-                with torch.cuda.stream(cs):
-                    done = tm.bracket("comm", cs) if tm is not None else None
-                    fn()
-                    if done is not None:
-                        done()
-            else:
-                fn()
-
-        def join():  # the compute stream waits for everything enqueued on the communication stream so far
-            done = tm.bracket("exposed", cur) if tm is not None else None
-            cur.wait_stream(cs)
-            if done is not None:
-                done()
 
         def seq2head():
             for i in range(3):
                 dist.all_to_all_single(joint[i][:tot].view(n, n_img, hdn), snd[i], group=self.group)
 
-        on_comm(seq2head)
+        self._enqueue(seq2head, snd)
         for i in range(3):  # this rank's heads of the text tokens (n_txt x hd/N: a few hundred rows), beside the exchange
             joint[i][tot:].copy_(txt_qkv[i][:, r * hdn : (r + 1) * hdn])
-        if use_streams:
-            join()
+        self._join(snd)
         jq, jk, jv = joint[0], joint[1], joint[2]
         nq = tot + n_valid
         fast = self.attn_fn is None and (variant & 0xFF) == lib.ATTN_FAST
@@ -561,10 +516,7 @@ class UlyssesHunyuanAttention:
                 lib.attention(jq[rows], jk[:nq], jv[:nq], hl, 128, out=o[rows], variant=variant)
 
         # head->seq of the image rows in two pieces by destination rank: the first piece's exchange runs under the second piece's attention
-        split = self.split_head2seq
-        if split is True and not split_form_ok(self.group, o.device):
-            split = self.split_head2seq = False
-        plan = _split_plan(n, r, n_img, split)
+        plan = self._head2seq_plan(n_img, o.device)
         recv_all = a_img[:n].view(tot, hdn)
         for pi, (_, rows, in_split, out_split, rrows) in enumerate(plan):
             last = pi == len(plan) - 1
@@ -575,19 +527,17 @@ class UlyssesHunyuanAttention:
                     self.attn_fn(jq[pad], jk[pad], jv[pad], hl, o[pad])
                 else:
                     lib.attention(jq[pad], jk[pad], jv[pad], hl, 128, out=o[pad], variant=variant)
-            on_comm(lambda recv=recv_all[rrows], send=o[rows], out_split=out_split, in_split=in_split: dist.all_to_all_single(recv, send, out_split, in_split, group=self.group))
+            self._enqueue(lambda: dist.all_to_all_single(recv_all[rrows], o[rows], out_split, in_split, group=self.group), o)
         # text rows: every rank holds all text tokens for its heads -> gather the head blocks (block j = rank j's heads)
-        on_comm(lambda: dist.all_gather_into_tensor(a_txt[:n].view(n * n_txt, hdn), o[tot:], group=self.group))
-        if use_streams:
-            join()
+        self._enqueue(lambda: dist.all_gather_into_tensor(a_txt[:n].view(n * n_txt, hdn), o[tot:], group=self.group), o)
+        self._join(o)
         return a_img, a_txt
 
     # ---- row-major entry (the reference's functional form) -----------------------------------------------------------------
     def __call__(self, q, k, v, n_img, segs_txt, num_heads, out, variant=0):
-        """q, k, v: [n_img_local + n_txt, H*128] views; out: same rows, H*128 columns.  segs_txt = (n_valid_txt, n_txt)."""
-        n, r = _world(self.group)
-        if num_heads % n != 0:
-            raise lib.X2VError(f"Ulysses needs num_heads % world_size == 0 (H={num_heads}, N={n})")
+        """q, k, v: [n_img_local + n_txt, H*128] views; out: same rows, H*128 columns.  segs_txt = (n_valid_txt, n_txt).
+        Every collective of this entry runs on the calling stream, as it always did: a candidate for a later change of behaviour."""
+        n, r, hl = self._heads(num_heads)
         self.copies += 4  # three transposing sends + the gather of the received output
         hd = q.shape[1]
         hdn = hd // n
@@ -601,9 +551,9 @@ class UlyssesHunyuanAttention:
         o = torch.empty((tot + n_txt, hdn), dtype=q.dtype, device=q.device)
         n_valid = segs_txt[0]
         fn = self.attn_fn or (lambda a, b, c, h, oo: lib.attention(a, b, c, h, 128, out=oo, variant=variant))
-        fn(joint[0][: tot + n_valid], joint[1][: tot + n_valid], joint[2][: tot + n_valid], num_heads // n, o[: tot + n_valid])
+        fn(joint[0][: tot + n_valid], joint[1][: tot + n_valid], joint[2][: tot + n_valid], hl, o[: tot + n_valid])
         if n_valid < n_txt:
-            fn(joint[0][tot + n_valid :], joint[1][tot + n_valid :], joint[2][tot + n_valid :], num_heads // n, o[tot + n_valid :])
+            fn(joint[0][tot + n_valid :], joint[1][tot + n_valid :], joint[2][tot + n_valid :], hl, o[tot + n_valid :])
         # image rows: head→seq; the send buffer [N, n_img, hd/N] is o's image part as it is
         recv = torch.empty((n, n_img, hdn), dtype=q.dtype, device=q.device)
         dist.all_to_all_single(recv, o[:tot].view(n, n_img, hdn), group=self.group)

@@ -76,6 +76,17 @@ def test_ulysses_over_rccl_world1():
     assert "DIST_GPU_RCCL1_OK" in p.stdout
 
 
+def test_ulysses_hunyuan_over_rccl_world1():
+    """The Hunyuan driver over the real RCCL backend at world size 1: every collective of a forward on the one communication stream, counted, and
+    every enqueue and join bracketed by the CommTimer."""
+    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29555",
+           os.path.join(ROOT, "tests", "_dist_gpu_worker_hunyuan_rccl1.py")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    assert "DIST_GPU_HUNYUAN_RCCL1_OK" in p.stdout
+
+
 @pytest.mark.parametrize("gpus", [2, 4])
 def test_bench_n8_code_path_on_one_gpu(gpus):
     """`python bench.py --full --gpus N` (N = 2 bare, N = 4 under the launcher: what the driver's scaling run launches) END TO END on a one-GPU box (X2V_ONE_GPU_TEST=1: all ranks drive cuda:0 over gloo with host-staged collectives,
