@@ -493,6 +493,48 @@ int x2v_gemm_mxfp6_mxfp8_epi(const void* a, int64_t lda, const void* sa, const v
 int x2v_gemm_mxfp6_mxfp8_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
                                  const float* alpha, void* y, int64_t ldy, int64_t M, int N, int K, int variant, void* stream);
 
+/* MXFP4 quantisation (OCP microscaling, 4-bit elements), activations and weights alike — the w4a4 slot of the reference's kernel package, whose
+ * own pair (scaled_fp4_quant / cutlass_scaled_fp4_mm) is NVFP4: an e4m3 scale per 16 elements plus a global scale, which gfx950's matrix
+ * instruction does not apply.  This is x2v_quant_mxfp6_bf16's contract with 6 in place of 28 and e2m1 in place of e3m2:
+ * e2m1: 1 sign bit, 2 exponent bits (bias 1), 1 mantissa bit, code = s<<3 | e<<1 | m; e = 0: value m * 0.5, otherwise (2 + m) * 2^(e-2);
+ * magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; no NaN / Inf.
+ * Per 32 consecutive K elements the scale byte = biased exponent of the smallest power of two >= max|x| / 6 (the quotient in fp32 with
+ * denormals, saturating at 254; an all-zero block -> byte 0 and zero codes); code = e2m1(x * 2^(127 - byte)), one rounding to nearest-even on
+ * the e2m1 grid from the exact product (ties at 0.25, 1.25, 2.5 and 5 go down, at 0.75, 1.75 and 3.5 up), the sign of zero kept; +/-6 is
+ * reached by saturation only for NaN / Inf elements.
+ * x bf16 [M,K] (ldx % 8 == 0, 16-byte aligned); q bytes [M, K/2] (ldq in bytes, ldq % 8 == 0, ldq >= K/2, 8-byte aligned): two codes per byte,
+ * the dense little-endian nibble string — code j of a row sits at bits 4j .. 4j+3 of the row's bytes (the even code in the low nibble), the
+ * order in which the matrix instruction reads a lane's 16 bytes (tests/test_gpu_mx4.py walks it); scales: the [K/128][M][4] table of
+ * x2v_quant_mxfp8_bf16.  K % 128 == 0.
+ * NaN and Inf elements are outside the contract of their own 32-wide block and leave every other block as with 0 in their place
+ * (tests/test_gpu_mx4.py); measured, not promised: a NaN is skipped by the block maximum (the scale byte and the other 31 codes are those
+ * with 0 in its place) and saturates to +/-6 (e2m1 has no NaN code), an Inf gives scale byte 254, code 0x7 and +/-0 for the other 31
+ * (profiles/mx4_fp64_parity.txt). */
+int x2v_quant_mxfp4_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t M, int K, void* stream);
+
+/* y[M,N] = epi(alpha * (deq(a)[M,K] . deq(b)[N,K]^T) + bias[n]) → bf16 with a and b MXFP4 as written by x2v_quant_mxfp4_bf16: packed e2m1 codes
+ * [rows, K/2], lda and ldb in BYTES; deq = e2m1 value * 2^(scale byte - 127) of its row and 32-wide k block.  sa [K/128][M][4], sb [K/128][N][4];
+ * alpha: device pointer to one fp32 (NULL = 1), bias bf16 [N] or NULL; bias, alpha and the rounding points as x2v_gemm_mxfp8.
+ * Runs on v_mfma_scale_f32_32x32x64_f8f6f4 with both operands in format 4 (e2m1), the e8m0 block scales applied by the instruction: the form
+ * that takes the cycles of the bf16 instruction at four times the K.
+ * K % 256 == 0 (a 128-byte operand row per K-tile holds 256 k), N % 8 == 0; a, b, y: rows 16-byte aligned (lda % 16, ldb % 16, both >= K/2,
+ * ldy % 8); scale tables 4-byte, bias 8-byte aligned.  Anything else: X2V_E_SHAPE / X2V_E_ALIGN / X2V_E_ARG before any HIP call.
+ * Two bodies, chosen by x2v_gemm_mxfp8's rule on the number of 128-byte K-tiles (K / 256; from 6 K-tiles on, where MXFP8 wants 8): the fp4 mode
+ * of the 128x128-tile kernel and of the 256x256-tile ping-pong kernel (shapes that fill the chip and every fused epilogue; it addresses a tile with 32-bit offsets: lda, ldb < 2^24
+ * bytes, else X2V_E_SHAPE). */
+int x2v_gemm_mxfp4(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                   int64_t ldy, int64_t M, int N, int K, void* stream);
+
+/* x2v_gemm_mxfp4 with the fused epilogues of x2v_gemm_mxfp8_epi (X2V_EPI_*; X2V_EPI_RESIDUAL without resid: X2V_E_ARG): what the fused block
+ * drivers call for a linear layer held in MXFP4 (operator class MMWeightMxfp4Hip). */
+int x2v_gemm_mxfp4_epi(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                       int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
+
+/* Same with x2v_gemm_mxfp8_variant's kernel selector: 0 = automatic, 1 = 128x128-tile kernel, 2 = 256x256-tile ping-pong kernel; anything else:
+ * X2V_E_ARG. */
+int x2v_gemm_mxfp4_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                           void* y, int64_t ldy, int64_t M, int N, int K, int variant, void* stream);
+
 /* Timestep sinusoid: y[n, dim] bf16 = [cos(t*f_j) | sin(t*f_j)], f_j = 10000^(-j/(dim/2)) computed in
  * float64 then rounded — replaces sinusoidal_embedding_1d (wan/infer/utils.py:161-172).  t: int64 [n]. */
 int x2v_sinusoid_embed_bf16(const int64_t* t, void* y, int n, int dim, void* stream);

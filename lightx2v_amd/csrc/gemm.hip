@@ -3,7 +3,7 @@
 // it issues v_mfma_scale_f32_32x32x64_f8f6f4 with unit (2^0) block scales — the only fp8 MFMA that runs at
 // the 2x rate on gfx950 — and applies the per-token x per-channel fp32 scales in the epilogue.  Its MX mode (MXFP8, mx.hip's small shapes) hands
 // the same instruction the operands' own e8m0 block scales and multiplies by alpha in the epilogue; with MXM = 2 the weight operand is MXFP6 (packed
-// e3m2 codes, 96 bytes per row and K-tile).
+// e3m2 codes, 96 bytes per row and K-tile); with MXM = 3 both operands are MXFP4 (e2m1, two codes per byte: a 128-byte row per stage is 256 k-values).
 //
 // Bound: MFMA (bf16 dense peak ~2.5 PFLOP/s); algorithmic work 2*M*N*K FLOP per launch.
 //
@@ -57,6 +57,11 @@ struct alignas(16) Dword3 { int x, y, z; };  // the 12 valid bytes of a 16-byte 
 // MXM = 2 (MXFP6 weights x MXFP8 activations, mx.hip): MX with W rows of packed e3m2 codes, 96 bytes per row and K-tile in HBM, staged in 12-byte
 // pieces (16 codes) with the fp8 lane -> (row, chunk) map and swizzle into the same [128][128 B] image (12 of every 16 bytes used), the W fragment
 // two 12-byte pieces in the low 6 dwords, cbsz = 3; the x side, the scale dwords, the K loop, the waits and the epilogue are MXFP8's.
+// MXM = 3 (MXFP4 x MXFP4, mx.hip): both operands rows of packed e2m1 codes, format code 4 on both sides.  The stage image, the swizzle, the DMA and the
+// waits are MXFP8's; a K-tile is 256 k = 8 scale blocks = four MFMAs of K = 64 per accumulator tile, each reading ONE 16-byte chunk (32 codes = one
+// scale block, the low 4 of the 8 fragment dwords) per operand and lane.  Which 64 k an MFMA multiplies is free as long as both operands and their
+// scales agree, so MFMA s takes k blocks s (lanes of half 0) and 4 + s (half 1): chunk fh * 4 + s, and a lane needs ONE scale dword per operand row
+// and K-tile — entry 2 kt + fh of the [K/128][rows] table, whose byte s the instruction selects (opsel = s), with no shift.
 template <bool FP8, int EPI, bool I8, int MXM = 0>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                       const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
@@ -64,8 +69,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
                                                       const unsigned short* __restrict__ gate, const float* __restrict__ sx,
                                                       const float* __restrict__ sw, int ntm, int ntn, GemmBlocking gb,
                                                       const unsigned* __restrict__ SA, const unsigned* __restrict__ SB) {
-  constexpr bool MX = MXM != 0, MX6 = MXM == 2;
-  static_assert(MXM >= 0 && MXM <= 2 && (!MX || (FP8 && !I8)), "MX: block-scaled fp8 (1) or fp6 weights x fp8 (2)");
+  constexpr bool MX = MXM != 0, MX6 = MXM == 2, MX4 = MXM == 3;
+  constexpr int NSD = MX4 ? 2 : 1;  // scale-table entries ([K/128][rows] dwords) per K-tile
+  static_assert(MXM >= 0 && MXM <= 3 && (!MX || (FP8 && !I8)), "MX: block-scaled fp8 (1), fp6 weights x fp8 (2) or fp4 x fp4 (3)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int a_kpb = gb.a_kpb > 0 && gb.a_kpb < nk ? gb.a_kpb : nk;
   const int tid = threadIdx.x;
@@ -131,7 +137,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int c = MX ? ((ks >> 1) * 4 + (ks & 1) * 2 + fh) : (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
+      // MXFP4 (probed with one-hot codes on both sides): a lane's 16 bytes are 32 consecutive k, low nibble first; MFMA ks reads chunk fh*4 + ks
+      const int c = MX4 ? (fh * 4 + ks) : MX ? ((ks >> 1) * 4 + (ks & 1) * 2 + fh) : (FP8 && !I8) ? ((ks >> 1) * 4 + fh * 2 + (ks & 1)) : (ks * 2 + fh);
       a_off[i][ks] = swz_off(wr * 64 + i * 32 + fl, c);
       // MXFP6 W (probed with one-hot codes against a one-hot x): the 32 codes of a lane are k = fh*32 .. +31 in order (scale block fh), not the fp8
       // fragment's two halves: 12-byte chunks s*4 + fh*2 and s*4 + fh*2 + 1
@@ -143,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
   // The dwords of a K-tile are loaded with its stage (sa_nxt / sb_nxt) and adopted, shifted, at the top of the iteration that multiplies it.
   const unsigned* sa_row[2];
   const unsigned* sb_row[2];
-  const int sh = fh * 8;
+  const int sh = MX4 ? 0 : fh * 8;  // MXFP4: half fh reads its own table entry instead
   unsigned sa_cur[2], sb_cur[2], sa_nxt[2], sb_nxt[2];
   if constexpr (MX) {
 #pragma unroll
@@ -152,8 +159,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
       gm = gm < M ? gm : M - 1;
       int gn = n0 + wc * 64 + i * 32 + fl;
       gn = gn < N ? gn : N - 1;
-      sa_row[i] = SA + gm;  // [K-tile][row] dwords
-      sb_row[i] = SB + gn;
+      sa_row[i] = SA + gm + (MX4 ? fh * M : 0);  // [K-tile][row] dwords
+      sb_row[i] = SB + gn + (MX4 ? fh * (int64_t)N : 0);
       sa_nxt[i] = sa_row[i][0];
       sb_nxt[i] = sb_row[i][0];
     }
@@ -193,8 +200,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
       if constexpr (MX) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          sa_nxt[i] = sa_row[i][(int64_t)(kt + 1) * M];
-          sb_nxt[i] = sb_row[i][(int64_t)(kt + 1) * N];
+          sa_nxt[i] = sa_row[i][(int64_t)(kt + 1) * NSD * M];
+          sb_nxt[i] = sb_row[i][(int64_t)(kt + 1) * NSD * N];
         }
       }
     }
@@ -227,6 +234,23 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const char* __restrict__ A
 #pragma unroll
           for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wb[j], xa[i], acc[i][j], 0, 0, 0);
       }
+    } else if constexpr (MX4) {
+      // format 4 = e2m1 for both operands, 32 codes = 4 dwords (the instruction reads the low 4 of the 8); first = W fragment, second = x fragment, as below
+#define G_MX4_STEP(KS_)                                                                                                                       \
+  {                                                                                                                                           \
+    i32x8_t xa[2], wb[2];                                                                                                                     \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                                           \
+      const i32x4_t a0 = *reinterpret_cast<const i32x4_t*>(base + a_off[i][KS_]);                                                             \
+      const i32x4_t b0 = *reinterpret_cast<const i32x4_t*>(base + b_off[i][KS_]);                                                             \
+      xa[i] = i32x8_t{a0[0], a0[1], a0[2], a0[3], 0, 0, 0, 0};                                                                                \
+      wb[i] = i32x8_t{b0[0], b0[1], b0[2], b0[3], 0, 0, 0, 0};                                                                                \
+    }                                                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                                             \
+      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                                           \
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 4, 4, KS_, (int)sb_cur[j], KS_, (int)sa_cur[i]); \
+  }
+      G_MX4_STEP(0) G_MX4_STEP(1) G_MX4_STEP(2) G_MX4_STEP(3)
+#undef G_MX4_STEP
     } else {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -405,6 +429,22 @@ int gemm128_mx6_dispatch(const void* a, int64_t lda, const void* sa, const void*
                      (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
                      (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
   X2V_LAUNCH_CHECK("gemm_mxfp6_mxfp8 launch");
+  return X2V_OK;
+}
+
+// MXFP4 x MXFP4 (mx.hip), shapes below the 256x256 kernel's: a, b = packed e2m1 codes [rows, K/2], lda / ldb in bytes, nk = K / 256.  No fused
+// epilogue (those go to gemm256_mx4_dispatch).  Arguments validated by the caller.
+int gemm128_mx4_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
+                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
+  const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
+  {
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 3>, G_LDS_BYTES, "gemm_mxfp4 attr");
+    if (rc != X2V_OK) return rc;
+  }
+  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 3>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
+                     (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
+                     (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
+  X2V_LAUNCH_CHECK("gemm_mxfp4 launch");
   return X2V_OK;
 }
 }  // namespace x2v

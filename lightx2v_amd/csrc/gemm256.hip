@@ -44,6 +44,11 @@ struct alignas(16) T_Dword3 { int x, y, z; };  // the 12 valid bytes of a 16-byt
 // e3m2 codes, 96 bytes per row and K-tile, staged in 12-byte pieces (buffer_load_dwordx3 ... lds keeps the 16-byte lane stride in LDS and leaves the
 // fourth dword alone, so the half-tile image, the swizzle, the DMA instruction count and the counted vmcnt waits are MXFP8's), W fragments of
 // 6 dwords in the instruction's fp6 order (a lane's 32 codes are k = fh*32 .. +31), cbsz = 3.
+// 3 = MXFP4 x MXFP4: both operands rows of packed e2m1 codes (two per byte), format code 4 on both sides.  A 128-byte row per K-tile holds 256 k, so
+// the half-tile image, the swizzle, the DMA count and the counted waits are MXFP8's again.  A phase is 8 MFMAs of K = 64: k-step s of 4 reads the one
+// 16-byte chunk fh * 4 + s per operand and lane (a lane's 32 codes are 32 consecutive k = one scale block; which 64 k an MFMA multiplies is free as
+// long as both operands and their scales agree), so a lane takes ONE scale dword per operand row and K-tile — entry 2 t + fh of the [K/128][rows]
+// table, byte s by opsel, no shift — and the scale registers and the 6 scale loads per K-tile are MXFP8's too.
 template <bool FP8, int EPI, int LEAD, int KW, int MXM>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict__ A, int64_t lda_bytes, const char* __restrict__ W, int64_t ldw_bytes,
                                                          const unsigned short* __restrict__ bias, unsigned short* __restrict__ Y, int64_t ldy, int64_t M,
@@ -53,8 +58,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
                                                          const unsigned* __restrict__ SA, const unsigned* __restrict__ SB, GemmBlocking gb) {
 #if defined(__HIP_DEVICE_COMPILE__)
   static_assert(LEAD >= KW + 3 && LEAD <= 7 && LEAD >= 4, "see the hazard accounting in the header comment (and the A-half K offsets ak1/ak2)");
-  constexpr bool MX = MXM != 0, MX6 = MXM == 2;
-  static_assert(MXM >= 0 && MXM <= 2 && (!MX || FP8), "MX: block-scaled fp8 (1) or fp6 weights x fp8 (2)");
+  constexpr bool MX = MXM != 0, MX6 = MXM == 2, MX4 = MXM == 3;
+  constexpr int NSD = MX4 ? 2 : 1;  // scale-table entries ([K/128][rows] dwords) per K-tile
+  static_assert(MXM >= 0 && MXM <= 3 && (!MX || FP8), "MX: block-scaled fp8 (1), fp6 weights x fp8 (2) or fp4 x fp4 (3)");
   // bf16 runs on v_mfma_f32_16x16x32_bf16: at the board's power limit (where this kernel lives) the 16x16 shape delivers ~11 % more FLOP/s
   // than 32x32x16 for the same LDS fragment traffic (tools/probes/mfma_power_probe.hip, profiles/r02_mfma_power_probe.log)
   constexpr bool MI16 = !FP8;
@@ -142,10 +148,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
       }
   } else {
     const int swz = (fl >> 1) & 7;
-    const int lp = fh ^ swz;
+    const int lp = (MX4 ? fh << 2 : fh) ^ swz;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int kp = FP8 ? (((ks >> 1) << 2) | ((ks & 1) << 1)) : (ks << 1);
+      const int kp = MX4 ? ks : FP8 ? (((ks >> 1) << 2) | ((ks & 1) << 1)) : (ks << 1);  // MXFP4: k-step ks reads chunk fh*4 + ks
       const int o = fl * 128 + ((lp ^ kp) << 4);
       rd_a[ks] = o + wr * 4096;
       // MXFP6 W: MFMA s reads the 12-byte pieces s*4 + fh*2 and s*4 + fh*2 + 1 (the lane's 32 codes are consecutive k)
@@ -179,28 +185,30 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
   if constexpr (MX) {
     // whole tables behind the descriptors; rows of a partial last tile read a neighbour's scales (their outputs are never stored) or,
     // past the end of the table, zero
-    rsa = __builtin_amdgcn_make_buffer_rsrc((void*)SA, 0, (unsigned)((int64_t)nk * M * 4), 0x00020000);
-    rsb = __builtin_amdgcn_make_buffer_rsrc((void*)SB, 0, (unsigned)((int64_t)nk * N * 4), 0x00020000);
-    sa_voff = (unsigned)((m0 + wr * 32 + fl) * 4);
-    sb_voff = (unsigned)((n0 + wc * 32 + fl) * 4);
+    rsa = __builtin_amdgcn_make_buffer_rsrc((void*)SA, 0, (unsigned)((int64_t)nk * NSD * M * 4), 0x00020000);
+    rsb = __builtin_amdgcn_make_buffer_rsrc((void*)SB, 0, (unsigned)((int64_t)nk * NSD * N * 4), 0x00020000);
+    sa_voff = (unsigned)((m0 + wr * 32 + fl + (MX4 ? fh * M : 0)) * 4);  // MXFP4: half fh reads its own table entry
+    sb_voff = (unsigned)((n0 + wc * 32 + fl + (MX4 ? fh * (int64_t)N : 0)) * 4);
   }
 #define T_SC_LOAD(T_)                                                                                                          \
   {                                                                                                                            \
     _Pragma("unroll") for (int mi_ = 0; mi_ < 4; ++mi_)                                                                        \
-      sx_nxt[mi_] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsa, sa_voff, (unsigned)((int64_t)(T_) * M * 4) + (unsigned)(mi_ * 256), 0); \
+      sx_nxt[mi_] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsa, sa_voff, (unsigned)((int64_t)(T_) * NSD * M * 4) + (unsigned)(mi_ * 256), 0); \
     _Pragma("unroll") for (int nj_ = 0; nj_ < 2; ++nj_)                                                                        \
-      sw_nxt[nj_] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsb, sb_voff, (unsigned)((int64_t)(T_) * N * 4) + (unsigned)(nj_ * 512), 0); \
+      sw_nxt[nj_] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsb, sb_voff, (unsigned)((int64_t)(T_) * NSD * N * 4) + (unsigned)(nj_ * 512), 0); \
   }
 #define T_SC_ADOPT()                                                                                                           \
   {                                                                                                                            \
-    _Pragma("unroll") for (int mi_ = 0; mi_ < 4; ++mi_) sx_cur[mi_] = sx_nxt[mi_] >> (fh * 8);                                 \
-    _Pragma("unroll") for (int nj_ = 0; nj_ < 2; ++nj_) sw_cur[nj_] = sw_nxt[nj_] >> (fh * 8);                                 \
+    _Pragma("unroll") for (int mi_ = 0; mi_ < 4; ++mi_) sx_cur[mi_] = sx_nxt[mi_] >> (MX4 ? 0 : fh * 8);                       \
+    _Pragma("unroll") for (int nj_ = 0; nj_ < 2; ++nj_) sw_cur[nj_] = sw_nxt[nj_] >> (MX4 ? 0 : fh * 8);                       \
   }
 
   const int total = nk * 4;  // half-tiles in this tile's K loop
 
+  // (MXFP4: chunk (fh*4 + ks) ^ swz = chunk(0) ^ ks — one address register per operand, the k-step by an exclusive or in front of the read: with four
+  // the body spilled a VGPR)
 #define T_RD(DST_, SLOT_, RD_, EXTRA_) \
-  _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) DST_[ks_] = *reinterpret_cast<const i32x4_t*>(smem + (SLOT_) * T_HALF_BYTES + (EXTRA_) + RD_[ks_]);
+  _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) DST_[ks_] = *reinterpret_cast<const i32x4_t*>(smem + (SLOT_) * T_HALF_BYTES + (EXTRA_) + (MX4 ? RD_[0] ^ (ks_ << 4) : RD_[ks_]));
 
   // W fragments; MXFP6: 12 bytes per slot (ds_read_b96), so a phase's W fragments hold 12 VGPRs, not 16 (with ds_read_b128 and the fourth dword
   // dropped afterwards the kernel spilled 14 VGPRs)
@@ -212,6 +220,15 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
     }                                                                                                                          \
   } else { T_RD(DST_, SLOT_, rd_b, 0) }
 
+  // MXFP4: k-step S_ (a literal: opsel) of one phase, both row blocks
+#define T_MFMA4(MI0_, NJ_, WB_, S_)                                                                                            \
+  {                                                                                                                            \
+    const i32x8_t wf_ = i32x8_t{WB_[S_][0], WB_[S_][1], WB_[S_][2], WB_[S_][3], 0, 0, 0, 0};                                   \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                                         \
+      const i32x8_t xf_ = i32x8_t{xa[i_][S_][0], xa[i_][S_][1], xa[i_][S_][2], xa[i_][S_][3], 0, 0, 0, 0};                     \
+      acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf_, xf_, acc[(MI0_) + i_][NJ_], 4, 4, S_, (int)sw_cur[NJ_], S_, (int)sx_cur[(MI0_) + i_]); \
+    }                                                                                                                          \
+  }
   // 8 MFMAs (fp8: 4) of one phase
 #define T_MFMA(MI0_, NJ_, WB_, I0_, I1_)                                                                                                 \
   if constexpr (MI16) {                                                                                                        \
@@ -226,6 +243,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
       acc[(MI0_) + i_][NJ_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, WB_[ks_]),                  \
                                                                       __builtin_bit_cast(bf16x8_t, xa[i_][ks_]), acc[(MI0_) + i_][NJ_], 0, 0, 0); \
     }                                                                                                                          \
+  } else if constexpr (MX4) { /* 8 MFMAs: k-step s of 4, one 16-byte chunk per operand in the low 4 fragment dwords, format 4 on both sides */ \
+    T_MFMA4(MI0_, NJ_, WB_, 0) T_MFMA4(MI0_, NJ_, WB_, 1) T_MFMA4(MI0_, NJ_, WB_, 2) T_MFMA4(MI0_, NJ_, WB_, 3)                 \
   } else {                                                                                                                     \
     constexpr int kOne = 0x7f7f7f7f; /* e8m0 2^0 block scales */                                                               \
     _Pragma("unroll") for (int idx_ = (I0_) / 4; idx_ < (I1_) / 4; ++idx_) {                                                   \
@@ -354,6 +373,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const char* __restrict_
 #undef T_AK_NEXT
 #undef T_PIN
 #undef T_MFMA
+#undef T_MFMA4
 #undef T_MFMA_Q
 #undef T_RD
 #undef T_RDW
@@ -493,6 +513,13 @@ int gemm256_mx6_dispatch(int epilogue, const void* a, int64_t lda, const void* s
                          void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
   return with_epilogue("gemm_mxfp6_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
     return launch_gemm256<true, decltype(epi)::value, 2>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+  });
+}
+// MXFP4 x MXFP4 (mx.hip): a, b = packed e2m1 codes [rows, K/2], lda / ldb in bytes, nk = K / 256.  Arguments validated by the caller.
+int gemm256_mx4_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
+                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
+  return with_epilogue("gemm_mxfp4", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    return launch_gemm256<true, decltype(epi)::value, 3>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
   });
 }
 

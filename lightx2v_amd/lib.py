@@ -75,6 +75,10 @@ PROTOTYPES = {
     "x2v_gemm_mxfp6_mxfp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p],
     "x2v_gemm_mxfp6_mxfp8_epi": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_mxfp6_mxfp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
+    "x2v_quant_mxfp4_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_gemm_mxfp4_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p],
+    "x2v_gemm_mxfp4_epi": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "x2v_gemm_mxfp4": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
     "x2v_gemm_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_fp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
     "x2v_quant_int8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
@@ -907,6 +911,20 @@ def quant_mxfp6(x):
     return q, sc
 
 
+def quant_mxfp4(x):
+    """bf16 [M, K] → (uint8 [M, K/2]: e2m1 codes, two per byte, the dense little-endian nibble string, code j of a row at bits 4j .. 4j+3 of its
+    bytes; e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp4_bf16."""
+    x2 = _row2d(_bf16(x, "x"), "x")
+    M, K = x2.shape
+    q = torch.empty((M, K // 2), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((max(K // 128, 1), M, 4), dtype=torch.uint8, device=x.device)
+    init()
+    if M == 0:
+        return q, sc
+    _check(_lib.x2v_quant_mxfp4_bf16(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), "quant_mxfp4")
+    return q, sc
+
+
 def mx_scales_rowmajor(sc):
     """[K/128, rows, 4] (kernel layout) → logical [rows, K/32]."""
     return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
@@ -918,19 +936,24 @@ def mx_scales_tiled(sc_rm):
     return sc_rm.reshape(rows, kb // 4, 4).permute(1, 0, 2).contiguous()
 
 
-def _gemm_mx(tag, fp6, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate):
-    """gemm_mxfp8 and gemm_mxfp6_mxfp8: one set of checks, the entries x2v_gemm_<tag>_variant / _epi.  fp6: b is the packed uint8 [N, 3K/4]."""
-    M, K = a.shape
+_MX_PACKED = {6: "uint8 matrix of packed e3m2 codes [rows, 3K/4]", 4: "uint8 matrix of packed e2m1 codes [rows, K/2]"}
+
+
+def _gemm_mx(tag, bits_a, bits_b, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate):
+    """gemm_mxfp8, gemm_mxfp6_mxfp8 and gemm_mxfp4: one set of checks, the entries x2v_gemm_<tag>_variant / _epi.  bits_a, bits_b: the element width
+    of each operand — 8: e4m3 bytes [rows, K]; 6: the packed uint8 [rows, 3K/4]; 4: the packed uint8 [rows, K/2] (K % 256 == 0)."""
+    M = a.shape[0]
+    K = a.shape[1] * 8 // bits_a
     N = b.shape[0]
-    if a.dtype not in (torch.float8_e4m3fn, torch.uint8) or not a.is_cuda or a.stride(1) != 1:
-        raise X2VError(f"gemm_{tag}: a must be a CUDA e4m3 (or raw uint8) matrix with unit inner stride")
-    if b.dtype not in ((torch.uint8,) if fp6 else (torch.float8_e4m3fn, torch.uint8)) or not b.is_cuda or b.stride(1) != 1:
-        raise X2VError(f"gemm_{tag}: b must be a CUDA " + ("uint8 matrix of packed e3m2 codes [N, 3K/4]" if fp6 else "e4m3 (or raw uint8) matrix") + " with unit inner stride")
+    kmult = 256 if 4 in (bits_a, bits_b) else 128
+    for t, name, bits in ((a, "a", bits_a), (b, "b", bits_b)):
+        if t.dtype not in ((torch.float8_e4m3fn, torch.uint8) if bits == 8 else (torch.uint8,)) or not t.is_cuda or t.stride(1) != 1:
+            raise X2VError(f"gemm_{tag}: {name} must be a CUDA " + (_MX_PACKED[bits] if bits != 8 else "e4m3 (or raw uint8) matrix") + " with unit inner stride")
     for t, name, rows in ((sa, "scales_a", M), (sb, "scales_b", N)):
         if t.element_size() != 1 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (K // 128, rows, 4):
             raise X2VError(f"gemm_{tag}: {name} must be the contiguous CUDA byte tensor [K/128, {rows}, 4] of quant_mxfp8, got {tuple(t.shape)}")
-    if b.shape[1] != (K // 4 * 3 if fp6 else K) or K % 128:
-        raise X2VError(f"gemm_{tag}: shapes a{tuple(a.shape)} b{tuple(b.shape)} do not agree (K % 128 == 0" + (", b holds 3K/4 bytes per row)" if fp6 else ")"))
+    if a.shape[1] * 8 % bits_a or b.shape[1] != K * bits_b // 8 or K % kmult:
+        raise X2VError(f"gemm_{tag}: shapes a{tuple(a.shape)} b{tuple(b.shape)} do not agree (K % {kmult} == 0, a row holds {bits_a}K/8 bytes of a and {bits_b}K/8 of b)")
     if alpha is not None and (alpha.dtype != torch.float32 or not alpha.is_cuda):
         raise X2VError(f"gemm_{tag}: alpha must be a float32 CUDA tensor")
     if bias is not None:
@@ -964,13 +987,19 @@ def _gemm_mx(tag, fp6, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid,
 def gemm_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
     """alpha * deq(a)[M,K] @ deq(b)[N,K]^T + bias → bf16 [M,N]; scales uint8/e8m0 [K/128, rows, 4] as produced by quant_mxfp8;
     alpha: fp32 device tensor or None."""
-    return _gemm_mx("mxfp8", False, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
+    return _gemm_mx("mxfp8", 8, 8, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
 
 
 def gemm_mxfp6_mxfp8(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
     """gemm_mxfp8 with b = the packed e3m2 codes uint8 [N, 3K/4] and scales of quant_mxfp6; a and sa from quant_mxfp8.  variant as gemm_mxfp8 — see
     include/x2v.h::x2v_gemm_mxfp6_mxfp8."""
-    return _gemm_mx("mxfp6_mxfp8", True, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
+    return _gemm_mx("mxfp6_mxfp8", 8, 6, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
+
+
+def gemm_mxfp4(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogue=EPI_NONE, resid=None, gate=None):
+    """gemm_mxfp8 with both operands the packed e2m1 codes uint8 [rows, K/2] and scales of quant_mxfp4 (K % 256 == 0).  variant as gemm_mxfp8 — see
+    include/x2v.h::x2v_gemm_mxfp4."""
+    return _gemm_mx("mxfp4", 4, 4, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
 
 
 def _gemm8(kind, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period):

@@ -7,6 +7,11 @@ straight back to the GEMM (`lib.mx_scales_rowmajor` gives the logical [rows, K/3
     a_q, a_s = scaled_fp8_quant(activation)          # bf16 [m, k] -> e4m3 bytes [m, k], e8m0 [k/128, m, 4]
     w_q, w_s = scaled_fp8_quant(weight)              # [n, k]
     y = cutlass_scaled_mxfp8_mm(a_q, w_q, a_s, w_s, alpha=alpha, bias=bias)   # bf16 [m, n]
+
+The package's 4-bit pair, `scaled_fp4_quant(input, input_global_scale)` / `cutlass_scaled_fp4_mm`, is NOT mirrored under its names: it is NVFP4 (e2m1
+elements with one e4m3 scale per 16 elements plus a global fp32 scale), and gfx950's block-scaled matrix instruction applies one e8m0 scale per
+32 elements and nothing else.  The w4a4 slot is filled by MXFP4 x MXFP4 under names of its own, `scaled_mxfp4_quant` / `scaled_mxfp4_mm` below:
+the same e2m1 elements and rounding table, the scale format the hardware has.
 """
 import torch
 
@@ -47,3 +52,23 @@ def cutlass_scaled_mxfp6_mxfp8_mm(mat_a, mat_b, scales_a, scales_b, alpha, bias=
 
 
 scaled_mxfp6_mxfp8_mm = cutlass_scaled_mxfp6_mxfp8_mm
+
+
+# ---- MXFP4 x MXFP4: the w4a4 slot.  The reference's `scaled_fp4_quant(input, input_global_scale)` / `cutlass_scaled_fp4_mm` (gemm.py) are NVFP4:
+#      e2m1 elements with one e4m3 scale per 16 elements plus a global fp32 scale.  gfx950's matrix instruction applies one e8m0 scale per 32
+#      elements and nothing else, so those two names are NOT aliased here: a tensor quantised for one format is garbage to the other.  What runs is
+#      MXFP4 (OCP: e2m1 elements, two codes per byte, code j of a row at bits 4j .. 4j+3, the e8m0 table above), activations and weights alike.
+#      K must be a multiple of 256.
+#
+#     w_q, w_s = scaled_mxfp4_quant(weight)            # bf16 [n, k] -> uint8 [n, k/2], e8m0 [k/128, n, 4]
+#     a_q, a_s = scaled_mxfp4_quant(activation)
+#     y = scaled_mxfp4_mm(a_q, w_q, a_s, w_s, alpha=alpha, bias=bias)
+def scaled_mxfp4_quant(input: torch.Tensor):
+    q, sc = lib.quant_mxfp4(input)
+    return q, (sc.view(_E8M0) if _E8M0 is not None else sc)
+
+
+def scaled_mxfp4_mm(mat_a, mat_b, scales_a, scales_b, alpha, bias=None):
+    sa = scales_a.view(torch.uint8) if scales_a.dtype != torch.uint8 else scales_a
+    sb = scales_b.view(torch.uint8) if scales_b.dtype != torch.uint8 else scales_b
+    return lib.gemm_mxfp4(mat_a, sa, mat_b, sb, alpha=alpha, bias=None if bias is None else bias.reshape(-1))

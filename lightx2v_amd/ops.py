@@ -263,6 +263,29 @@ class MMWeightMxfp6Hip(MMWeightMxfp8Hip):
     _gemm = staticmethod(lib.gemm_mxfp6_mxfp8)
 
 
+@MM_WEIGHT_REGISTER("W-mxfp4-A-mxfp4-dynamic-Hip")
+class MMWeightMxfp4Hip(MMWeightMxfp8Hip):
+    """MXFP4 weights x MXFP4 activations (OCP e2m1, two codes per byte, one e8m0 scale per 32 K elements on both sides): the w4a4 slot of the
+    reference's kernel package (`scaled_fp4_quant` + `cutlass_scaled_fp4_mm`, NVFP4) filled with the 4-bit format gfx950's matrix instruction has.
+    MMWeightMxfp8Hip's protocol with the MXFP4 quantiser on both sides: the weight is uint8 [N, K/2] with the e8m0 table [K/128, N, 4] under
+    `<name>_scale`; a fused driver's shared quantised activation is `quantize_input`'s pair.  K % 256 == 0."""
+
+    def load(self, weight_dict):
+        w = weight_dict[self.weight_name]
+        if not w.is_cuda:
+            raise lib.X2VError(f"{self.weight_name}: MXFP4 weights are quantised by the HIP kernel at load — tensor is on {w.device}")
+        if w.dtype == torch.uint8:  # what state_dict wrote: the packed codes with their table
+            self.weight, self.weight_scale = w.contiguous(), weight_dict[self.weight_name + "_scale"].view(torch.uint8).contiguous()
+        else:
+            self.weight, self.weight_scale = lib.quant_mxfp4(w.to(torch.bfloat16).contiguous())
+        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
+
+    def quantize_input(self, input_tensor):
+        return lib.quant_mxfp4(input_tensor)
+
+    _gemm = staticmethod(lib.gemm_mxfp4)
+
+
 @RMS_WEIGHT_REGISTER("hip")
 class RMSWeightHip(_Movable):
     """reference: common/ops/norm/rms_norm_weight.py:53-118.  `round_mode`: fp32 statistics (what

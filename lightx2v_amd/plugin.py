@@ -28,6 +28,7 @@ def register_into_reference():
         (rf.MM_WEIGHT_REGISTER, "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip", ops.MMWeightInt8Hip),
         (rf.MM_WEIGHT_REGISTER, "W-mxfp8-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp8Hip),
         (rf.MM_WEIGHT_REGISTER, "W-mxfp6-A-mxfp8-dynamic-Hip", ops.MMWeightMxfp6Hip),
+        (rf.MM_WEIGHT_REGISTER, "W-mxfp4-A-mxfp4-dynamic-Hip", ops.MMWeightMxfp4Hip),
         (rf.ATTN_WEIGHT_REGISTER, "hip_flash", ops.HipFlashAttnWeight),
         (rf.ATTN_WEIGHT_REGISTER, "hip_radial", ops.HipRadialAttnWeight),
         (rf.ATTN_WEIGHT_REGISTER, "hip_mxfp8", ops.HipMxfp8AttnWeight),

@@ -2,7 +2,7 @@
 """End-to-end wall clock of the hot path on one GPU: the full denoise loop (all infer_steps, CFG) followed by the VAE decode of the
 final latents — the quantity BASELINE.json's north star asks for next to the per-step number ("end-to-end wall-clock and frames/sec").
 Synthetic weights and inputs of the named shape (the text encoder's output is an input here, as in bench.py, unless --t5 is given).  One JSON line.
-    python tools/e2e.py [--workload wan14b_720px81f] [--steps 50] [--fp8|--int8|--mxfp8|--mxfp6] [--distill] [--teacache T]
+    python tools/e2e.py [--workload wan14b_720px81f] [--steps 50] [--fp8|--int8|--mxfp8|--mxfp6|--mxfp4] [--distill] [--teacache T]
     python tools/e2e.py --i2v --image PATH | --encode   (image → CLIP tower + VAE encode → loop → decode; --encode: a seeded synthetic 720p image;
                                                          --clip-ckpt PATH: the CLIP checkpoint instead of seeded synthetic tower weights)
     python tools/e2e.py --t5   (context / context_null from seeded token ids through the HIP umT5-XXL encoder, seeded weights, timed as t5_encode_s)
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--int8", action="store_true", help="w8a8 int8 linear layers (the reference's int8 presets), weights quantised at load")
     ap.add_argument("--mxfp8", action="store_true")
     ap.add_argument("--mxfp6", action="store_true", help="MXFP6 (e3m2) weights x MXFP8 activations, weights quantised at load")
+    ap.add_argument("--mxfp4", action="store_true", help="MXFP4 (e2m1) weights x MXFP4 activations, weights quantised at load (every linear K a multiple of 256)")
     ap.add_argument("--distill", action="store_true", help="4-step distilled schedule, no CFG (BASELINE config #4)")
     ap.add_argument("--vae16", action="store_true", help="fastest VAE decode: convolution operands rounded to fp16")
     ap.add_argument("--vae32", action="store_true", help="VAE convolutions on the fp32 matrix instruction (default: hi/lo fp16 split, fp32-grade)")
@@ -74,6 +75,8 @@ def main():
         extra["mm_config"] = {"mm_type": "W-mxfp8-A-mxfp8-dynamic-Hip", "weight_auto_quant": True}
     if a.mxfp6:
         extra["mm_config"] = {"mm_type": "W-mxfp6-A-mxfp8-dynamic-Hip", "weight_auto_quant": True}
+    if a.mxfp4:
+        extra["mm_config"] = {"mm_type": "W-mxfp4-A-mxfp4-dynamic-Hip", "weight_auto_quant": True}
     if a.distill:
         extra.update(enable_cfg=False, denoising_step_list=[1000, 750, 500, 250], sample_shift=5.0)
     if a.teacache > 0:
@@ -232,7 +235,7 @@ def main():
     t2 = time.perf_counter()
     assert torch.isfinite(video).all() and torch.isfinite(sch.latents).all()
     frames = wl["frames"]
-    rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"{'ring' if a.ring else 'ulysses'}-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp6xmxfp8" if a.mxfp6 else "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
+    rec = {"workload": a.workload, "task": dims.get("task", "t2v"), "guide_scale": cfg["sample_guide_scale"], "sample_shift": cfg["sample_shift"], "n_gpus": world, "parallelism": f"{'ring' if a.ring else 'ulysses'}-sp{world} + decode_dist" if world > 1 else "single", "steps": steps, "cfg": bool(cfg["enable_cfg"]), "gemm_dtype": "mxfp4" if a.mxfp4 else "mxfp6xmxfp8" if a.mxfp6 else "mxfp8" if a.mxfp8 else "int8" if a.int8 else "fp8" if a.fp8 else "bf16",
            "teacache_thresh": a.teacache, "vae_conv_operands": "bf16 (tiny VAE / TAEHV)" if a.tiny_vae else "fp16" if a.vae16 else "fp32" if a.vae32 else "fp16 hi/lo split (fp32-grade)", "tiny_vae": bool(a.tiny_vae), "vae_tiling": bool(a.tiling_vae and world == 1), "denoise_s": t1 - t0, "ms_per_step": (t1 - t0) * 1e3 / steps, "vae_decode_s": t2 - t1, "total_s": t2 - t0,
            "frames": frames, "video_shape": list(video.shape), "fps_denoise_only": frames / (t1 - t0), "fps_with_vae": frames / (t2 - t0),
            "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}
