@@ -50,9 +50,9 @@ def case(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------- buffers
-def window(rows, HD):
+def window(rows, HD, dtype=BF16):
     """A poisoned [rows + 4, HD + 4] buffer and its [rows, HD] window (two rows down: a 16-byte aligned start with an 8-byte aligned token stride)."""
-    big = torch.full((rows + 4, HD + 4), POISON, dtype=BF16, device="cuda")
+    big = torch.full((rows + 4, HD + 4), POISON, dtype=dtype, device="cuda")
     return big, big[2 : rows + 2, :HD]
 
 
