@@ -204,6 +204,17 @@ int x2v_attn_fwd_bf16_variant(const void* q, int64_t ldq, const void* k, int64_t
  * keys >= Sk zero-filled (ldvt % 64 == 0, ldvt >= Sk): the operand layout of x2v_attn_fwd_bf16_vt. */
 int x2v_transpose_heads_bf16(const void* v, int64_t ldv, void* vt, int64_t ldvt, int64_t Sk, int H, void* stream);
 
+/* Append to a V^T cache — the KV cache of the autoregressive Wan (models/networks/wan/infer/causvid/transformer_infer.py:85-120, where the cache is
+ * row-major and flash-attention reads it in place): v [S, H*128] bf16 (token stride ldv) into the key columns [key0, key0 + S) of
+ * vt [H][ldvt/64][128][64] bf16.  After the call key key0 + s of head h, component dv — element vt[((h * (ldvt/64) + (key0+s)/64) * 128 + dv) * 64 +
+ * (key0+s) % 64] — holds v[s][h*128 + dv] for 0 <= s < S, a bit copy, and NO other byte of vt has changed: not the keys < key0 (the key0 % 64 of them
+ * that share the first tile included), not the keys >= key0 + S (the rest of the last tile included), no other tile.  No row of v outside [0, S) is
+ * read.  key0 and S are arbitrary (odd too); ranges whose ends are multiples of 8 keys take a kernel without the edge handling.
+ * Appends to one cache, and the attention launches over it, must be ordered on one stream.
+ * ldvt % 64 == 0, key0 >= 0, S >= 0, key0 + S <= ldvt, 1 <= H <= 65535 (else X2V_E_SHAPE); v, vt 16-byte aligned and ldv % 8 == 0 (X2V_E_ALIGN);
+ * ldv >= H*128; S == 0 is X2V_OK without a launch. */
+int x2v_transpose_heads_append_bf16(const void* v, int64_t ldv, void* vt, int64_t ldvt, int64_t key0, int64_t S, int H, void* stream);
+
 /* x2v_attn_fwd_bf16 on a pre-transposed V (x2v_transpose_heads_bf16) — the "ping-pong" kernel the fused block drivers launch for
  * self-attention (transformer_infer.py:369-379): V^T is staged by LDS-DMA and read as plain 16-byte fragments, the softmax scale * log2(e)
  * lives in q.  flags: X2V_ATTN_VT_PRESCALED — q already carries scale*log2(e) (x2v_rmsnorm_rope_scaled_bf16 / x2v_headnorm_rope_bf16 folded it
@@ -538,6 +549,11 @@ int x2v_gemm_mxfp4_variant(const void* a, int64_t lda, const void* sa, const voi
 /* Timestep sinusoid: y[n, dim] bf16 = [cos(t*f_j) | sin(t*f_j)], f_j = 10000^(-j/(dim/2)) computed in
  * float64 then rounded — replaces sinusoidal_embedding_1d (wan/infer/utils.py:161-172).  t: int64 [n]. */
 int x2v_sinusoid_embed_bf16(const int64_t* t, void* y, int n, int dim, void* stream);
+
+/* The same for fractional timesteps, t: float64 [n] — the step-distill scheduler's timesteps are sigma * 1000 in fp32 (999.87 for step 999 at
+ * shift 8) and sinusoidal_embedding_1d takes them as they are (`position.type(torch.float64)`, utils.py:163).  For integral t the bits of
+ * x2v_sinusoid_embed_bf16. */
+int x2v_sinusoid_embed_f64_bf16(const double* t, void* y, int n, int dim, void* stream);
 
 /* One denoise step's sampler update on the fp32 latent tensor as a single elementwise kernel — replaces the CFG combine
  * `noise_pred = uncond + guide * (cond - uncond)` (models/networks/wan/model.py:218) followed by WanScheduler.step_post

@@ -354,6 +354,19 @@ __global__ void sinusoid_kernel(const int64_t* __restrict__ t, unsigned short* _
   }
 }
 
+// The same for fractional timesteps (float64 positions): the step-distill scheduler's timesteps are sigma * 1000 in fp32 (999.87 for step 999 at
+// shift 8), and the reference embeds them as they are (utils.py:163 `position.type(torch.float64)`).
+__global__ void sinusoid_f64_kernel(const double* __restrict__ t, unsigned short* __restrict__ y, int n, int dim) {
+  const int half = dim / 2;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * half; i += gridDim.x * blockDim.x) {
+    const int r = i / half, j = i % half;
+    const double f = pow(10000.0, -((double)j / (double)half));
+    const double a = t[r] * f;
+    y[(int64_t)r * dim + j] = f2bf((float)cos(a));
+    y[(int64_t)r * dim + half + j] = f2bf((float)sin(a));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // HunyuanVideo q/k path: per-head RMSNorm over d = 128 followed (for the first `l_rope` tokens = the image
 // tokens) by the real-valued RoPE  x*cos + rotate_half(x)*sin  with bf16 cos/sin tables [l_rope, 128] —
@@ -623,6 +636,15 @@ extern "C" __attribute__((visibility("default"))) int x2v_sinusoid_embed_bf16(co
   const int total = n * (dim / 2);
   hipLaunchKernelGGL(sinusoid_kernel, dim3((total + 127) / 128), dim3(128), 0, (hipStream_t)stream, t, (unsigned short*)y, n, dim);
   X2V_LAUNCH_CHECK("sinusoid launch");
+  return X2V_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int x2v_sinusoid_embed_f64_bf16(const double* t, void* y, int n, int dim, void* stream) {
+  X2V_REQUIRE(t && y, X2V_E_ARG, "sinusoid_f64: null pointer");
+  X2V_REQUIRE(n > 0 && dim > 0 && dim % 2 == 0, X2V_E_SHAPE, "sinusoid_f64: n=%d dim=%d", n, dim);
+  const int total = n * (dim / 2);
+  hipLaunchKernelGGL(sinusoid_f64_kernel, dim3((total + 127) / 128), dim3(128), 0, (hipStream_t)stream, t, (unsigned short*)y, n, dim);
+  X2V_LAUNCH_CHECK("sinusoid_f64 launch");
   return X2V_OK;
 }
 

@@ -52,6 +52,7 @@ PROTOTYPES = {
     "x2v_gemm_kernel_choice": [_i64, _i32, _i32, _i64, _i64, _i32],
     "x2v_attn_fwd_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _c_void_p],
     "x2v_transpose_heads_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p],
+    "x2v_transpose_heads_append_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_vt_batched": [_c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_vt_launch_plan": [_i64, _i64, _i32, _i32, _i32],
     "x2v_mfma_probe_bf16": [_i32, ctypes.POINTER(_f32), _c_void_p],
@@ -94,6 +95,7 @@ PROTOTYPES = {
                            _c_void_p],
     "x2v_distill_step_f32": [_c_void_p, _c_void_p, _f32, _c_void_p, _i32, _c_void_p, _f32, _f32, _f32, _c_void_p, _c_void_p, _i64, _c_void_p],
     "x2v_sinusoid_embed_bf16": [_c_void_p, _c_void_p, _i32, _i32, _c_void_p],
+    "x2v_sinusoid_embed_f64_bf16": [_c_void_p, _c_void_p, _i32, _i32, _c_void_p],
     "x2v_causal_conv3d_f32": [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_vae_conv_f32": [_c_void_p, _i64, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_vae_prep_f32": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i64, _i64, _c_void_p],
@@ -567,6 +569,55 @@ def attention(q, k, v, num_heads, head_dim=128, scale=0.0, out=None, variant=0, 
     _check(
         _lib.x2v_attn_fwd_bf16_variant(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(v2), v2.stride(0), _p(out2), out2.stride(0), Sq, Sk, num_heads, head_dim, scale, variant, _stream()),
         "attn_fwd",
+    )
+    return out2
+
+
+def _vt_cache(vt, who, num_heads=None):  # a V^T cache [H, tiles, 128, 64]: more tiles than the keys in use, appended to in place
+    if vt.dim() != 4 or vt.dtype != torch.bfloat16 or not vt.is_cuda or not vt.is_contiguous() or tuple(vt.shape[2:]) != (128, 64) or (num_heads is not None and vt.shape[0] != num_heads):
+        raise X2VError(f"{who}: the V^T cache must be a contiguous bf16 [H, tiles, 128, 64] tensor on the GPU, got {vt.dtype} {tuple(vt.shape)} on {vt.device}")
+    return vt
+
+
+def transpose_heads_append(v, vt, key0):
+    """x2v_transpose_heads_append_bf16: v [S, H*128] (any token stride) into the key columns [key0, key0 + S) of the V^T cache vt [H, tiles, 128, 64],
+    a bit copy that changes no other byte of vt (key0 and S need not be multiples of the 64-key tile, nor even).  Appends to one cache and the
+    attention over it are ordered on one stream.  Returns vt."""
+    v2 = _row2d(_bf16(v, "v"), "v")
+    vt = _vt_cache(vt, "transpose_heads_append")
+    H, S = vt.shape[0], v2.shape[0]
+    if v2.shape[1] < H * 128:
+        raise X2VError(f"transpose_heads_append: v {tuple(v2.shape)} does not hold {H} heads of 128")
+    init()
+    if S == 0:  # torch hands out a null data_ptr for an empty tensor; the C entry would call it a null pointer
+        if key0 < 0 or key0 > vt.shape[1] * 64:
+            raise X2VError(f"transpose_heads_append: key0={key0} outside the cache's {vt.shape[1] * 64} keys")
+        return vt
+    _check(_lib.x2v_transpose_heads_append_bf16(_p(v2), v2.stride(0), _p(vt), vt.shape[1] * 64, key0, S, H, _stream()), "transpose_heads_append")
+    return vt
+
+
+def attention_cached(q, k_cache, vt_cache, kv_end, num_heads, out=None, prescaled=False, scale=0.0):
+    """Attention of q [Sq, H*128] over the first kv_end keys of a KV cache: k_cache [capacity, H*128] row-major, vt_cache [H, tiles, 128, 64] as
+    transpose_heads_append fills it (tiles * 64 >= kv_end) — x2v_attn_fwd_bf16_vt on k_cache[:kv_end] with ldvt = tiles * 64, one-walk or
+    short-walk form by the shape as for lib.attention; flags: X2V_ATTN_VT_PRESCALED when `prescaled`, nothing else.
+    The kernel gives a key >= kv_end of the last tile probability 0 and still multiplies it with the V^T entry there, so the cache's bytes at keys
+    >= kv_end must be FINITE (0 * inf = nan): causvid.KVCache zero-fills its tensors once and nothing but transpose_heads_append writes them."""
+    q2, k2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k_cache, "k_cache"), "k_cache")
+    vt = _vt_cache(vt_cache, "attention_cached", num_heads)
+    Sq, W = q2.shape[0], num_heads * 128
+    if min(q2.shape[1], k2.shape[1]) < W:
+        raise X2VError(f"attention_cached: q {tuple(q2.shape)} k_cache {tuple(k2.shape)} do not describe {num_heads} heads of 128")
+    if kv_end < 1 or kv_end > k2.shape[0] or kv_end > vt.shape[1] * 64:
+        raise X2VError(f"attention_cached: kv_end={kv_end} outside the cache (k_cache holds {k2.shape[0]} keys, vt_cache {vt.shape[1] * 64})")
+    out2 = _attn_out(out, "attention_cached", Sq, W, q.device)
+    init()
+    if Sq == 0:
+        return out2
+    _check(
+        _lib.x2v_attn_fwd_bf16_vt(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(vt), vt.shape[1] * 64, _p(out2), out2.stride(0), Sq, kv_end, num_heads, 128, scale,
+                                  1 if prescaled else 0, _stream()),
+        "attention_cached",
     )
     return out2
 
@@ -1116,6 +1167,14 @@ def gemm_int8_blocked(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, out=None,
 
 
 def sinusoid_embed(t, dim):
+    """Timestep sinusoid [n, dim] bf16.  Integer timesteps (the UniPC scheduler's) go to x2v_sinusoid_embed_bf16; floating-point ones (the step-distill
+    scheduler's sigma * 1000, fractional) keep their fraction, as in the reference: x2v_sinusoid_embed_f64_bf16."""
+    if t.is_floating_point():
+        t = t.reshape(-1).to(torch.float64)
+        out = torch.empty((t.numel(), dim), dtype=torch.bfloat16, device=t.device)
+        init()
+        _check(_lib.x2v_sinusoid_embed_f64_bf16(_p(t), _p(out), t.numel(), dim, _stream()), "sinusoid_embed")
+        return out
     t = t.reshape(-1).to(torch.int64)
     out = torch.empty((t.numel(), dim), dtype=torch.bfloat16, device=t.device)
     init()

@@ -206,7 +206,12 @@ class WanPreInfer:
         seq_len = sch.seq_len
 
         if self.task == "i2v":  # pre_infer.py:44-55: noise latents + [first-frame mask | conditioning latents] along the channel axis (36 channels)
-            latents = torch.cat([latents, inputs["image_encoder_output"]["vae_encode_out"].to(latents.dtype)], dim=0)
+            image_encoder = inputs["image_encoder_output"]["vae_encode_out"]
+            if kv_end > 0:  # CausVid (:47-52): the conditioning frames of the block whose tokens are [kv_start, kv_end)
+                frame_seq_length = (image_encoder.size(2) // 2) * (image_encoder.size(3) // 2)
+                if kv_end - kv_start >= frame_seq_length:
+                    image_encoder = image_encoder[:, kv_start // frame_seq_length : kv_end // frame_seq_length]
+            latents = torch.cat([latents, image_encoder.to(latents.dtype)], dim=0)
         x = weights.patch_embedding.apply(latents.unsqueeze(0))  # [1, D, T, H/2, W/2] (pre_infer.py:57)
         grid_sizes = torch.tensor([list(x.shape[2:])], dtype=torch.long)
         x = x.flatten(2).transpose(1, 2).squeeze(0)  # :59 — a view chain back onto the GEMM's contiguous [S, D]

@@ -5,6 +5,7 @@ Synthetic weights and inputs of the named shape (the text encoder's output is an
     python tools/e2e.py [--workload wan14b_720px81f] [--steps 50] [--fp8|--int8|--mxfp8|--mxfp6|--mxfp4] [--distill] [--teacache T]
     python tools/e2e.py --i2v --image PATH | --encode   (image → CLIP tower + VAE encode → loop → decode; --encode: a seeded synthetic 720p image;
                                                          --clip-ckpt PATH: the CLIP checkpoint instead of seeded synthetic tower weights)
+    python tools/e2e.py --causvid --workload wan1.3b_480px81f   (the autoregressive Wan: 7 blocks of 3 latent frames, 9 steps each, over a KV cache; then the decode)
     python tools/e2e.py --t5   (context / context_null from seeded token ids through the HIP umT5-XXL encoder, seeded weights, timed as t5_encode_s)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/e2e.py --gpus N ...
         (N GPUs of one node: Ulysses sequence parallel denoise loop over RCCL + the halo-split `decode_dist` VAE decode)"""
@@ -20,8 +21,75 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightx2v_amd import lib, scheduler, synth, vae, wan  # noqa: E402
 
 
+CAUSVID_STEP_LIST = [999, 934, 862, 756, 603, 410, 250, 140, 74]  # configs/causvid/wan_t2v_causvid.json of the reference
+
+
+def causvid_main(a):
+    """--causvid: the reference's `wan2.1_causvid` run (configs/causvid/wan_t2v_causvid.json: 21 latent frames in 7 blocks of 3, 9 distilled steps per
+    block, no CFG, shift 8) on the workload's latent grid, then the VAE decode of the assembled latents.  One JSON line; `block_s` is the wall clock of
+    each autoregressive block (9 steps), fenced by a device synchronise."""
+    from lightx2v_amd import causvid
+
+    if a.gpus != 1:
+        raise SystemExit("--causvid: single GPU (the causal driver has no parallel attention, as the reference)")
+    torch.cuda.set_device(0)
+    lib.init(0)
+    wl = synth.WORKLOADS[a.workload]
+    dims = synth.WAN_DIMS[wl["model"]]
+    if dims.get("task") == "i2v":
+        raise SystemExit("--causvid: a t2v workload (the i2v path is covered by the parity tests)")
+    _, T, h, w = wl["target_shape"]
+    nfpb = 3
+    blocks = a.causvid_blocks or T // nfpb
+    steps = CAUSVID_STEP_LIST[: a.steps] if a.steps else CAUSVID_STEP_LIST
+    ts = (16, nfpb, h, w)
+    fsl = (h // 2) * (w // 2)
+    extra = {}
+    if a.fp8:
+        extra["mm_config"] = {"mm_type": "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip", "weight_auto_quant": True}
+    if a.int8:
+        extra["mm_config"] = {"mm_type": "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip", "weight_auto_quant": True}
+    _, _, wd, _, inputs = synth.workload_setup(a.workload, seed=0, device="cuda")
+    cfg = wan.default_config(dims, target_shape=ts, target_video_length=wl["frames"], infer_steps=len(steps), enable_cfg=False, sample_shift=8.0, denoising_step_list=steps,
+                             num_frames=T, num_frame_per_block=nfpb, num_blocks=blocks, frame_seq_length=fsl, num_fragments=1, **extra)
+    model = causvid.WanCausVidModel(cfg, wd)
+    del wd
+    sch = scheduler.WanStepDistillScheduler(cfg, device="cuda")
+    model.set_scheduler(sch)
+    decoder = vae.WanVAE(synth.synth_wan_vae_weights(dim=96, seed=0), dim=96, conv16=(True if a.vae16 else False if a.vae32 else "split"), use_tiling=a.tiling_vae)
+    # warm-up outside the clock: one block (allocator pools, lazy tables, the cross-attention K / V) and a short decode
+    warm = dict(cfg, num_blocks=1)
+    causvid.run_causvid(model, sch, inputs, warm)
+    decoder.decode(torch.zeros(16, 2, h, w, device="cuda"))
+    torch.cuda.synchronize()
+    marks = []
+
+    def after_step(b, s):
+        if s == len(steps) - 1:
+            torch.cuda.synchronize()
+            marks.append(time.perf_counter())
+
+    t0 = time.perf_counter()
+    latents = causvid.run_causvid(model, sch, inputs, cfg, step_callback=after_step)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    video = decoder.decode(latents[:, : blocks * nfpb].float())
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    assert torch.isfinite(latents.float()).all() and torch.isfinite(video).all()
+    block_s = [b - a_ for a_, b in zip([t0] + marks[:-1], marks)]  # block 0 includes the cache allocation
+    frames = 1 + 4 * (blocks * nfpb - 1)
+    print(json.dumps({"workload": a.workload, "mode": "causvid", "latent_frames": blocks * nfpb, "output_latents_shape": list(latents.shape), "blocks": blocks, "frames_per_block": nfpb,
+                      "steps_per_block": len(steps), "tokens_per_block": nfpb * fsl, "kv_capacity": T * fsl, "cfg": False,
+                      "gemm_dtype": "int8" if a.int8 else "fp8" if a.fp8 else "bf16", "denoise_s": t1 - t0, "block_s": block_s, "ms_per_step_by_block": [x * 1e3 / len(steps) for x in block_s],
+                      "vae_decode_s": t2 - t1, "total_s": t2 - t0, "frames": frames, "video_shape": list(video.shape), "fps_with_vae": frames / (t2 - t0),
+                      "hbm_gb_peak": torch.cuda.max_memory_allocated() / 1e9, "data": "synthetic weights / latents / text embeddings"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--causvid", action="store_true", help="the autoregressive Wan (wan2.1_causvid): blocks of 3 latent frames, 9 distilled steps each, over a per-layer KV cache; use a 21-latent-frame t2v workload such as wan1.3b_480px81f; single GPU")
+    ap.add_argument("--causvid-blocks", type=int, default=0, help="--causvid: number of blocks (default: all the workload's latent frames / 3)")
     ap.add_argument("--workload", default="wan14b_720px81f")
     ap.add_argument("--steps", type=int, default=0, help="0 = the workload's own schedule length (50; 40 for the i2v benchmark workloads)")
     ap.add_argument("--i2v", action="store_true", help="--workload wan14b_i2v_720px81f: the reference's published benchmark (I2V-14B, 40 steps, CFG 5, shift 5; configs/bench/lightx2v_2.json)")
@@ -46,6 +114,8 @@ def main():
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
     ap.add_argument("--t5", action="store_true", help="build context / context_null from seeded token ids (77- and 126-token prompts) with the HIP umT5-XXL encoder (seeded weights), timed as t5_encode_s")
     a = ap.parse_args()
+    if a.causvid:
+        return causvid_main(a)
     from lightx2v_amd import launch
 
     world, rank, local_rank = launch.ranks(__file__, a.gpus)  # bare `--gpus N`: re-runs itself as N ranks under torch.distributed.run
