@@ -438,6 +438,13 @@ int x2v_gemm_int8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_k
  * row-major y.  Negative = X2V_E_SHAPE.  Host-only. */
 int x2v_gemm_int8_kernel_choice(int64_t M, int N, int K, int64_t ldx, int64_t ldw);
 
+/* Which body variant 0 of the MX GEMMs launches for this shape without a fused epilogue: 1 = the 128x128 kernel, 2 = the 256x256 ping-pong kernel.
+ * format: 1 = x2v_gemm_mxfp8, 2 = x2v_gemm_mxfp6_mxfp8, 3 = x2v_gemm_mxfp4 (anything else: X2V_E_ARG); lda, ldb in bytes, as there.  The rule: at
+ * least 192 tiles of 256x256, both leading dimensions below 2^24 bytes, and at least 8 (formats 1, 2: K / 128) or 6 (format 3: K / 256) K-tiles of
+ * 128 bytes per row of a.  Negative = X2V_E_SHAPE (K not a multiple of the format's K-tile, N % 8, a leading dimension below the row's bytes).
+ * Host-only. */
+int x2v_gemm_mx_kernel_choice(int format, int64_t M, int N, int K, int64_t lda, int64_t ldb);
+
 /* MXFP8 (OCP microscaling) activation / weight quantisation — replaces lightx2v_kernel.gemm.scaled_fp8_quant
  * (lightx2v_kernel/python/lightx2v_kernel/gemm.py:73-83, csrc/gemm/mxfp8_quant_kernels_sm120.cu:139-196): per 32 consecutive K
  * elements one e8m0 scale = the smallest power of two >= max|x|/448, elements = e4m3fn_rne(x / scale).
@@ -454,16 +461,22 @@ int x2v_quant_mxfp8_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void*
  * 32-wide k block — replaces lightx2v_kernel.gemm.cutlass_scaled_mxfp8_mm (gemm.py:93-97,
  * csrc/gemm/mxfp8_scaled_mm_kernels_sm120.cu:60-66,150-160).  sa [K/128][M][4], sb [K/128][N][4] as written by
  * x2v_quant_mxfp8_bf16; alpha: device pointer to one fp32 (NULL = 1), bias bf16 [N] or NULL.
- * Runs on v_mfma_scale_f32_32x32x64_f8f6f4 with the block scales applied by the matrix instruction.  K % 128 == 0, N % 8 == 0. */
+ * Runs on v_mfma_scale_f32_32x32x64_f8f6f4 with the block scales applied by the matrix instruction.
+ * K % 128 == 0, N % 8 == 0; a, b, y: rows 16-byte aligned (lda % 16, ldb % 16, both >= K, ldy % 8); scale tables 4-byte, bias 8-byte aligned.
+ * Anything else: X2V_E_SHAPE / X2V_E_ALIGN / X2V_E_ARG before any HIP call.
+ * Two bodies, chosen by x2v_gemm_mx_kernel_choice's rule: the MX mode of the 128x128-tile kernel and of the 256x256-tile ping-pong kernel (shapes that
+ * fill the chip and every fused epilogue; it addresses a tile with 32-bit offsets: lda, ldb < 2^24 bytes, else X2V_E_SHAPE). */
 int x2v_gemm_mxfp8(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
                    int64_t ldy, int64_t M, int N, int K, void* stream);
 
-/* x2v_gemm_mxfp8 with the fused epilogues of x2v_gemm_bf16 / x2v_gemm_fp8 (X2V_EPI_*; y = epi(alpha * a.b^T + bias)): what the fused
- * block drivers call for a linear layer held in MXFP8 (operator class MMWeightMxfp8Hip). */
+/* x2v_gemm_mxfp8 with the fused epilogues of x2v_gemm_bf16 / x2v_gemm_fp8 (X2V_EPI_*; y = epi(alpha * a.b^T + bias); X2V_EPI_RESIDUAL without
+ * resid: X2V_E_ARG): what the fused block drivers call for a linear layer held in MXFP8 (operator class MMWeightMxfp8Hip).  Every fused epilogue
+ * runs the 256x256 body: lda, ldb < 2^24 bytes, else X2V_E_SHAPE. */
 int x2v_gemm_mxfp8_epi(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
                        int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
 
-/* Same with a kernel selector: 0 = automatic (as x2v_gemm_mxfp8), 1 = 128x128-tile kernel, 2 = 256x256-tile ping-pong kernel. */
+/* Same with a kernel selector: 0 = automatic (as x2v_gemm_mxfp8), 1 = 128x128-tile kernel, 2 = 256x256-tile ping-pong kernel (lda, ldb < 2^24
+ * bytes, else X2V_E_SHAPE); anything else: X2V_E_ARG. */
 int x2v_gemm_mxfp8_variant(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
                            void* y, int64_t ldy, int64_t M, int N, int K, int variant, void* stream);
 

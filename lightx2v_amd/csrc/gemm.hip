@@ -399,55 +399,31 @@ static int launch_gemm(const void* x, int64_t ldx_bytes, const void* w, int64_t 
   return X2V_OK;
 }
 
-// MXFP8 (mx.hip), shapes below the 256x256 kernel's: e4m3 operands with e8m0 block-scale tables [K/128][rows][4]; alpha = device pointer or null.  No fused
+// The MX modes (mx.hip: MXFP8, MXFP6 weights x MXFP8 activations, MXFP4 x MXFP4 — MxFormat::mxm), shapes below the 256x256 kernel's.  No fused
 // epilogue (those go to gemm256_mx_dispatch).  Arguments validated by the caller.
-namespace x2v {
-int gemm128_mx_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
-                        int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
+template <int MXM>
+static int launch_gemm128_mx(const char* who, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                             const float* alpha, void* y, int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
   const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
   {
-    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 1>, G_LDS_BYTES, "gemm_mxfp8 attr");
+    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, MXM>, G_LDS_BYTES, who);
     if (rc != X2V_OK) return rc;
   }
-  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 1>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
+  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, MXM>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
                      (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
                      (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
-  X2V_LAUNCH_CHECK("gemm_mxfp8 launch");
+  X2V_LAUNCH_CHECK(who);
   return X2V_OK;
 }
 
-// MXFP6 weights x MXFP8 activations (mx.hip), shapes below the 256x256 kernel's: b = packed e3m2 codes [N, 3K/4], ldb in bytes.  No fused epilogue
-// (those go to gemm256_mx6_dispatch).  Arguments validated by the caller.
-int gemm128_mx6_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
-                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
-  const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
-  {
-    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 2>, G_LDS_BYTES, "gemm_mxfp6_mxfp8 attr");
-    if (rc != X2V_OK) return rc;
+int x2v::gemm128_mx_dispatch(const MxFormat& f, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                             const float* alpha, void* y, int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
+  switch (f.mxm) {
+    case 1: return launch_gemm128_mx<1>(f.gemm_name, a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, nk, st);
+    case 2: return launch_gemm128_mx<2>(f.gemm_name, a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, nk, st);
+    default: return launch_gemm128_mx<3>(f.gemm_name, a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, nk, st);
   }
-  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 2>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
-                     (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
-                     (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
-  X2V_LAUNCH_CHECK("gemm_mxfp6_mxfp8 launch");
-  return X2V_OK;
 }
-
-// MXFP4 x MXFP4 (mx.hip), shapes below the 256x256 kernel's: a, b = packed e2m1 codes [rows, K/2], lda / ldb in bytes, nk = K / 256.  No fused
-// epilogue (those go to gemm256_mx4_dispatch).  Arguments validated by the caller.
-int gemm128_mx4_dispatch(const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha, void* y,
-                         int64_t ldy, int64_t M, int N, int nk, hipStream_t st) {
-  const int ntm = (int)((M + GB_M - 1) / GB_M), ntn = (N + GB_N - 1) / GB_N;
-  {
-    int rc = ensure_dynamic_lds((const void*)gemm_kernel<true, X2V_EPI_NONE, false, 3>, G_LDS_BYTES, "gemm_mxfp4 attr");
-    if (rc != X2V_OK) return rc;
-  }
-  hipLaunchKernelGGL((gemm_kernel<true, X2V_EPI_NONE, false, 3>), dim3((unsigned)ntm * (unsigned)ntn), dim3(256), G_LDS_BYTES, st, (const char*)a, lda,
-                     (const char*)b, ldb, (const unsigned short*)bias, (unsigned short*)y, ldy, M, N, nk, (const unsigned short*)nullptr, (int64_t)0,
-                     (const unsigned short*)nullptr, alpha, (const float*)nullptr, ntm, ntn, GemmBlocking(), (const unsigned*)sa, (const unsigned*)sb);
-  X2V_LAUNCH_CHECK("gemm_mxfp4 launch");
-  return X2V_OK;
-}
-}  // namespace x2v
 
 // The shape rule of variant 0 (one place: the dispatcher and x2v_gemm_kernel_choice both ask it): the 256^2 kernel wants at least
 // ~one full round of tiles (256 CUs), a K loop longer than its pipeline, and 32-bit buffer offsets over a 256-row tile.

@@ -501,25 +501,18 @@ int gemm256_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, i
     return launch_gemm256<FP8, decltype(epi)::value>(x, ldxb, w, ldwb, bias, y, ldy, M, N, nk, r, lr, g, sx, sw, gm_tiles, st, nullptr, nullptr, gb);
   });
 }
-// MXFP8 (mx.hip): e4m3 operands with e8m0 block-scale tables [K/128][rows][4]; alpha = device pointer or null.  Arguments validated by the caller.
-int gemm256_mx_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
-                        void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
-  return with_epilogue("gemm_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
-    return launch_gemm256<true, decltype(epi)::value, 1>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
-  });
-}
-// MXFP6 weights x MXFP8 activations (mx.hip): b = packed e3m2 codes [N, 3K/4], ldb in bytes.  Arguments validated by the caller.
-int gemm256_mx6_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
-                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
-  return with_epilogue("gemm_mxfp6_mxfp8", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
-    return launch_gemm256<true, decltype(epi)::value, 2>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
-  });
-}
-// MXFP4 x MXFP4 (mx.hip): a, b = packed e2m1 codes [rows, K/2], lda / ldb in bytes, nk = K / 256.  Arguments validated by the caller.
-int gemm256_mx4_dispatch(int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias, const float* alpha,
-                         void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
-  return with_epilogue("gemm_mxfp4", epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
-    return launch_gemm256<true, decltype(epi)::value, 3>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+// The MX modes (mx.hip; MxFormat::mxm = the kernel's MXM).  Arguments validated by the caller.
+int gemm256_mx_dispatch(const MxFormat& f, int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                        const float* alpha, void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st) {
+  return with_epilogue(f.gemm_name, epilogue, resid, ldr, gate, [&](auto epi, const void* r, int64_t lr, const void* g) {
+    auto launch = [&](auto mxm) {
+      return launch_gemm256<true, decltype(epi)::value, decltype(mxm)::value>(a, lda, b, ldb, bias, y, ldy, M, N, nk, r, lr, g, alpha, nullptr, 4, st, sa, sb);
+    };
+    switch (f.mxm) {
+      case 1: return launch(std::integral_constant<int, 1>{});
+      case 2: return launch(std::integral_constant<int, 2>{});
+      default: return launch(std::integral_constant<int, 3>{});
+    }
   });
 }
 

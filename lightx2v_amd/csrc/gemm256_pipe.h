@@ -7,6 +7,7 @@
 #pragma once
 #include <type_traits>
 
+#include "mx_format.h"
 #include "x2v_common.h"
 
 namespace x2v {
@@ -29,6 +30,13 @@ int gemm256c8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w,
 // gemm256c8.hip, I8 form: the same kernel for the w8a8 int8 operator (v_mfma_i32_32x32x32_i8, int32 accumulators)
 int gemm256ci8_dispatch(int epilogue, const void* x, int64_t ldxb, const void* w, int64_t ldwb, const void* bias, void* y, int64_t ldy, int64_t M, int N, int nk,
                         const void* resid, int64_t ldr, const void* gate, const float* sx, const float* sw, int gm_tiles, hipStream_t st, GemmBlocking gb);
+// The MX modes (mx.hip; f.mxm picks the kernels' MXM): a, b = rows of f.bits_a / f.bits_b-bit codes, lda / ldb in bytes, sa / sb = e8m0 block-scale
+// tables [K/128][rows][4], alpha = device pointer or null, nk = K / f.k_tile.  gemm.hip: the 128x128-tile kernel (small shapes, no fused epilogue);
+// gemm256.hip: the ping-pong kernel (shapes that fill the chip, and every fused epilogue)
+int gemm128_mx_dispatch(const MxFormat& f, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                        const float* alpha, void* y, int64_t ldy, int64_t M, int N, int nk, hipStream_t st);
+int gemm256_mx_dispatch(const MxFormat& f, int epilogue, const void* a, int64_t lda, const void* sa, const void* b, int64_t ldb, const void* sb, const void* bias,
+                        const float* alpha, void* y, int64_t ldy, int64_t M, int N, int nk, const void* resid, int64_t ldr, const void* gate, hipStream_t st);
 
 // ---- host: run-time epilogue -> template argument.  f(integral_constant<int, EPI>, resid, ldr, gate); the non-residual epilogues get no residual.
 template <class F>

@@ -91,6 +91,7 @@ PROTOTYPES = {
     "x2v_gemm_int8_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64,
                               _c_void_p, _c_void_p],
     "x2v_gemm_int8_kernel_choice": [_i64, _i32, _i32, _i64, _i64],
+    "x2v_gemm_mx_kernel_choice": [_i32, _i64, _i32, _i32, _i64, _i64],
     "x2v_unipc_step_f32": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, ctypes.POINTER(_f32), _i32, _i32, _i64,
                            _c_void_p],
     "x2v_distill_step_f32": [_c_void_p, _c_void_p, _f32, _c_void_p, _i32, _c_void_p, _f32, _f32, _f32, _c_void_p, _c_void_p, _i64, _c_void_p],
@@ -934,46 +935,36 @@ def layernorm_quant_int8(x, weight=None, bias=None, scale=None, shift=None, eps=
     return _layernorm_quant8(x, weight, bias, scale, shift, eps, _INT8)
 
 
-def quant_mxfp8(x):
-    """bf16 [M, K] → (e4m3 [M, K], e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp8_bf16.
-    `mx_scales_rowmajor` turns the scale tensor into the logical [M, K/32] table."""
+def _quant_mx(bits, x):
+    """quant_mxfp8 / quant_mxfp6 / quant_mxfp4: a row of K elements of `bits` bits is K * bits / 8 bytes (e4m3 bytes as torch's dtype, the packed codes as uint8)."""
+    tag = f"quant_mxfp{bits}"
     x2 = _row2d(_bf16(x, "x"), "x")
     M, K = x2.shape
-    q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    q = torch.empty((M, K // 8 * bits), dtype=torch.float8_e4m3fn if bits == 8 else torch.uint8, device=x.device)
     sc = torch.empty((max(K // 128, 1), M, 4), dtype=torch.uint8, device=x.device)
     init()
     if M == 0:
         return q, sc
-    _check(_lib.x2v_quant_mxfp8_bf16(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), "quant_mxfp8")
+    _check(getattr(_lib, f"x2v_{tag}_bf16")(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), tag)
     return q, sc
+
+
+def quant_mxfp8(x):
+    """bf16 [M, K] → (e4m3 [M, K], e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp8_bf16.
+    `mx_scales_rowmajor` turns the scale tensor into the logical [M, K/32] table."""
+    return _quant_mx(8, x)
 
 
 def quant_mxfp6(x):
     """bf16 [M, K] → (uint8 [M, 3K/4]: e3m2 codes, the dense little-endian 6-bit string, code j of a row at bits 6j .. 6j+5 of its bytes;
     e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp6_bf16."""
-    x2 = _row2d(_bf16(x, "x"), "x")
-    M, K = x2.shape
-    q = torch.empty((M, K // 4 * 3), dtype=torch.uint8, device=x.device)
-    sc = torch.empty((max(K // 128, 1), M, 4), dtype=torch.uint8, device=x.device)
-    init()
-    if M == 0:
-        return q, sc
-    _check(_lib.x2v_quant_mxfp6_bf16(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), "quant_mxfp6")
-    return q, sc
+    return _quant_mx(6, x)
 
 
 def quant_mxfp4(x):
     """bf16 [M, K] → (uint8 [M, K/2]: e2m1 codes, two per byte, the dense little-endian nibble string, code j of a row at bits 4j .. 4j+3 of its
     bytes; e8m0 scale bytes [K/128, M, 4]) — see include/x2v.h::x2v_quant_mxfp4_bf16."""
-    x2 = _row2d(_bf16(x, "x"), "x")
-    M, K = x2.shape
-    q = torch.empty((M, K // 2), dtype=torch.uint8, device=x.device)
-    sc = torch.empty((max(K // 128, 1), M, 4), dtype=torch.uint8, device=x.device)
-    init()
-    if M == 0:
-        return q, sc
-    _check(_lib.x2v_quant_mxfp4_bf16(_p(x2), x2.stride(0), _p(q), q.stride(0), _p(sc), M, K, _stream()), "quant_mxfp4")
-    return q, sc
+    return _quant_mx(4, x)
 
 
 def mx_scales_rowmajor(sc):
@@ -1051,6 +1042,16 @@ def gemm_mxfp4(a, sa, b, sb, alpha=None, bias=None, out=None, variant=0, epilogu
     """gemm_mxfp8 with both operands the packed e2m1 codes uint8 [rows, K/2] and scales of quant_mxfp4 (K % 256 == 0).  variant as gemm_mxfp8 — see
     include/x2v.h::x2v_gemm_mxfp4."""
     return _gemm_mx("mxfp4", 4, 4, a, sa, b, sb, alpha, bias, out, variant, epilogue, resid, gate)
+
+
+def gemm_mx_kernel_choice(bits_a, bits_b, M, N, K, lda=None, ldb=None):
+    """The body variant 0 of gemm_mxfp8 (bits 8, 8), gemm_mxfp6_mxfp8 (8, 6) or gemm_mxfp4 (4, 4) launches for this shape without a fused epilogue:
+    1 = the 128x128 kernel, 2 = the 256x256 ping-pong kernel (x2v_gemm_mx_kernel_choice; host arithmetic).  lda, ldb in bytes, default: dense rows."""
+    fmt = {(8, 8): 1, (8, 6): 2, (4, 4): 3}.get((bits_a, bits_b), 0)
+    rc = _lib.x2v_gemm_mx_kernel_choice(fmt, M, N, K, K * bits_a // 8 if lda is None else lda, K * bits_b // 8 if ldb is None else ldb)
+    if rc < 0:
+        raise X2VError(f"gemm_mx_kernel_choice: bad format or shape ({bits_a}, {bits_b}) M={M} N={N} K={K}")
+    return rc
 
 
 def _gemm8(kind, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period):

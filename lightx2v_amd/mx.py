@@ -20,15 +20,26 @@ from . import lib
 _E8M0 = getattr(torch, "float8_e8m0fnu", None)
 
 
+def _e8m0(scales):
+    """The scale bytes as torch's e8m0 dtype, where this torch has it."""
+    return scales.view(_E8M0) if _E8M0 is not None else scales
+
+
+def _bytes(scales):
+    return scales.view(torch.uint8) if scales.dtype != torch.uint8 else scales
+
+
+def _mm(gemm, mat_a, mat_b, scales_a, scales_b, alpha, bias):
+    return gemm(mat_a, _bytes(scales_a), mat_b, _bytes(scales_b), alpha=alpha, bias=None if bias is None else bias.reshape(-1))
+
+
 def scaled_fp8_quant(input: torch.Tensor):
     q, sc = lib.quant_mxfp8(input)
-    return q.view(torch.uint8), (sc.view(_E8M0) if _E8M0 is not None else sc)
+    return q.view(torch.uint8), _e8m0(sc)
 
 
 def cutlass_scaled_mxfp8_mm(mat_a, mat_b, scales_a, scales_b, alpha, bias=None):
-    sa = scales_a.view(torch.uint8) if scales_a.dtype != torch.uint8 else scales_a
-    sb = scales_b.view(torch.uint8) if scales_b.dtype != torch.uint8 else scales_b
-    return lib.gemm_mxfp8(mat_a, sa, mat_b, sb, alpha=alpha, bias=None if bias is None else bias.reshape(-1))
+    return _mm(lib.gemm_mxfp8, mat_a, mat_b, scales_a, scales_b, alpha, bias)
 
 
 scaled_mxfp8_mm = cutlass_scaled_mxfp8_mm  # the name without the CUDA library in it
@@ -42,13 +53,11 @@ scaled_mxfp8_mm = cutlass_scaled_mxfp8_mm  # the name without the CUDA library i
 #     y = cutlass_scaled_mxfp6_mxfp8_mm(a_q, w_q, a_s, w_s, alpha=alpha, bias=bias)
 def scaled_fp6_quant(input: torch.Tensor):
     q, sc = lib.quant_mxfp6(input)
-    return q, (sc.view(_E8M0) if _E8M0 is not None else sc)
+    return q, _e8m0(sc)
 
 
 def cutlass_scaled_mxfp6_mxfp8_mm(mat_a, mat_b, scales_a, scales_b, alpha, bias=None):
-    sa = scales_a.view(torch.uint8) if scales_a.dtype != torch.uint8 else scales_a
-    sb = scales_b.view(torch.uint8) if scales_b.dtype != torch.uint8 else scales_b
-    return lib.gemm_mxfp6_mxfp8(mat_a, sa, mat_b, sb, alpha=alpha, bias=None if bias is None else bias.reshape(-1))
+    return _mm(lib.gemm_mxfp6_mxfp8, mat_a, mat_b, scales_a, scales_b, alpha, bias)
 
 
 scaled_mxfp6_mxfp8_mm = cutlass_scaled_mxfp6_mxfp8_mm
@@ -65,10 +74,8 @@ scaled_mxfp6_mxfp8_mm = cutlass_scaled_mxfp6_mxfp8_mm
 #     y = scaled_mxfp4_mm(a_q, w_q, a_s, w_s, alpha=alpha, bias=bias)
 def scaled_mxfp4_quant(input: torch.Tensor):
     q, sc = lib.quant_mxfp4(input)
-    return q, (sc.view(_E8M0) if _E8M0 is not None else sc)
+    return q, _e8m0(sc)
 
 
 def scaled_mxfp4_mm(mat_a, mat_b, scales_a, scales_b, alpha, bias=None):
-    sa = scales_a.view(torch.uint8) if scales_a.dtype != torch.uint8 else scales_a
-    sb = scales_b.view(torch.uint8) if scales_b.dtype != torch.uint8 else scales_b
-    return lib.gemm_mxfp4(mat_a, sa, mat_b, sb, alpha=alpha, bias=None if bias is None else bias.reshape(-1))
+    return _mm(lib.gemm_mxfp4, mat_a, mat_b, scales_a, scales_b, alpha, bias)

@@ -215,11 +215,18 @@ class MMWeightMxfp8Hip(_Movable):
         self.config = {}
         self.weight = self.weight_scale = self.bias = None
 
+    # what the subclasses change: the weight's format and quantiser, whether a uint8 weight is the packed codes state_dict wrote (MXFP8's e4m3 bytes
+    # arrive as bf16 / fp16 / fp32 only), and the GEMM
+    _label, _quant_weight, _takes_packed = "MXFP8", staticmethod(lib.quant_mxfp8), False
+
     def load(self, weight_dict):
         w = weight_dict[self.weight_name]
         if not w.is_cuda:
-            raise lib.X2VError(f"{self.weight_name}: MXFP8 weights are quantised by the HIP kernel at load — tensor is on {w.device}")
-        self.weight, self.weight_scale = lib.quant_mxfp8(w.to(torch.bfloat16).contiguous())
+            raise lib.X2VError(f"{self.weight_name}: {self._label} weights are quantised by the HIP kernel at load — tensor is on {w.device}")
+        if self._takes_packed and w.dtype == torch.uint8:  # what state_dict wrote: the packed codes with their table
+            self.weight, self.weight_scale = w.contiguous(), weight_dict[self.weight_name + "_scale"].view(torch.uint8).contiguous()
+        else:
+            self.weight, self.weight_scale = self._quant_weight(w.to(torch.bfloat16).contiguous())
         self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
 
     def quantize_input(self, input_tensor):
@@ -250,16 +257,7 @@ class MMWeightMxfp6Hip(MMWeightMxfp8Hip):
     protocol: `quantize_input` stays the MXFP8 quantiser, so a fused driver's shared quantised activation serves both classes; the weight is
     uint8 [N, 3K/4] with the same e8m0 table [K/128, N, 4] under `<name>_scale`."""
 
-    def load(self, weight_dict):
-        w = weight_dict[self.weight_name]
-        if not w.is_cuda:
-            raise lib.X2VError(f"{self.weight_name}: MXFP6 weights are quantised by the HIP kernel at load — tensor is on {w.device}")
-        if w.dtype == torch.uint8:  # what state_dict wrote: the packed codes with their table
-            self.weight, self.weight_scale = w.contiguous(), weight_dict[self.weight_name + "_scale"].view(torch.uint8).contiguous()
-        else:
-            self.weight, self.weight_scale = lib.quant_mxfp6(w.to(torch.bfloat16).contiguous())
-        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
-
+    _label, _quant_weight, _takes_packed = "MXFP6", staticmethod(lib.quant_mxfp6), True
     _gemm = staticmethod(lib.gemm_mxfp6_mxfp8)
 
 
@@ -270,15 +268,7 @@ class MMWeightMxfp4Hip(MMWeightMxfp8Hip):
     MMWeightMxfp8Hip's protocol with the MXFP4 quantiser on both sides: the weight is uint8 [N, K/2] with the e8m0 table [K/128, N, 4] under
     `<name>_scale`; a fused driver's shared quantised activation is `quantize_input`'s pair.  K % 256 == 0."""
 
-    def load(self, weight_dict):
-        w = weight_dict[self.weight_name]
-        if not w.is_cuda:
-            raise lib.X2VError(f"{self.weight_name}: MXFP4 weights are quantised by the HIP kernel at load — tensor is on {w.device}")
-        if w.dtype == torch.uint8:  # what state_dict wrote: the packed codes with their table
-            self.weight, self.weight_scale = w.contiguous(), weight_dict[self.weight_name + "_scale"].view(torch.uint8).contiguous()
-        else:
-            self.weight, self.weight_scale = lib.quant_mxfp4(w.to(torch.bfloat16).contiguous())
-        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
+    _label, _quant_weight, _takes_packed = "MXFP4", staticmethod(lib.quant_mxfp4), True
 
     def quantize_input(self, input_tensor):
         return lib.quant_mxfp4(input_tensor)

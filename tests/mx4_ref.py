@@ -1,4 +1,4 @@
-"""float64 references, seeded inputs and fp32 emulations for the MXFP4 x MXFP4 path: quant_mxfp4_kernel (lightx2v_amd/csrc/mx.hip) and the MXM = 3
+"""float64 references, seeded inputs and fp32 emulations for the MXFP4 x MXFP4 path: quant_mx_kernel<3> (lightx2v_amd/csrc/mx.hip) and the MXM = 3
 instantiations of gemm_kernel (gemm.hip, 128x128) and gemm256_kernel (gemm256.hip, 256x256 ping-pong) — OCP e2m1 elements on both sides.  Plain PyTorch
 on float64; nothing here imports the library or oracle/.  The scale rule, the table layout, family I / R, Expect, Case, the epilogue chains and both
 acceptance rules are tests/mx_ref.py's and tests/gemm_ref.py's; this module adds the 4-bit element, its packing and the inputs whose a and b are e2m1.
@@ -222,6 +222,6 @@ def family_i_shapes():
 
 
 def auto_body(M, N, K):
-    """The body variant 0 takes without an epilogue (mx.hip gemm_mxfp4_impl: MXFP8's rule on the K-tiles of 256, from 6 K-tiles on instead of 8;
+    """The body variant 0 takes without an epilogue (mx.hip mx_body: MXFP8's rule on the K-tiles of 256, from 6 K-tiles on instead of 8;
     row strides far below 2^24)."""
     return 2 if -(-M // 256) * -(-N // 256) >= 192 and K // KTILE4 >= 6 else 1

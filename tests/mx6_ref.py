@@ -1,4 +1,4 @@
-"""float64 references, seeded inputs and fp32 emulations for the MXFP6-weight path: quant_mxfp6_kernel (lightx2v_amd/csrc/mx.hip) and the MXM = 2
+"""float64 references, seeded inputs and fp32 emulations for the MXFP6-weight path: quant_mx_kernel<2> (lightx2v_amd/csrc/mx.hip) and the MXM = 2
 instantiations of gemm_kernel (gemm.hip, 128x128) — MXFP6 (e3m2) weights x MXFP8 (e4m3) activations.  Plain PyTorch on float64; nothing here imports
 the library or oracle/.  The scale rule, the table layout, family I / R, Expect, Case, the epilogue chains and both acceptance rules are
 tests/mx_ref.py's and tests/gemm_ref.py's; this module adds the 6-bit element, its packing and the inputs whose b is e3m2.  Shared by

@@ -1,4 +1,4 @@
-"""float64 references, seeded inputs, fp32 emulations and the GPU module's lists for the MXFP8 path: quant_mxfp8_kernel
+"""float64 references, seeded inputs, fp32 emulations and the GPU module's lists for the MXFP8 path: quant_mx_kernel<1>
 (lightx2v_amd/csrc/mx.hip) and the MX instantiations of gemm_kernel (gemm.hip, 128x128) and gemm256_kernel (gemm256.hip).  Plain PyTorch on float64; nothing here imports the library or
 oracle/.  bf16 rounding, Expect, Case, the epilogue chains and both acceptance rules are tests/gemm_ref.py's.  Shared by tests/test_mx_ref_host.py
 (the yardstick checked without a GPU) and tests/test_gpu_mx_fp64.py (the kernels checked against it).
@@ -357,5 +357,5 @@ def family_i_shapes():
 
 
 def auto_body(M, N, K):
-    """The body variant 0 takes without an epilogue (mx.hip gemm_mxfp8_impl; operand row strides far below 2^24)."""
+    """The body variant 0 takes without an epilogue (mx.hip mx_body; operand row strides far below 2^24)."""
     return 2 if -(-M // 256) * -(-N // 256) >= 192 and K // 128 >= 8 else 1

@@ -1,4 +1,4 @@
-"""MXFP4 (e2m1) x MXFP4 — quant_mxfp4_kernel of mx.hip and the fp4 modes of gemm.hip's 128x128 kernel and of gemm256.hip's 256x256 ping-pong kernel —
+"""MXFP4 (e2m1) x MXFP4 — quant_mx_kernel<3> of mx.hip and the fp4 modes of gemm.hip's 128x128 kernel and of gemm256.hip's 256x256 ping-pong kernel —
 against the float64 references of tests/mx4_ref.py, at the smallest shapes at which each edge exists.  tests/test_mx4_ref_host.py shows which subtly
 wrong kernels and quantisers this rejects.
 

@@ -1,4 +1,4 @@
-"""MXFP6 (e3m2) weights x MXFP8 (e4m3) activations — quant_mxfp6_kernel of mx.hip and the fp6-weight modes of gemm.hip's 128x128 kernel and of
+"""MXFP6 (e3m2) weights x MXFP8 (e4m3) activations — quant_mx_kernel<2> of mx.hip and the fp6-weight modes of gemm.hip's 128x128 kernel and of
 gemm256.hip's 256x256 ping-pong kernel — against the float64 references of tests/mx6_ref.py, at the smallest shapes at which each edge exists.
 tests/test_mx6_ref_host.py shows which subtly wrong kernels and quantisers this rejects.
 

@@ -1,4 +1,4 @@
-"""The MXFP8 path — quant_mxfp8_kernel of mx.hip and the MX instantiations of gemm.hip's 128x128 kernel and of gemm256.hip's 256x256 ping-pong kernel —
+"""The MXFP8 path — quant_mx_kernel<1> of mx.hip and the MX instantiations of gemm.hip's 128x128 kernel and of gemm256.hip's 256x256 ping-pong kernel —
 against the float64 references of tests/mx_ref.py, at the smallest shapes at which each edge exists.  tests/test_mx_ref_host.py shows which subtly
 wrong kernels and quantisers this rejects.
 
@@ -233,9 +233,9 @@ def test_epilogues(lib, M, N, K):
 @pytest.mark.parametrize("M,N,K", X.AUTO)
 def test_automatic_choice(lib, M, N, K):
     """variant = 0 just above and just below `tiles256 >= 192 && K / 128 >= 8` (13 x 16 = 208 tiles of 256; 8 K tiles -> the 256x256 body, 7 -> the
-    128x128 body; there is no choice query for MX).  Family I: the result equals the float64 chain and the forced variant's output bit for bit.
-    Family I cannot tell the bodies apart by their bits: this pins the correctness of whatever runs, not the choice.  The float64 side of this
-    shape lives on the device."""
+    128x128 body).  Family I: the result equals the float64 chain and the forced variant's output bit for bit.
+    Family I cannot tell the bodies apart by their bits: this pins the correctness of whatever runs, not the choice — that is pinned on the host,
+    through x2v_gemm_mx_kernel_choice (tests/test_mx_ref_host.py::test_kernel_choice_query).  The float64 side of this shape lives on the device."""
     inp, d = inputs("I", M, N, K)
     for use_alpha in (True, False):
         v = inp.scaled(use_alpha)

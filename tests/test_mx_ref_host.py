@@ -175,3 +175,86 @@ def test_gemm_mutations_are_rejected(mut):
     assert "I" in hits
     if mut in ("scale_bytes_swapped", "scale_dword_late", "drop_last_tile", "k_tile_twice", "alpha_after_bias", "rowmajor_table_read_as_tiled", "truncate"):
         assert hits == {"I", "R"}
+
+
+# ------------------------------------------------------------------------------------------------------------------- argument validation
+def test_argument_validation_needs_no_gpu():
+    """The MXFP8 entries check their arguments before any HIP call, with the library's error codes (-1 shape, -2 alignment, -5 argument) — the
+    checks of the MXFP6 and MXFP4 entries (tests/test_mx6_ref_host.py, tests/test_mx4_ref_host.py): one body serves the three formats."""
+    import ctypes
+
+    from lightx2v_amd import lib
+
+    L = lib._lib
+    a, odd, two = ctypes.c_void_p(4096), ctypes.c_void_p(4100), ctypes.c_void_p(4098)
+    assert {"x2v_quant_mxfp8_bf16", "x2v_gemm_mxfp8", "x2v_gemm_mxfp8_epi", "x2v_gemm_mxfp8_variant"} <= set(lib.PROTOTYPES)
+    # x2v_quant_mxfp8_bf16(x, ldx, q, ldq, scales, M, K, stream)
+    assert L.x2v_quant_mxfp8_bf16(a, 96, a, 96, a, 4, 96, None) == -1 and b"K=96" in L.x2v_last_error()
+    assert L.x2v_quant_mxfp8_bf16(None, 128, a, 128, a, 4, 128, None) == -5
+    assert L.x2v_quant_mxfp8_bf16(a, 128, odd, 128, a, 4, 128, None) == -2  # q not 8-byte aligned
+    assert L.x2v_quant_mxfp8_bf16(a, 128, a, 120, a, 4, 128, None) == -2  # ldq below K
+    assert L.x2v_quant_mxfp8_bf16(a, 128, a, 128, a, 0, 128, None) == 0  # no rows: nothing launched
+    # x2v_gemm_mxfp8(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, stream)
+    P = L.x2v_gemm_mxfp8
+    assert P(a, 192, a, a, 192, a, None, None, a, 64, 4, 64, 192, None) == -1 and b"K=192" in L.x2v_last_error()  # K % 128
+    assert P(a, 128, a, None, 128, a, None, None, a, 64, 4, 64, 128, None) == -5  # null operand
+    assert P(None, 128, a, a, 128, a, None, None, a, 64, 4, 64, 128, None) == -5
+    assert P(a, 128, None, a, 128, a, None, None, a, 64, 4, 64, 128, None) == -5  # null scale table
+    assert P(a, 128, a, a, 128, a, None, None, a, 64, 4, 60, 128, None) == -1  # N % 8
+    assert P(a, 128, a, odd, 128, a, None, None, a, 64, 4, 64, 128, None) == -2  # b not 16-byte aligned
+    assert P(a, 128, a, a, 136, a, None, None, a, 64, 4, 64, 128, None) == -2  # ldb % 16
+    assert P(a, 112, a, a, 128, a, None, None, a, 64, 4, 64, 128, None) == -2  # lda below K bytes
+    assert P(a, 128, a, a, 128, a, None, None, odd, 64, 4, 64, 128, None) == -2  # y
+    assert P(a, 128, a, a, 128, a, two, None, a, 64, 4, 64, 128, None) == -2  # a bias only 2-byte aligned: both bodies fetch it as 8-byte pairs
+    # x2v_gemm_mxfp8_variant(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, variant, stream)
+    V = L.x2v_gemm_mxfp8_variant
+    assert V(a, 128, a, a, 128, a, None, None, a, 64, 4, 64, 128, 3, None) == -5 and b"unknown variant" in L.x2v_last_error()
+    assert V(a, 128, a, a, 128, a, None, None, a, 64, 4, 64, 128, -1, None) == -5
+    assert V(a, 1 << 24, a, a, 128, a, None, None, a, 64, 4, 64, 128, 2, None) == -1  # the 256x256 body's 32-bit tile addressing
+    assert V(a, 128, a, a, 1 << 24, a, None, None, a, 64, 4, 64, 128, 2, None) == -1 and b"leading dimension" in L.x2v_last_error()
+    # x2v_gemm_mxfp8_epi(a, lda, sa, b, ldb, sb, bias, alpha, y, ldy, M, N, K, epilogue, resid, ldr, gate, stream)
+    E = L.x2v_gemm_mxfp8_epi
+    assert E(a, 128, a, a, 128, a, None, None, a, 64, 4, 64, 128, 2, None, 0, None, None) == -5 and b"resid" in L.x2v_last_error()  # residual epilogue without resid
+    assert E(a, 128, a, a, 128, a, None, None, a, 64, 4, 64, 128, 2, a, 60, None, None) == -2  # ldr below N
+    assert E(a, 1 << 24, a, a, 128, a, None, None, a, 64, 4, 64, 128, 1, None, 0, None, None) == -1  # every fused epilogue runs the 256x256 body
+    assert E(a, 128, a, a, 128, a, None, None, a, 64, 4, 64, 192, 0, None, 0, None, None) == -1
+
+
+# ------------------------------------------------------------------------------------------------------------------- body rule
+MX_FORMATS = ((8, 8, 128, 8), (8, 6, 128, 8), (4, 4, 256, 6))  # element bits of a and b, k-values per K-tile, K-tiles from which the 256x256 body runs
+
+
+@pytest.mark.parametrize("bits_a,bits_b,ktile,nk_min", MX_FORMATS)
+def test_kernel_choice_query(bits_a, bits_b, ktile, nk_min):
+    """x2v_gemm_mx_kernel_choice (host arithmetic) is the rule variant 0 follows: the 256x256 body from 192 tiles of 256x256 and the format's least
+    number of K-tiles on, with both leading dimensions below 2^24 bytes.  For the formats with e4m3 activations it is the w8a8 GEMM's rule, asked
+    of x2v_gemm_kernel_choice over the edges; and it is the rule the GPU suites model (auto_body) at their AUTO shapes."""
+    from lightx2v_amd import lib
+    from tests import mx4_ref as R4
+
+    ch = lambda M, N, K, **ld: lib.gemm_mx_kernel_choice(bits_a, bits_b, M, N, K, **ld)
+    big = 1 << 24
+    assert ch(3073, 4096, nk_min * ktile) == 2 and ch(3073, 4096, (nk_min - 1) * ktile) == 1  # 13 x 16 tiles
+    assert ch(191 * 256, 256, 16 * ktile) == 1 and ch(191 * 256 + 1, 256, 16 * ktile) == 2 and ch(3072, 4096 - 256, 16 * ktile) == 1  # 191, 192, 180 tiles
+    assert ch(3073, 4096, 16 * ktile, lda=big) == 1 and ch(3073, 4096, 16 * ktile, ldb=big) == 1 and ch(3073, 4096, 16 * ktile, lda=big - 16, ldb=big - 16) == 2
+    ref = R4 if bits_a == 4 else X  # tests/mx6_ref.py takes mx_ref's AUTO shapes and auto_body
+    assert [ch(*s) for s in ref.AUTO] == [ref.auto_body(*s) for s in ref.AUTO] == [2, 1]
+    if bits_a == 8:
+        n = 0
+        for M in (1, 190 * 256, 191 * 256, 191 * 256 + 1, 3072, 3073):
+            for N in (8, 256, 3848, 4096):
+                for nk in (1, 7, 8, 9, 16):
+                    for lda in (nk * 128, big - 16, big):
+                        for ldb in (nk * 128 * bits_b // 8, big - 16, big):
+                            w8a8 = lib.gemm_kernel_choice(M, N, nk * 128, ldx=lda, ldw=ldb if bits_b == 8 else lda, fp8=True) == 2
+                            assert (ch(M, N, nk * 128, lda=lda, ldb=ldb) == 2) == (w8a8 and ldb < big), (M, N, nk, lda, ldb)
+                            n += 1
+        assert n == 6 * 4 * 5 * 9
+    # a bad shape or format is an error, not a guess
+    L = lib._lib
+    assert L.x2v_gemm_mx_kernel_choice(0, 256, 256, 256, 256, 256) == -5 and L.x2v_gemm_mx_kernel_choice(4, 256, 256, 256, 256, 256) == -5
+    fmt = MX_FORMATS.index((bits_a, bits_b, ktile, nk_min)) + 1
+    assert L.x2v_gemm_mx_kernel_choice(fmt, 256, 256, ktile // 2 * 3, 512, 512) == -1 and L.x2v_gemm_mx_kernel_choice(fmt, 256, 252, ktile, 512, 512) == -1
+    assert L.x2v_gemm_mx_kernel_choice(fmt, 256, 256, 2 * ktile, 2 * ktile * bits_a // 8 - 16, 512) == -1  # lda below the row's bytes
+    with pytest.raises(lib.X2VError):
+        ch(0, 256, ktile)
