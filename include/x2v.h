@@ -816,6 +816,35 @@ int x2v_gemm_rows_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, v
  * no reference counterpart). */
 int x2v_gemm_rows_bf16_tile_choice(int64_t M, int N, int epilogue);
 
+/* ---- the quantised umT5 encoder (t5_quantized with t5_quant_scheme int8 | fp8): every Linear of T5Attention and T5FeedForward is a QuantLinearInt8 /
+ * QuantLinearFp8 (models/input_encoders/hf/q_linear.py:20-39, 69-87; built by t5/model.py:84-96, 145-155), a per-token dynamic activation quantiser
+ * followed by cutlass_scaled_mm with a per-output-channel weight scale and no bias.  The activation quantisers are x2v_quant_{int8,fp8}_rowwise. ---- */
+
+/* code types of x2v_gemm_rows_w8a8 */
+#define X2V_W8A8_INT8 0 /* two's-complement int8 codes, the "w8a8 int8" contract above */
+#define X2V_W8A8_E4M3 1 /* float8_e4m3fn (OCP) codes, the contract of x2v_quant_fp8_rowwise / x2v_gemm_fp8 */
+
+/* y[M,N] = epi(float(xq[M,K] . wq[N,K]^T) * sx[m] * sw[n]) -> bf16 for 1 <= M <= 4096, the weight-streaming small-M form of x2v_gemm_int8 / x2v_gemm_fp8 —
+ * replaces cutlass_scaled_mm of q_linear.py:32-39, 80-87 (bias is None in T5).  xq [M,K] and wq [N,K] are row-major codes of `kind`, sx [M] and sw [N] fp32.
+ * The product is that of the code type's contract (int8: the exact int32 sum, converted once by v_cvt_f32_i32; e4m3: exact products of the codes, decoded to fp16, summed in fp32), and
+ * v = (float(acc) * sx[m]) * sw[n] is rounded to bf16 once, in the statement order of x2v_gemm_int8 / x2v_gemm_fp8.  Epilogues: the X2V_EPIR_* set, on v in
+ * the place of acc (X2V_EPIR_GEGLU: wq and sw hold 2N rows, fc1 and gate.0 interleaved; resid is read by X2V_EPIR_RESIDUAL only, and y may alias it).
+ * K % 64 == 0 (int8, and K <= 65536: |acc| < 2^31) or K % 128 == 0 (e4m3); N % 4 == 0; ldx, ldw multiples of 16; xq, wq, sw, y, resid 16-byte aligned.
+ * Each output value is reduced in k order by one lane whatever M and whatever the tile: rows of a packed batch equal the rows computed alone, bit for bit. */
+int x2v_gemm_rows_w8a8(const void* xq, int64_t ldx, const float* sx, const void* wq, int64_t ldw, const float* sw, void* y, int64_t ldy, int64_t M, int N, int K,
+                       int kind, int epilogue, const void* resid, int64_t ldr, void* stream);
+
+/* The tile x2v_gemm_rows_w8a8 launches for (M, N, epilogue), either code type: the codes of x2v_gemm_rows_bf16_tile_choice (host arithmetic; no reference
+ * counterpart). */
+int x2v_gemm_rows_w8a8_tile_choice(int64_t M, int N, int epilogue);
+
+/* x2v_rmsnorm_bf16 with X2V_ROUND_FP32 (T5LayerNorm, t5/model.py:68-72) fused with x2v_quant_int8_rowwise / x2v_quant_fp8_rowwise on its bf16 output, in one
+ * pass over the row: xq [M,D] codes (ld = ldq) and sx [M] fp32 scales, bit-identical to the two calls in sequence — the norm in front of q | k | v and of
+ * fc1 | gate.0, quantised once for every QuantLinear that reads it (q_linear.py:20-22, 69-71 on the same input give the same codes).  D % 8 == 0,
+ * D <= 16384; rows 16-byte aligned, code rows 8-byte aligned. */
+int x2v_rmsnorm_quant_int8(const void* x, int64_t ldx, const void* w, void* xq, int64_t ldq, float* sx, int64_t M, int D, float eps, void* stream);
+int x2v_rmsnorm_quant_fp8(const void* x, int64_t ldx, const void* w, void* xq, int64_t ldq, float* sx, int64_t M, int D, float eps, void* stream);
+
 /* out[r0_b + i, h*64 : h*64 + 64] = softmax_j(scale * q_i . k_j + bias[h][j - i + 511]) v_j over the keys of sequence b only, non-causal, head dim 64 —
  * replaces the einsum / attn_bias / softmax / einsum of T5Attention.forward (t5/model.py:115-129) with the block's T5RelativeEmbedding (:255-263) and the
  * padding mask (:121) folded in: `batch` <= 8 sequences of 1..512 tokens are packed row after row, sequence b being rows cu_seqlens[b] .. cu_seqlens[b+1] - 1

@@ -119,6 +119,10 @@ PROTOTYPES = {
     "x2v_clip_preprocess_f16": [_c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _c_void_p],
     "x2v_gemm_rows_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
     "x2v_gemm_rows_bf16_tile_choice": [_i64, _i32, _i32],
+    "x2v_gemm_rows_w8a8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
+    "x2v_gemm_rows_w8a8_tile_choice": [_i64, _i32, _i32],
+    "x2v_rmsnorm_quant_int8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _f32, _c_void_p],
+    "x2v_rmsnorm_quant_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _f32, _c_void_p],
     "x2v_attn_bf16_d64_relbias": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, ctypes.POINTER(_i32), _i32, _i32, _f32, _c_void_p],
     "x2v_attn_f16_causal": [_c_void_p, _i64, _c_void_p, _i64, ctypes.POINTER(_i32), _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p],
     "x2v_rmsnorm_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _f32, _c_void_p],
@@ -1704,6 +1708,69 @@ def gemm_rows_bf16_tile_choice(M, N, epilogue=EPIR_NONE):
     t = _lib.x2v_gemm_rows_bf16_tile_choice(M, N, epilogue)
     _check(min(t, 0), "gemm_rows_bf16_tile_choice")
     return ((128, 64), (64, 64), (64, 32), (64, 16))[t]
+
+
+W8A8_INT8, W8A8_E4M3 = 0, 1  # x2v.h X2V_W8A8_*
+_ROWS8_KINDS = {torch.int8: W8A8_INT8, torch.float8_e4m3fn: W8A8_E4M3}  # codes dtype -> kind
+
+
+def _codes2d(t, name, dtype=None):
+    if t.dtype not in _ROWS8_KINDS or (dtype is not None and t.dtype != dtype):
+        raise X2VError(f"{name}: expected {'int8 or float8_e4m3fn codes' if dtype is None else dtype}, got {t.dtype}")
+    return _row2d(t, name)
+
+
+def gemm_rows_w8a8(xq, sx, wq_nk, sw, epilogue=EPIR_NONE, resid=None, out=None):
+    """x2v_gemm_rows_w8a8: y[M, N] = epi((xq[M, K] . wq^T) * sx[m] * sw[n]) in bf16, M <= 4096, on int8 or float8_e4m3fn codes (both operands of the one
+    type) with fp32 scales sx [M] / [M, 1] and sw [rows of wq] / [.., 1]; K % 64 == 0 (int8) or K % 128 == 0 (e4m3), N % 4 == 0.  wq is [N, K], or
+    [2N, K] with EPIR_GEGLU (rows of fc1 and gate.0 interleaved, sw likewise)."""
+    x, w = _codes2d(xq, "gemm_rows_w8a8 xq"), _codes2d(wq_nk, "gemm_rows_w8a8 weight", xq.dtype)
+    kind = _ROWS8_KINDS[x.dtype]
+    M, K = x.shape
+    if w.shape[1] != K:
+        raise X2VError(f"gemm_rows_w8a8: xq {tuple(x.shape)} and weight {tuple(w.shape)} disagree on K")
+    if epilogue == EPIR_GEGLU and w.shape[0] % 2:
+        raise X2VError(f"gemm_rows_w8a8: the GEGLU epilogue needs an even number of weight rows, got {w.shape[0]}")
+    N = w.shape[0] // 2 if epilogue == EPIR_GEGLU else w.shape[0]
+    if (resid is not None) != (epilogue == EPIR_RESIDUAL):
+        raise X2VError("gemm_rows_w8a8: resid goes with EPIR_RESIDUAL, and only with it")
+    sx, sw = _vec(sx, "gemm_rows_w8a8 sx", M, dtype=torch.float32), _vec(sw, "gemm_rows_w8a8 sw", w.shape[0], dtype=torch.float32)
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device) if out is None else _bf16rows(out, "gemm_rows_w8a8 out")
+    if out.shape != (M, N) or (resid is not None and _bf16rows(resid, "gemm_rows_w8a8 resid").shape != (M, N)):
+        raise X2VError(f"gemm_rows_w8a8: out / resid must be [{M}, {N}]")
+    init()
+    _check(_lib.x2v_gemm_rows_w8a8(_p(x), x.stride(0), _p(sx), _p(w), w.stride(0), _p(sw), _p(out), out.stride(0), M, N, K, kind, epilogue, _p(resid),
+                                   0 if resid is None else resid.stride(0), _stream()), "gemm_rows_w8a8")
+    return out
+
+
+def gemm_rows_w8a8_tile_choice(M, N, epilogue=EPIR_NONE):
+    """x2v_gemm_rows_w8a8_tile_choice: (rows of xq, rows of wq) of the workgroup tile x2v_gemm_rows_w8a8 launches — host arithmetic."""
+    t = _lib.x2v_gemm_rows_w8a8_tile_choice(M, N, epilogue)
+    _check(min(t, 0), "gemm_rows_w8a8_tile_choice")
+    return ((128, 64), (64, 64), (64, 32), (64, 16))[t]
+
+
+def _rmsnorm_quant8(x, weight, eps, kind, entry):
+    x2 = _bf16rows(x, f"rmsnorm_quant_{kind.tag} x")
+    M, D = x2.shape
+    weight = _vec(weight, f"rmsnorm_quant_{kind.tag} weight", D)
+    xq = torch.empty((M, D), dtype=kind.dtype, device=x.device)
+    s = torch.empty((M, 1), dtype=torch.float32, device=x.device)
+    init()
+    if M:
+        _check(entry(_p(x2), x2.stride(0), _p(weight), _p(xq), xq.stride(0), _p(s), M, D, eps, _stream()), f"rmsnorm_quant_{kind.tag}")
+    return xq, s
+
+
+def rmsnorm_quant_int8(x, weight, eps=1e-6):
+    """(int8 codes [M, D], fp32 scales [M, 1]) of T5's RMSNorm of x — x2v_rmsnorm_quant_int8, bit-identical to quant_int8_rowwise(rmsnorm(x, weight, eps))."""
+    return _rmsnorm_quant8(x, weight, eps, _INT8, _lib.x2v_rmsnorm_quant_int8)
+
+
+def rmsnorm_quant_fp8(x, weight, eps=1e-6):
+    """rmsnorm_quant_int8 for the e4m3 codes — x2v_rmsnorm_quant_fp8, bit-identical to quant_fp8_rowwise(rmsnorm(x, weight, eps))."""
+    return _rmsnorm_quant8(x, weight, eps, _FP8, _lib.x2v_rmsnorm_quant_fp8)
 
 
 def _cu_seqlens(cu_seqlens, rows, who):

@@ -25,7 +25,7 @@ class PackedTower:
         self._bufs, self._rows, self._plans, self._tokenizer = {}, 0, OrderedDict(), None
 
     def _buffers(self):
-        """name → columns, or (columns, rows) for a buffer that does not follow M."""
+        """name → columns, or (columns, rows) for a buffer that does not follow M (rows None: M), or (columns, rows, dtype) for one that is not DTYPE."""
         raise NotImplementedError
 
     def _launches(self, p, M, cu_arr, batch, stream):
@@ -38,8 +38,8 @@ class PackedTower:
         if M > self._rows:
 
             def buf(spec):
-                cols, rows = spec if isinstance(spec, tuple) else (spec, M)
-                return torch.empty((rows, cols), dtype=self.DTYPE, device=self.device)
+                cols, rows, dtype = (*spec, self.DTYPE)[:3] if isinstance(spec, tuple) else (spec, M, self.DTYPE)
+                return torch.empty((M if rows is None else rows, cols), dtype=dtype, device=self.device)
 
             self._plans.clear()
             self._bufs = {k: buf(spec) for k, spec in self._buffers().items()}

@@ -112,6 +112,7 @@ def main():
     ap.add_argument("--image", default=None, help="i2v: build clip_encoder_out / vae_encode_out from this image (PIL) with the HIP CLIP tower / VAE encoder, timed as clip_encode_s / vae_encode_s")
     ap.add_argument("--clip-ckpt", default=None, help="i2v with --image / --encode: CLIP checkpoint (.pth / .safetensors) for the HIP image tower (default: seeded synthetic weights)")
     ap.add_argument("--encode", action="store_true", help="i2v: as --image, on a seeded synthetic image of the workload's size")
+    ap.add_argument("--quant", choices=["int8", "fp8"], default=None, help="with --t5: the quantised encoder (t5_quantized, weights from t5.quantize_state_dict)")
     ap.add_argument("--t5", action="store_true", help="build context / context_null from seeded token ids (77- and 126-token prompts) with the HIP umT5-XXL encoder (seeded weights), timed as t5_encode_s")
     a = ap.parse_args()
     if a.causvid:
@@ -203,7 +204,13 @@ def main():
 
         if dims.get("text_dim", 4096) != synth.T5_DIMS["umt5-xxl"]["dim"]:
             raise SystemExit(f"--t5: the workload's text_dim {dims.get('text_dim')} is not umT5-XXL's {synth.T5_DIMS['umt5-xxl']['dim']}")
-        t5_model = t5.T5EncoderModel(dims.get("text_len", 512), torch.bfloat16, "cuda", synth.synth_t5_weights(synth.T5_DIMS["umt5-xxl"], seed=0, device="cuda"))
+        t5_sd = synth.synth_t5_weights(synth.T5_DIMS["umt5-xxl"], seed=0, device="cuda")
+        if a.quant:
+            t5_model = t5.T5EncoderModel(dims.get("text_len", 512), torch.bfloat16, "cuda", None, t5_quantized=True, t5_quantized_ckpt=t5.quantize_state_dict(t5_sd, a.quant),
+                                         quant_scheme=a.quant)
+        else:
+            t5_model = t5.T5EncoderModel(dims.get("text_len", 512), torch.bfloat16, "cuda", t5_sd)
+        del t5_sd
         gt = torch.Generator().manual_seed(7)
         t5_ids = [torch.randint(1, synth.T5_DIMS["umt5-xxl"]["vocab"], (1, n), generator=gt) for n in (77, 126)]  # prompt, negative prompt
         t5_args = (t5_ids[0], torch.ones_like(t5_ids[0]), t5_ids[1], torch.ones_like(t5_ids[1]))

@@ -5,7 +5,11 @@ process, interleaved A-B-A-B, the same encoder in bf16 through plain PyTorch on 
 one forward per prompt (tests/t5_restatement.py; its ids and mask are on the GPU and its delta -> bucket map is built before the clock starts, so the timed
 baseline holds no host work beyond PyTorch's own launches).  Reports ms, Linear weight bytes / time against the streaming rate `tools/x2v_check hbm` measures in the same
 session (run first, as a child process; --hbm-gbs overrides) and against DESIGN §4's 6.29 TB/s.  One JSON line.
-    python tools/t5_encode_bench.py [--rounds 3] [--layers 24]"""
+    python tools/t5_encode_bench.py [--rounds 3] [--layers 24]
+--quant int8 fp8: instead, the quantised encoder(s) (t5_quantized, weights from quantize_state_dict) against the bf16 one, all on the HIP kernels, the launch
+chain of the 77 + 126 pass interleaved A-B-A-B (median of --rounds, default 7), each form against its own weight-streaming floor, and per launch the four
+GEMM shapes in bf16 and in 8 bits and the two row quantisers a block adds.  One JSON line, also written to --out.
+    python tools/t5_encode_bench.py --quant int8 fp8 --out profiles/t5_quant_encode_bench.json"""
 import argparse
 import json
 import os
@@ -40,12 +44,75 @@ def timed_ms(fn):
     return a.elapsed_time(b)
 
 
+def median_ms(fn, rounds=7):
+    fn()
+    return sorted(timed_ms(fn) for _ in range(rounds))[rounds // 2]
+
+
+def quant_main(a):
+    from lightx2v_amd import lib, synth, t5
+
+    lib.init(0)
+    rounds = a.rounds or 7
+    dims = dict(synth.T5_DIMS["umt5-xxl"], layers=a.layers)
+    sd = synth.synth_t5_weights(dims, seed=0, device="cuda")
+    models = {"bf16": t5.T5EncoderModel(512, torch.bfloat16, "cuda", sd)}
+    for scheme in a.quant:
+        models[scheme] = t5.T5EncoderModel(512, torch.bfloat16, "cuda", None, t5_quantized=True, t5_quantized_ckpt=t5.quantize_state_dict(sd, scheme), quant_scheme=scheme)
+    g = torch.Generator().manual_seed(4)
+    prompts = [torch.randint(1, dims["vocab"], (1, n), generator=g) for n in (77, 126)]
+    args = (prompts[0], torch.ones_like(prompts[0]), prompts[1], torch.ones_like(prompts[1]))
+    for m in models.values():  # warm-up; leaves every model's M = 203 workspace filled
+        t5.run_text_encoder(m, *args)
+        t5.run_text_encoder(m, *args)
+    torch.cuda.synchronize()
+    ms = {k: [] for k in models}
+    for _ in range(rounds):  # A-B-A-B: the forms alternate inside one process
+        for k, m in models.items():
+            ms[k].append(timed_ms(lambda: m.forward_packed((77, 126))))
+    med = {k: sorted(v)[rounds // 2] for k, v in ms.items()}
+    res = {"workload": f"umT5-XXL encoder, {a.layers} blocks: prompts of 77 + 126 tokens in one packed pass, launch chain on a filled workspace, median of {rounds}",
+           "ms_per_encode": med, "ms_all": ms, "ratio_over_bf16": {k: med[k] / med["bf16"] for k in a.quant}, "forms": {}}
+    for k, m in models.items():
+        wb = m.weight_bytes()
+        floor = wb / (HBM_TBS * 1e12) * 1e3
+        res["forms"][k] = {"weight_bytes": wb, "weight_gbs": wb / med[k] / 1e6, "weight_stream_floor_ms_at_6.29TBs": floor, "multiple_of_own_floor": med[k] / floor,
+                           "launches_per_forward": (9 if k != "bf16" else 7) * a.layers + 1}
+    # per launch, M = 203: the four GEMM shapes (fused q | k | v, o, fc1 / gate GEGLU, fc2) and the row quantisers of the attention and the GEGLU output
+    M, D, A, F = 203, dims["dim"], dims["dim_attn"], dims["ffn"]
+    b0, launches = models["bf16"].blocks[0], {}
+    shapes = {"qkv": ("qkv", D, lib.EPIR_NONE), "o": ("o", A, lib.EPIR_RESIDUAL), "geglu": ("geglu", D, lib.EPIR_GEGLU), "fc2": ("fc2", F, lib.EPIR_RESIDUAL)}
+    for name, (key, K, epi) in shapes.items():
+        x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+        r = torch.randn(M, D, device="cuda").to(torch.bfloat16) if epi == lib.EPIR_RESIDUAL else None
+        launches[name] = {"N_rows_of_W": b0[key].shape[0], "K": K, "bf16_ms": median_ms(lambda: lib.gemm_rows_bf16(x, b0[key], epilogue=epi, resid=r), rounds)}
+        for scheme in a.quant:
+            bq = models[scheme].blocks[0]
+            xq, sx = (lib.quant_int8_rowwise if scheme == "int8" else lib.quant_fp8_rowwise)(x)
+            launches[name][scheme + "_ms"] = median_ms(lambda: lib.gemm_rows_w8a8(xq, sx, bq[key], bq[key + "_s"], epilogue=epi, resid=r), rounds)
+    for scheme in a.quant:
+        quant = lib.quant_int8_rowwise if scheme == "int8" else lib.quant_fp8_rowwise
+        xa, xf = (torch.randn(M, n, device="cuda").to(torch.bfloat16) for n in (A, F))
+        launches["quantisers_" + scheme] = {"attention_output_ms": median_ms(lambda: quant(xa), rounds), "geglu_output_ms": median_ms(lambda: quant(xf), rounds)}
+    res["per_launch_M203_wrapper_calls"] = launches
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=0)
+    ap.add_argument("--quant", nargs="+", choices=["int8", "fp8"], default=None)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--hbm-gbs", type=float, default=0.0)
     a = ap.parse_args()
+    if a.quant:
+        return quant_main(a)
+    a.rounds = a.rounds or 3
     hbm = a.hbm_gbs or session_hbm_gbs()
     from lightx2v_amd import lib, synth, t5
     from tests import t5_restatement as R
