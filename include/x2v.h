@@ -283,6 +283,29 @@ int x2v_attn_fwd_bf16_vt_batched(const void* q, int64_t ldq, int64_t q_bstride, 
                                  int64_t vt_bstride, void* o, int64_t ldo, int64_t o_bstride, int64_t Sq, int64_t Sk, int H, int B, int head_dim, float scale,
                                  int flags, void* stream);
 
+/* Per-frame cross-attention, head dim 128 (attn_frames.hip): every query row attends the keys of its OWN frame only — replaces
+ * PerceiverAttentionCA.forward's flash_attn_varlen_func (wan/audio_adapter.py:129-142: q_lens = [h w] * f, k_lens = [128] * f, and the first / last
+ * entry shorter on a sequence-parallel rank, get_q_lens_audio_range :71-94) in one launch.
+ * q, o: [Sq, H*128] bf16, token strides ldq / ldo, head h at column h*128.  k, v: [n_frames * keys_per_frame, H*128] bf16, ROW-MAJOR, token strides
+ * ldk / ldv (the step-invariant K / V projections of the audio tokens; the kernel transposes V in LDS itself, there is no V^T pre-pass).
+ * Local query row r is global row g = row0 + r of frame t = g / rows_per_frame and attends keys [t Kf, (t + 1) Kf), Kf = keys_per_frame:
+ * o[r, h] = softmax(scale * q[r, h] k_t^T) v_t, non-causal.  row0 and Sq are arbitrary: the first and the last frame of the range may be partial.
+ * No byte of o outside the Sq x H*128 window is written; no row of k / v outside the attended frames t(row0) .. t(row0 + Sq - 1) is read.
+ * flags: X2V_ATTN_VT_PRESCALED (q already carries scale*log2(e)), nothing else (X2V_E_ARG).  scale <= 0 selects 1/sqrt(128).
+ * head_dim == 128; Kf in {32, 64, 96, 128}; rows_per_frame >= 1; row0 >= 0; (row0 + Sq - 1) / rows_per_frame < n_frames; 1 <= H <= 65535; every ld
+ * >= H*128 (else X2V_E_SHAPE); q, k, v, o 16-byte aligned and every ld % 8 == 0 (X2V_E_ALIGN).  Sq == 0 is X2V_OK without a launch.
+ *
+ * Arithmetic, per query row and head, every line one rounding unless it says otherwise:
+ *   1.  q' = q with PRESCALED, else bf16(fp32(q) * fp32(scale * log2(e)))         (as x2v_attn_fwd_bf16_vt)
+ *   2.  s_j = q' . k_j for the Kf keys of the frame: fp32, from v_mfma_f32_16x16x32_bf16 on the bf16 operands (base-2 scores)
+ *   3.  m = max_j s_j over ALL Kf scores — they are in registers before anything is exponentiated: the true maximum, no running reference, no rescale
+ *   4.  e_j = exp2(s_j - m) (v_exp_f32, 1 ulp);  l = sum_j e_j over the fp32 e_j (four per-lane partial sums of Kf / 4, then pairwise across lanes)
+ *   5.  a[d] = sum_j bf16(e_j) v_j[d]: P rounded to bf16 (nearest even) as the MFMA operand only, fp32 accumulation
+ *   6.  o[d] = bf16(a[d] * (1 / l)): one reciprocal, one rounding to bf16 at the store.
+ * tests/attn_frames_ref.py restates it in float64. */
+int x2v_attn_frames_fwd_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, int64_t Sq, int64_t row0,
+                             int64_t rows_per_frame, int n_frames, int keys_per_frame, int H, int head_dim, float scale, int flags, void* stream);
+
 /* Block-sparse self-attention: x2v_attn_fwd_bf16_vt restricted to a static mask of 128 x 128 (query rows x keys) blocks — replaces
  * RadialAttnWeight.apply (common/ops/attn/attn_weight.py:129-162 -> attentions/common/radial_attn.py:34-46, the block-sparse wrapper with
  * R = C = 128 it plans and runs) for one sequence.  Operands, layouts and flags (X2V_ATTN_VT_PRESCALED only) as x2v_attn_fwd_bf16_vt, Sq == Sk.

@@ -59,6 +59,7 @@ PROTOTYPES = {
     "x2v_attn_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_vt_carry": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32,
                                    _c_void_p],
+    "x2v_attn_frames_fwd_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_bsr_fwd_bf16_vt": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p],
     "x2v_attn_fwd_bf16_variant": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _c_void_p],
     "x2v_attn_mx_sizes": [_i64, _i64, _i32, ctypes.POINTER(_i64)],
@@ -624,6 +625,25 @@ def attention_cached(q, k_cache, vt_cache, kv_end, num_heads, out=None, prescale
                                   1 if prescaled else 0, _stream()),
         "attention_cached",
     )
+    return out2
+
+
+def attention_frames(q, k, v, num_heads, rows_per_frame, row0=0, keys_per_frame=128, prescaled=False, scale=0.0, out=None):
+    """Per-frame cross-attention (x2v_attn_frames_fwd_bf16): q [Sq, H*128]; k, v [n_frames * keys_per_frame, H*128] row-major (any token stride).
+    Local row r is global row row0 + r, belongs to frame (row0 + r) // rows_per_frame and attends that frame's keys_per_frame keys only; the first
+    and last frame of [row0, row0 + Sq) may be partial (a sequence-parallel rank's rows).  prescaled: q already carries scale*log2(e)."""
+    q2, k2, v2 = _row2d(_bf16(q, "q"), "q"), _row2d(_bf16(k, "k"), "k"), _row2d(_bf16(v, "v"), "v")
+    Sq, W = q2.shape[0], num_heads * 128
+    if min(q2.shape[1], k2.shape[1], v2.shape[1]) < W:
+        raise X2VError(f"attention_frames: q {tuple(q2.shape)} k {tuple(k2.shape)} v {tuple(v2.shape)} do not describe {num_heads} heads of 128")
+    if keys_per_frame <= 0 or k2.shape[0] % keys_per_frame or v2.shape[0] != k2.shape[0] or k2.shape[0] == 0:
+        raise X2VError(f"attention_frames: k {tuple(k2.shape)} v {tuple(v2.shape)} are not whole frames of {keys_per_frame} keys")
+    n_frames = k2.shape[0] // keys_per_frame
+    out2 = _attn_out(out, "attention_frames", Sq, W, q.device)
+    init()
+    # Sq == 0: torch hands out a null data_ptr for an empty tensor, which the C entry never looks at (it returns after its shape checks)
+    _check(_lib.x2v_attn_frames_fwd_bf16(_p(q2), q2.stride(0), _p(k2), k2.stride(0), _p(v2), v2.stride(0), _p(out2), out2.stride(0), Sq, row0, rows_per_frame, n_frames,
+                                         keys_per_frame, num_heads, 128, scale, 1 if prescaled else 0, _stream()), "attn_frames")
     return out2
 
 

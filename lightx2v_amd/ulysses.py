@@ -351,6 +351,8 @@ def shard_wan_block_stack(wan_model, pa, passthrough=lambda: False):
     original_infer = tr.infer
 
     def new_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks=None):
+        if audio_dit_blocks:
+            tr._refuse_unbuilt_audio()  # parallel_attention is set: there is no multi-GPU driver for the audio model
         if passthrough():
             return original_infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
         x = pre_process(x, pa.group)

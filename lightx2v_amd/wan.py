@@ -308,6 +308,7 @@ class WanTransformerInfer:
         # self_attn_1_type "hip_mxfp8": block-scaled fp8 self-attention (lib.attention_mx) on the single-sequence path; q comes from the norm+RoPE
         # kernel with its scale folded in, v from the plain projection.  Cross-attention stays bf16.
         self.mx_attn = _cfg(config, "self_attn_1_type", "hip_flash") == "hip_mxfp8"
+        self.audio_sr = bool(_cfg(config, "audio_sr", False))
         self.blocks_num = config["num_layers"]
         self.phases_num = 4
         self.num_heads = config["num_heads"]
@@ -333,12 +334,27 @@ class WanTransformerInfer:
         self.infer_conditional = not self.infer_conditional
 
     def infer(self, weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks=None):
-        return self._infer_without_offload(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
+        return self._infer_without_offload(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks)
 
     def _infer_without_offload(self, weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks=None):
+        """audio_dit_blocks: a list of {block_idx: {"modify_func", "kwargs"}} dicts (lightx2v_amd.audio.AudioAdapter.forward, or the reference's
+        AudioAdapter): after block i every dict that names i rewrites x (transformer_infer.py:282-286).  None or empty: nothing changes."""
+        if audio_dit_blocks:
+            self._refuse_unbuilt_audio()
         for block_idx in range(self.blocks_num):
             x = self.infer_block(weights.blocks[block_idx], grid_sizes, embed, x, embed0, seq_lens, freqs, context)
+            for blocks in audio_dit_blocks or ():
+                if block_idx in blocks:
+                    x = blocks[block_idx]["modify_func"](x, grid_sizes, **blocks[block_idx]["kwargs"])
         return x
+
+    def _refuse_unbuilt_audio(self):
+        """The audio adapter's per-frame cross-attention runs on one GPU, one forward per pass: its rows are frame-aligned from row 0 (the kernel's
+        row0 / partial-frame form has no driver yet), and the pair pass stacks two forwards in x."""
+        if self._pair is not None:
+            raise NotImplementedError("audio_dit_blocks in the CFG pair pass: the audio adapter takes one forward's rows (set cfg_pair=False)")
+        if self.parallel_attention is not None:
+            raise NotImplementedError("audio_dit_blocks with Ulysses or ring attention (parallel_attn_type): there is no multi-GPU driver for the audio model")
 
     def infer_block(self, weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context):
         shift_msa, scale_msa, gate_msa, c_shift_msa, c_scale_msa, c_gate_msa = self.infer_modulation(weights.compute_phases[0], embed0)
@@ -356,6 +372,8 @@ class WanTransformerInfer:
         # norm1 has no affine (transformer_weights.py:127-129); quantised operator classes get n1 quantised once for q, k and v
         n1, mmkw = _ln_then_mm_input(weights.self_attn_q, x, scale=scale_msa, shift=shift_msa, eps=weights.norm1.eps)
         grid = tuple(int(g) for g in grid_sizes[0].tolist())
+        if self.audio_sr:  # the audio model's RoPE grid (utils.py:23-37 compute_freqs_audio): one more frame, for the reference-image tokens behind the video's
+            grid = (grid[0] + 1,) + grid[1:]
         if freqs.is_complex():  # driven by the reference's WanPreInfer: complex128 [1024, 64] (pre_infer.py:12-19)
             if self._rope_cs is None or self._rope_cs.device != x.device:
                 self._rope_cs = torch.stack([freqs.real, freqs.imag], dim=-1).to(torch.float32).contiguous().to(x.device)
@@ -603,7 +621,7 @@ class WanTransformerInferTeaCaching(WanTransformerInfer):
         tag = "even" if self.infer_conditional else "odd"
         if records[index]:
             ori_x = x.clone()
-            x = super().infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context)
+            x = super().infer(weights, grid_sizes, embed, x, embed0, seq_lens, freqs, context, audio_dit_blocks)
             if self._minus_one is None or self._minus_one.device != x.device:
                 self._minus_one = torch.full((x.shape[1],), -1.0, dtype=x.dtype, device=x.device)
             res = x.clone()
