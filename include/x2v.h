@@ -798,6 +798,32 @@ int x2v_gemm_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const v
 /* The tile x2v_gemm_f16 launches for (M, N): 0 = 128 x 64, 1 = 64 x 64, 2 = 64 x 32, 3 = 64 x 16 (host arithmetic; no reference counterpart). */
 int x2v_gemm_f16_tile_choice(int64_t M, int N);
 
+/* y[M,N] = epi(x[M,K] . W[N,K]^T + bias) in fp16 with fp32 accumulation for 128 <= M <= 512 or so (1 <= M <= 4096 is admitted; M = 0 launches nothing):
+ * the LDS-tiled form with a K split, for the row counts at which x2v_gemm_f16 re-reads x from L2 and the 256x256 GEMMs leave most of the chip idle — the
+ * Linears of a Llama text-tower layer at 351 tokens.  Workgroup tile 128 x 128, K tiles of 64; where the output tiles do not fill the compute units, K is
+ * cut into `splits` contiguous ranges of whole K tiles (the first ranges take the extra tile), each workgroup leaves its fp32 tile in `workspace`, and the
+ * workgroup that arrives last at a tile sums the ranges in the order 0 .. splits - 1, applies the epilogue and stores y.  No workgroup waits for another;
+ * the same operands give the same bits on every run.  The summation order is not x2v_gemm_f16's: the two entries agree to rounding, not bit for bit.
+ * Epilogues: X2V_EPI16_NONE, _RESIDUAL (y may alias resid) and _SWIGLU (W has 2N rows, bias NULL) with x2v_gemm_f16's rounding points; any other code is
+ * X2V_E_ARG.  K % 32 == 0, W's row count (N, or 2N with SWIGLU) % 8 == 0, ldx, ldw < 2^22; otherwise x2v_gemm_f16's argument checks and error codes.
+ * splits: 0 = the library's choice for the current device (x2v_gemm_mid_choice with its compute-unit count), else 1 .. the number of K tiles (X2V_E_ARG
+ * beyond it).  workspace: device memory of at least x2v_gemm_mid_workspace_bytes(...) bytes, 16-byte aligned, ZEROED ONCE by whoever allocates it; its
+ * first 4096 bytes are 1024 counters, one per output tile whatever the shape, which every launch leaves at zero, so launches of any shapes that follow
+ * each other on one stream share it without clearing it (launches on two streams at once need one each).  Too small, or NULL, with more than one split, or
+ * more than 1024 output tiles with more than one split: X2V_E_ARG.  With one split it is not touched and may be NULL.  No reference counterpart (the
+ * reference calls nn.Linear). */
+int x2v_gemm_mid_f16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int64_t M, int N, int K, int epilogue,
+                     const void* resid, int64_t ldr, int splits, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Bytes of workspace x2v_gemm_mid_f16 needs for W of N rows (2N with SWIGLU) and `splits` ranges (0: the library's choice, as above): 0 for one split, else
+ * 4096 bytes of counters + ceil(M/128) ceil(N/128) tiles x splits x 64 KiB (host arithmetic). */
+int64_t x2v_gemm_mid_workspace_bytes(int64_t M, int N, int K, int splits);
+
+/* What x2v_gemm_mid_f16 launches for W of N rows on a device of cu_count compute units: low byte = tile form (1 = 128 x 128, the only one), bits 8.. = the
+ * number of K splits — 1 where the output tiles number cu_count or more, else ceil(cu_count / tiles), at most 16 and at most half the K tiles.  Negative =
+ * X2V_E_SHAPE.  Host arithmetic. */
+int x2v_gemm_mid_choice(int64_t M, int N, int K, int cu_count);
+
 /* out[b*S + i, h*80 : h*80 + 80] = softmax(scale * q_i . k_j) v_j over the S keys of image b, non-causal, head dim 80 — replaces
  * attention(q, k, v, attention_type="torch_sdpa") of SelfAttention.forward (model.py:82-86).  qkv is the to_qkv output [batch*S, >= 3*H*80] read in
  * place: q | k | v at columns 0, H*80, 2*H*80 of a row.  1 <= S <= 272; scale = 0 means 80^-1/2.  fp32 softmax statistics. */

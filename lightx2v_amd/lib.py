@@ -114,6 +114,9 @@ PROTOTYPES = {
     "x2v_vae_tile_compose_f32": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_gemm_f16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p],
     "x2v_gemm_f16_tile_choice": [_i64, _i32],
+    "x2v_gemm_mid_f16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _i32, _c_void_p, _i64, _c_void_p],
+    "x2v_gemm_mid_workspace_bytes": [_i64, _i32, _i32, _i32],
+    "x2v_gemm_mid_choice": [_i64, _i32, _i32, _i32],
     "x2v_attn_f16_d80": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
     "x2v_layernorm_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _f32, _c_void_p],
     "x2v_clip_embed_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
@@ -135,7 +138,7 @@ PROTOTYPES = {
                         _c_void_p],
     "x2v_taehv_clamp_bf16": [_c_void_p, _i32, _i64, _i64, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p],
 }
-_RESTYPES = {"x2v_last_error": ctypes.c_char_p, "x2v_version": ctypes.c_char_p}
+_RESTYPES = {"x2v_last_error": ctypes.c_char_p, "x2v_version": ctypes.c_char_p, "x2v_gemm_mid_workspace_bytes": _i64}
 
 
 class X2VError(RuntimeError):
@@ -1628,6 +1631,49 @@ def gemm_f16_tile_choice(M, N):
     t = _lib.x2v_gemm_f16_tile_choice(M, N)
     _check(min(t, 0), "gemm_f16_tile_choice")
     return ((128, 64), (64, 64), (64, 32), (64, 16))[t]
+
+
+_mid_workspaces = {}  # device index -> the zero-initialised workspace of gemm_mid_f16 (int32 words: the tile counters first)
+
+
+def gemm_mid_workspace(device, nbytes=0):
+    """The device's workspace of gemm_mid_f16, at least `nbytes` long: allocated zeroed, grown on demand (a new zeroed one), and shared by every call on
+    the device — x2v_gemm_mid_f16 leaves the counter words at its start zero, so launches that follow each other on one stream need no clearing."""
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    ws = _mid_workspaces.get(idx)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _mid_workspaces[idx] = torch.zeros((max(int(nbytes), 256) + 3) // 4, dtype=torch.int32, device=torch.device("cuda", idx))
+    return ws
+
+
+def gemm_mid_f16(x, weight_nk, bias=None, epilogue=EPI16_NONE, resid=None, out=None, splits=0):
+    """x2v_gemm_mid_f16: gemm_f16's product on the LDS-tiled, K-split kernel for 128 <= M <= 512 or so (1 <= M <= 4096); EPI16_NONE, _RESIDUAL and _SWIGLU;
+    K % 32 == 0, weight rows % 8 == 0.  splits = 0: the library's choice (gemm_mid_choice); the partial sums live in gemm_mid_workspace."""
+    x, w = _f16rows(x, "gemm_mid_f16 x"), _f16rows(weight_nk, "gemm_mid_f16 weight")
+    M, K = x.shape
+    if epilogue == EPI16_SWIGLU and w.shape[0] % 2:
+        raise X2VError(f"gemm_mid_f16: the SwiGLU epilogue needs an even number of weight rows, got {w.shape[0]}")
+    N = w.shape[0] // 2 if epilogue == EPI16_SWIGLU else w.shape[0]
+    if w.shape[1] != K:
+        raise X2VError(f"gemm_mid_f16: x {tuple(x.shape)} and weight {tuple(w.shape)} disagree on K")
+    bias = _vec(bias, "gemm_mid_f16 bias", N, dtype=torch.float16)
+    out = torch.empty((M, N), dtype=torch.float16, device=x.device) if out is None else _f16rows(out, "gemm_mid_f16 out")
+    if out.shape != (M, N) or (resid is not None and _f16rows(resid, "gemm_mid_f16 resid").shape != (M, N)):
+        raise X2VError(f"gemm_mid_f16: out / resid must be [{M}, {N}]")
+    init()
+    nbytes = _lib.x2v_gemm_mid_workspace_bytes(M, w.shape[0], K, splits)
+    ws = gemm_mid_workspace(x.device, nbytes) if nbytes else None
+    _check(_lib.x2v_gemm_mid_f16(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, epilogue, _p(resid), 0 if resid is None else resid.stride(0),
+                                 splits, _p(ws), 0 if ws is None else ws.numel() * 4, _stream()), "gemm_mid_f16")
+    return out
+
+
+def gemm_mid_choice(M, N, K, cu_count=256):
+    """x2v_gemm_mid_choice: ((rows, columns) of the workgroup tile, K splits) x2v_gemm_mid_f16 takes for W of N rows on cu_count compute units — host arithmetic."""
+    c = _lib.x2v_gemm_mid_choice(M, N, K, cu_count)
+    _check(min(c, 0), "gemm_mid_choice")
+    return {1: (128, 128)}[c & 0xFF], c >> 8
 
 
 def attention_f16_d80(qkv, batch, num_heads, out=None, scale=0.0):

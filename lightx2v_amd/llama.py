@@ -10,7 +10,8 @@ used.  The prompt is right-padded and the attention is causal, so a valid row ne
 [1, L - crop_start, D] with the rows from n - crop_start on ZERO (the reference leaves what the model computed on pad tokens there; its consumers read those
 rows only through the mask, hunyuan/infer/pre_infer.py:46-47,85-86,98-101).  Per layer 7 launches on one stream — RMSNorm, fused q | k | v GEMM, causal
 grouped-query attention with the rotary embedding inside, o GEMM + residual, RMSNorm, gate | up GEMM with the SwiGLU epilogue, down GEMM + residual; one
-workspace, sized to the largest n seen.  fp16 activations and weights, fp32 accumulation and statistics, as the reference's fp16 model.  Where it rounds
+workspace, sized to the largest n seen.  With `mid_gemm` (the default) a pass of 128 packed rows or more takes the four GEMMs through x2v_gemm_mid_f16
+(csrc/gemm_mid.h: LDS tiles, split K), with the same rounding points and another summation order.  fp16 activations and weights, fp32 accumulation and statistics, as the reference's fp16 model.  Where it rounds
 differently: the norm rounds once (LlamaRMSNorm rounds x * rsqrt(...) to fp16 and the weight product again), q and k are rotated in fp32 and rounded once
 (apply_rotary_pos_emb rounds both products and their sum, with cos / sin themselves rounded to fp16), scores and probabilities stay fp32 up to the PV operand
 (sdpa / eager round the scores to fp16), SiLU and its product are fp32 on the two fp16 Linear outputs.  The LLaVA tower of i2v, quantised Linears and
@@ -26,6 +27,8 @@ from .packed import MAX_PLANS, PackedTower  # noqa: F401
 
 HEAD_DIM = 128  # the rotary form of x2v_attn_f16_causal
 MAX_LEN = lib.ATTN_CAUSAL_MAX_LEN
+MID_GEMM_ROWS = 128  # packed rows from which mid_gemm takes x2v_gemm_mid_f16
+MID_GEMM_DEFAULT = True  # DESIGN §4.9, profiles/gemm_mid_bench.json: the chain at 351 tokens 31.6 -> 14.6 ms, spread of repeated medians 0.2 %
 
 
 def load_hf_dir(path):
@@ -90,8 +93,9 @@ class TextEncoderHFLlamaModel(PackedTower):
     """Same constructor, attributes, `infer`, `to_cuda` and `to_cpu` as the reference's TextEncoderHFLlamaModel; `model_path` may also be a
     (name → tensor dict, dims dict) pair (dims: the keys of synth.LLAMA_DIMS)."""
 
-    def __init__(self, model_path, device):
-        self.device, self.model_path = torch.device(device), model_path
+    def __init__(self, model_path, device, mid_gemm=MID_GEMM_DEFAULT):
+        """mid_gemm: the four Linears of a layer go through x2v_gemm_mid_f16 (LDS tiles, split K) whenever a pass has MID_GEMM_ROWS packed rows or more."""
+        self.device, self.model_path, self.mid_gemm = torch.device(device), model_path, bool(mid_gemm)
         self.init()
         if isinstance(model_path, (tuple, list)):
             sd, dims = model_path[0], dict(model_path[1])
@@ -150,6 +154,15 @@ class TextEncoderHFLlamaModel(PackedTower):
                 down=w(p + "mlp.down_proj.weight", (self.dim, self.dim_ffn))))
         self.rope = tuple(t.to(self.device) for t in rope_tables(self.rope_theta))
         self._init_plumbing()
+        self._mid_ws = None
+
+    def _mid_workspace(self, nbytes):
+        """The zero-initialised workspace of the plans' x2v_gemm_mid_f16 launches (one stream at a time, so they share it), grown to the largest need seen;
+        growing it drops the plans, which hold its pointer."""
+        if self._mid_ws is None or self._mid_ws.numel() * 4 < nbytes:
+            self._plans.clear()
+            self._mid_ws = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
+        return self._mid_ws
 
     # ---- plumbing (packed.PackedTower: one workspace, the plan cache) --------------------------------------------------
     def weight_bytes(self):
@@ -170,8 +183,15 @@ class TextEncoderHFLlamaModel(PackedTower):
         def norm(wt):
             plan.append((L.x2v_rmsnorm_f16, (p["x"], D, wt.data_ptr(), p["h"], D, M, D, eps, stream)))
 
+        mid = self.mid_gemm and M >= MID_GEMM_ROWS
+        ws = ws_bytes = None
+        if mid:  # one workspace for the largest of the layer's four launches (the library's split choice for each)
+            ws_bytes = max(L.x2v_gemm_mid_workspace_bytes(M, b_rows, k, 0) for b_rows, k in ((Q, D), (D, A), (2 * F, D), (D, F)))
+            ws = self._mid_workspace(ws_bytes).data_ptr() if ws_bytes else None
+
         def gemm(x, wt, y, n, k, epi, ldy, resid=None):
-            plan.append((L.x2v_gemm_f16, (p[x], k, wt.data_ptr(), k, None, p[y], ldy, M, n, k, epi, None if resid is None else p[resid], 0 if resid is None else ldy, stream)))
+            args = (p[x], k, wt.data_ptr(), k, None, p[y], ldy, M, n, k, epi, None if resid is None else p[resid], 0 if resid is None else ldy)
+            plan.append((L.x2v_gemm_mid_f16, (*args, 0, ws, ws_bytes or 0, stream)) if mid else (L.x2v_gemm_f16, (*args, stream)))
 
         for b in self.blocks:
             norm(b["n1"])

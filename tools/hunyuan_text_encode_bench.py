@@ -53,13 +53,147 @@ def hf_models(sd_l, dims_l, sd_c, dims_c):
     return ll.eval().requires_grad_(False), cl.eval().requires_grad_(False)
 
 
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def hf_llama(sd, dims):
+    """transformers' LlamaModel alone, as hf_models builds it, or None."""
+    try:
+        from transformers import LlamaConfig, LlamaModel
+    except Exception:
+        return None
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float16)
+    try:
+        with torch.device("cuda"):
+            ll = LlamaModel(LlamaConfig(vocab_size=dims["vocab"], hidden_size=dims["dim"], intermediate_size=dims["ffn"], num_hidden_layers=dims["layers"],
+                                        num_attention_heads=dims["heads"], num_key_value_heads=dims["kv_heads"], head_dim=dims["head_dim"], rms_norm_eps=dims["eps"],
+                                        rope_theta=dims["rope_theta"], max_position_embeddings=8192, hidden_act="silu", pad_token_id=None))
+    finally:
+        torch.set_default_dtype(old)
+    ll.load_state_dict(sd, strict=True)
+    return ll.eval().requires_grad_(False)
+
+
+def gemm_mid_mode(a):
+    """--gemm-mid.  Part one: the four Linears of a Llama layer at M = 351 and M = 130 through x2v_gemm_f16, x2v_gemm_mid_f16 and torch's fp16 matmul,
+    interleaved A-B-A-B, each sample `--inner` launches between two device events, medians of `--rounds`; the whole block is repeated `--repeats` times
+    and the spread of the repeated medians is reported.  Part two: the launch chain of infer_ids' forward (forward_packed on a filled workspace) and
+    infer_ids itself with mid_gemm off and on, interleaved, repeated the same way, next to the plain-PyTorch and transformers towers."""
+    from lightx2v_amd import lib, llama, synth
+    from tests import llama_restatement as RL
+
+    lib.init(0)
+    res = {"device": torch.cuda.get_device_name(0), "box_calibration": {"kernel": "v_mfma_f32_16x16x32_bf16 (x2v_mfma_probe_bf16)", "mfma_probe_tflops_before": lib.mfma_probe(500)},
+           "method": f"A-B-A-B in one process, device events, {a.inner} launches per sample, median of {a.rounds}, {a.repeats} repeats of every median"}
+    D, A, Q, F = 4096, 4096, 6144, 14336
+    g = torch.Generator().manual_seed(1)
+    products = {"qkv": (Q, D, lib.EPI16_NONE), "o": (D, A, lib.EPI16_RESIDUAL), "gate_up_swiglu": (F, D, lib.EPI16_SWIGLU), "down": (D, F, lib.EPI16_RESIDUAL)}
+    res["products"] = {}
+    for name, (N, K, epi) in products.items():
+        w = (torch.randn(2 * N if epi == lib.EPI16_SWIGLU else N, K, generator=g) / K**0.5).half().cuda()
+        for M in (351, 130):
+            x, r = torch.randn(M, K, generator=g).half().cuda(), torch.randn(M, N, generator=g).half().cuda()
+            out, resid = torch.empty(M, N, dtype=torch.float16, device="cuda"), (r if epi == lib.EPI16_RESIDUAL else None)
+            wt = w.t()
+            arms = {"gemm_f16": lambda: lib.gemm_f16(x, w, None, epilogue=epi, resid=resid, out=out),
+                    "gemm_mid_f16": lambda: lib.gemm_mid_f16(x, w, None, epilogue=epi, resid=resid, out=out),
+                    "torch_matmul_fp16_no_epilogue": lambda: torch.matmul(x, wt)}
+            for fn in arms.values():
+                fn()
+                fn()
+            # results must not change: the two entries on the same operands (out of place), elements further apart than one fp16 ulp
+            y_old, y_mid = (f(x, w, None, epilogue=epi, resid=resid).double() for f in (lib.gemm_f16, lib.gemm_mid_f16))
+            apart = ((y_old - y_mid).abs() > 2.0**-10 * y_old.abs() + 2.0**-23).double().mean().item()
+            meds = {k: [] for k in arms}
+            for _ in range(a.repeats):
+                ms = {k: [] for k in arms}
+                for _ in range(a.rounds):
+                    for k, fn in arms.items():
+                        ms[k].append(timed_ms(lambda: [fn() for _ in range(a.inner)]) / a.inner)
+                for k in arms:
+                    meds[k].append(median(ms[k]))
+            flop = 2.0 * M * w.shape[0] * K
+            (tile, splits), mid, old = lib.gemm_mid_choice(M, w.shape[0], K), median(meds["gemm_mid_f16"]), median(meds["gemm_f16"])
+            res["products"][f"{name}_M{M}"] = {"M": M, "W_rows": w.shape[0], "K": K, "tile": tile, "splits": splits, "ms_repeated_medians": meds,
+                                               "ms": {k: median(v) for k, v in meds.items()}, "tflops": {k: flop / median(v) / 1e9 for k, v in meds.items()},
+                                               "share_of_elements_over_1ulp_from_gemm_f16": apart, "gemm_f16_over_gemm_mid_f16": old / mid,
+"gemm_mid_f16_over_torch": mid / median(meds["torch_matmul_fp16_no_epilogue"]),
+                                               "spread_of_medians": {k: (max(v) - min(v)) / median(v) for k, v in meds.items()}}
+        del w
+    dims = dict(synth.LLAMA_DIMS["llama3-8b"], layers=a.layers)
+    sd = synth.synth_llama_weights(dims, seed=0, device="cuda")
+    models = {"mid_gemm_off": llama.TextEncoderHFLlamaModel((sd, dims), "cuda", mid_gemm=False), "mid_gemm_on": llama.TextEncoderHFLlamaModel((sd, dims), "cuda", mid_gemm=True)}
+    g = torch.Generator().manual_seed(4)
+    res["chain"] = {}
+    hf = None if a.no_transformers else hf_llama(sd, dims)
+    for n in (351, 130):
+        ids, mask = torch.zeros(1, 351, dtype=torch.long), torch.zeros(1, 351, dtype=torch.long)
+        ids[0, :n], mask[0, :n] = torch.randint(1, dims["vocab"], (n,), generator=g), 1
+        dev = (ids.cuda(), mask.cuda())
+        arms = {}
+        for k, m in models.items():
+            arms[f"infer_ids_{k}"] = lambda m=m: m.infer_ids(ids, mask)
+            arms[f"chain_{k}"] = lambda m=m: m.forward_packed((n,))
+        arms["torch_fp16_padded_351"] = lambda: RL.infer_ids(sd, dims, *dev, dtype=torch.float16, device="cuda", skip=2, crop_start=95)
+        if hf is not None:
+            arms["transformers_fp16_padded_351"] = lambda: hf(input_ids=dev[0], attention_mask=dev[1], output_hidden_states=True).hidden_states[-3][:, 95:]
+        with torch.no_grad():
+            for fn in arms.values():
+                fn()
+                fn()
+            same = torch.equal(models["mid_gemm_on"].infer_ids(ids, mask)[0], models["mid_gemm_on"].infer_ids(ids, mask)[0])
+            # results must not change.  At full depth the random-weight tower amplifies every rounding difference, so each path is held against the
+            # fp32 restatement next to the plain-PyTorch fp16 path, and the switch is compared at 2 layers (the depth of the GPU tests) as well
+            rel = lambda p, q: ((p.double() - q.double()).norm() / q.double().norm()).item()  # noqa: E731
+            on, off = (models[k].infer_ids(ids, mask)[0][0, : n - 95] for k in ("mid_gemm_on", "mid_gemm_off"))
+            truth, ref16 = (RL.infer_ids(sd, dims, *dev, dtype=t, device="cuda", skip=2, crop_start=95)[0][0, : n - 95] for t in (torch.float32, torch.float16))
+            d2 = dict(dims, layers=4)
+            on2, off2 = (llama.TextEncoderHFLlamaModel((sd, d2), "cuda", mid_gemm=s).infer_ids(ids, mask)[0][0, : n - 95] for s in (True, False))
+            truth2 = RL.infer_ids(sd, d2, *dev, dtype=torch.float32, device="cuda", skip=2, crop_start=95)[0][0, : n - 95]
+            parity = {"full_depth_vs_fp32": {"mid_gemm_on": rel(on, truth), "mid_gemm_off": rel(off, truth), "torch_fp16": rel(ref16, truth)},
+                      "full_depth_on_vs_off": rel(on, off), "full_depth_off_vs_torch_fp16": rel(off, ref16),
+                      "two_layers_vs_fp32": {"mid_gemm_on": rel(on2, truth2), "mid_gemm_off": rel(off2, truth2)}, "two_layers_on_vs_off": rel(on2, off2)}
+            del truth, ref16, on2, off2, truth2
+            meds = {k: [] for k in arms}
+            for _ in range(a.repeats):
+                ms = {k: [] for k in arms}
+                for _ in range(a.rounds):
+                    for k, fn in arms.items():
+                        ms[k].append(timed_ms(fn))
+                for k in arms:
+                    meds[k].append(median(ms[k]))
+        med = {k: median(v) for k, v in meds.items()}
+        spread = {k: (max(v) - min(v)) / median(v) for k, v in meds.items()}
+        gain = 1.0 - med["chain_mid_gemm_on"] / med["chain_mid_gemm_off"]
+        res["chain"][f"llama_{n}"] = {"ms_repeated_medians": meds, "ms": med, "spread_of_medians": spread, "chain_gain_of_mid_gemm": gain,
+                                      "chain_gain_exceeds_spread": gain > max(spread["chain_mid_gemm_on"], spread["chain_mid_gemm_off"]),
+                                      "mid_gemm_on_run_to_run_bit_equal": same, "rel_l2": parity,
+                                      "torch_fp16_over_hip": {k: med["torch_fp16_padded_351"] / med[f"infer_ids_{k}"] for k in models},
+                                      **({"transformers_fp16_over_hip": {k: med["transformers_fp16_padded_351"] / med[f"infer_ids_{k}"] for k in models}} if hf is not None else {})}
+    res["box_calibration"]["mfma_probe_tflops_after"] = lib.mfma_probe(500)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-transformers", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hunyuan_text_encode_bench.json"))
+    ap.add_argument("--gemm-mid", action="store_true", help="time x2v_gemm_mid_f16 against x2v_gemm_f16: the four Llama products, then the chain with mid_gemm off and on")
+    ap.add_argument("--inner", type=int, default=20, help="--gemm-mid: launches per timed sample of a single product")
+    ap.add_argument("--repeats", type=int, default=3, help="--gemm-mid: how often every median is taken again (their spread gates the driver's default)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "gemm_mid_bench.json" if a.gemm_mid else "hunyuan_text_encode_bench.json")
+    if a.gemm_mid:
+        return gemm_mid_mode(a)
     from lightx2v_amd import clip_text, lib, llama, synth
     from tests import clip_text_restatement as RC
     from tests import llama_restatement as RL
