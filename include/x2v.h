@@ -743,6 +743,23 @@ int x2v_groupnorm_affine_f32(const float* x, int64_t npix, int C, int G, const f
  * UNetMidBlockCausal3D.forward :629-634).  scale > 0 (the row maximum is taken before scaling; anything else, NaN included, is X2V_E_ARG). */
 int x2v_softmax_rows_causal_f32(float* s, int64_t ld, int64_t M, int N, float scale, int hw, int n_keys, void* stream);
 
+/* Fused fp16 attention of one head of width C over n = frames * hw tokens under the same frame-causal prefix (query row i attends keys
+ * j < (i / hw + 1) * hw) — the mid-block attention of the HunyuanVideo VAE without a score matrix (csrc/vae_attn.hip).  C = 512 or 128, else X2V_E_SHAPE;
+ * n <= 2^20.  Arithmetic contract:
+ *   1. q, k, v are rounded to fp16 once, round to nearest even (x2v_vae_attn_prep_f16);
+ *   2. a score is the fp32 dot product of the fp16 rows (v_mfma_f32_16x16x32_f16) times scale * log2(e) in fp32;
+ *   3. the softmax runs online in base 2 over tiles of 64 keys with its state in fp32: p = 2^(score - m), where a row's reference maximum m follows its running
+ *      maximum whenever that has grown by more than 8 (so p <= 2^8, inside fp16's range at full relative precision), and the accumulated output and
+ *      row sum are rescaled by 2^(m_old - m_new) at each such move; the row sum adds the fp32 p, before it is rounded;
+ *   4. p is rounded to fp16 for P . V, accumulated in fp32;
+ *   5. out[i] = accumulator / row sum, fp32 [n, C] with row stride ldo (floats, a multiple of 4);
+ *   6. masked positions are removed by selection (-inf for the maximum, 0 for p), never by adding a large negative number.
+ * x2v_vae_attn_prep_f16: one pass over the fp32 [n, 3 C] output of the fused q|k|v projection (row stride ld floats): writes fp16 q16 [n][C],
+ * k16 [64 ceil(n / 64)][C] with zero rows from n on, and V transposed into key tiles vt16 [ceil(n / 64)][C][64] with zero keys from n on — every byte
+ * of k16 and vt16 is written, the caller clears nothing.  x2v_vae_attn_f16 takes exactly these three buffers. */
+int x2v_vae_attn_prep_f16(const float* qkv, int64_t ld, void* q16, void* k16, void* vt16, int64_t n, int C, void* stream);
+int x2v_vae_attn_f16(const void* q16, const void* k16, const void* vt16, float* out, int64_t ldo, int frames, int hw, int C, float scale, void* stream);
+
 /* Linear cross-fade of overlapping tiles along one axis, tensors viewed as [outer][axis][inner]:
  * b[idx] = a[na-extent+idx]*(1-idx/extent) + b[idx]*(idx/extent), idx < extent — blend_v / blend_h / blend_t
  * (autoencoder_kl_causal_3d.py:347-364). */

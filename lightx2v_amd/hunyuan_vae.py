@@ -14,7 +14,8 @@ runs this VAE in fp16; fp32 is the more accurate side of that), channels-last, o
     kernel x2v_vae_prep_ex_f32 applies together with SiLU and the nearest upsampling (time factor 2 leaves the first frame
     single) while writing the next convolution's buffer — one pass per layer input;
   * the mid block's frame-causal attention over (f h w) tokens = fused q|k|v GEMM, QK^T GEMM, prefix-masked row softmax,
-    PV GEMM, output projection with the residual in its epilogue (1x1 taps of the same convolution kernel);
+    PV GEMM, output projection with the residual in its epilogue (1x1 taps of the same convolution kernel); with attn16=True the three
+    in the middle are one fused fp16 online-softmax kernel behind an fp16 preparation pass (csrc/vae_attn.hip), without the score matrix;
   * tile blending = x2v_blend_axis_f32; the final x/2+0.5, clamp(0,1) = one pass of the producer kernel.
 Torch is used for allocation, tile slicing / cropping / concatenation and layout changes — memory plumbing only.
 """
@@ -33,8 +34,12 @@ def _cl(w):
 class DecoderCausal3D:
     """reference: autoencoder_kl_causal_3d/vae.py:133-283."""
 
-    def __init__(self, sd, cfg, device, conv16=True):
+    def __init__(self, sd, cfg, device, conv16=True, attn16=False):
         self.cfg, self.device = cfg, device
+        # attn16: the mid-block attention as ONE fused fp16 kernel (lib.vae_attention16: fp16 q, k, v and p, fp32 softmax state and accumulation, no score
+        # matrix) in place of the fp32 QK^T / softmax / PV launches around an [npad, npad] tensor.  Off by default: no existing output changes.
+        self.attn16 = attn16
+        self.attn_ran = None  # "fused-fp16" / "fp32-scores": which mid-block attention the last forward took
         # 3x3x3 convolutions with Cin % 64 == 0 (all but conv_in) take fp16 operands when conv16 — the reference's precision for this VAE
         # (hunyuan_runner.py:40: dtype fp16); accumulation, bias, residual stream, GroupNorm statistics and the attention stay fp32
         self.conv16 = conv16
@@ -93,6 +98,9 @@ class DecoderCausal3D:
 
     def mid_attention(self, p, x):
         """reference: UNetMidBlockCausal3D.forward (:629-634) + diffusers' Attention (deprecated-attn-block form)."""
+        if self.attn16:
+            return self._mid_attention16(p, x)
+        self.attn_ran = "fp32-scores"
         t, h, w, c = x.shape
         n, hw = t * h * w, h * w
         npad = (n + 15) // 16 * 16  # the PV GEMM reduces over keys in 16-float slabs: pad the token axis with zero rows
@@ -114,6 +122,26 @@ class DecoderCausal3D:
         lib.vae_conv(o, (npad * c, npad * c, c), self.w[p + "to_out.0.weight"], out.view(1, 1, n, c), 1, 1, n, bias=self.w[p + "to_out.0.bias"], resid=x.view(1, 1, n, c))
         return out
 
+    def _mid_attention16(self, p, x):
+        """mid_attention with attn16: GroupNorm affine, q|k|v GEMM, fp16 preparation pass, fused attention, output projection with the residual."""
+        t, h, w, c = x.shape
+        n, hw = t * h * w, h * w
+        mul, add = self._gn(p + "group_norm", x)
+        y = torch.empty((1, 1, n, c), dtype=torch.float32, device=x.device)
+        lib.vae_prep_ex(x.reshape(1, 1, n, c), y, (n * c, n * c), mul=mul, add=add)
+        qkv = torch.empty((1, 1, n, 3 * c), dtype=torch.float32, device=x.device)
+        lib.vae_conv(y, (n * c, n * c, c), self.w[p + "qkv.weight"], qkv, 1, 1, n, bias=self.w[p + "qkv.bias"])
+        key = ("attn16", n, c)
+        bufs = self._bufs.get(key)
+        if bufs is None:
+            bufs = self._bufs[key] = lib.vae_attention16_buffers(n, c, x.device)
+        o = torch.empty((1, 1, n, c), dtype=torch.float32, device=x.device)
+        lib.vae_attention16(qkv.view(n, 3 * c), n, c, hw, 1.0 / math.sqrt(c), o.view(n, c), buffers=bufs)
+        self.attn_ran = "fused-fp16"
+        out = torch.empty_like(x)
+        lib.vae_conv(o, (n * c, n * c, c), self.w[p + "to_out.0.weight"], out.view(1, 1, n, c), 1, 1, n, bias=self.w[p + "to_out.0.bias"], resid=x.view(1, 1, n, c))
+        return out
+
     def forward(self, z):
         """z [T, h, w, 16] (after post_quant_conv) → [4(T-1)+1, 8h, 8w, 3]."""
         x = self._conv3("decoder.conv_in.conv", z)
@@ -131,13 +159,13 @@ class DecoderCausal3D:
 class AutoencoderKLCausal3D:
     """reference: autoencoder_kl_causal_3d.py:58-518 (decode side, tiling enabled as model.py:38 always does)."""
 
-    def __init__(self, sd, cfg=None, device="cuda", conv16=True, group=None):
+    def __init__(self, sd, cfg=None, device="cuda", conv16=True, group=None, attn16=False):
         """group: a torch.distributed process group (e.g. the sequence-parallel group of the denoise loop) — the independent tiles of
         the tiled decode are then shared out over its ranks (not in the reference, whose `parallel_vae` covers the Wan VAE only)."""
         self.cfg = cfg or synth.HUNYUAN_VAE_CFG
         self.device = device
         self.group = group
-        self.decoder = DecoderCausal3D(sd, self.cfg, device, conv16=conv16)
+        self.decoder = DecoderCausal3D(sd, self.cfg, device, conv16=conv16, attn16=attn16)
         zc = self.cfg["latent_channels"]
         self.pq_w = sd["post_quant_conv.weight"].to(device=device, dtype=torch.float32).reshape(zc, zc).contiguous()
         self.pq_b = sd["post_quant_conv.bias"].to(device=device, dtype=torch.float32).contiguous()
@@ -262,10 +290,11 @@ class AutoencoderKLCausal3D:
 class VideoEncoderKLCausal3DModel:
     """reference: autoencoder_kl_causal_3d/model.py:6-44 (decode side)."""
 
-    def __init__(self, sd, cfg=None, device="cuda", conv16=True, group=None):
+    def __init__(self, sd, cfg=None, device="cuda", conv16=True, group=None, attn16=False):
         """conv16 (default): fp16 operands for the 3x3x3 convolutions — the reference's precision for this VAE; False: everything fp32.
+        attn16: the mid-block attention as the fused fp16 kernel (see DecoderCausal3D); default off.
         group: process group whose ranks share the tiles of the tiled decode (see AutoencoderKLCausal3D)."""
-        self.model = AutoencoderKLCausal3D(sd, cfg, device, conv16=conv16, group=group)
+        self.model = AutoencoderKLCausal3D(sd, cfg, device, conv16=conv16, group=group, attn16=attn16)
         self.device = device
 
     def decode(self, latents, generator=None, config=None):

@@ -133,6 +133,8 @@ PROTOTYPES = {
     "x2v_vae_replicate_border_f32": [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p],
     "x2v_groupnorm_affine_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _f32, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "x2v_softmax_rows_causal_f32": [_c_void_p, _i64, _i64, _i32, _f32, _i32, _i32, _c_void_p],
+    "x2v_vae_attn_prep_f16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _c_void_p],
+    "x2v_vae_attn_f16": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
     "x2v_blend_axis_f32": [_c_void_p, _c_void_p, _i64, _i32, _i32, _i64, _i64, _i64, _i32, _c_void_p],
     "x2v_conv2d_bf16": [_c_void_p, _c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                         _c_void_p],
@@ -1523,6 +1525,36 @@ def softmax_rows_causal_(s, scale, hw, n_keys=None):
     init()
     _check(_lib.x2v_softmax_rows_causal_f32(_p(s), s.stride(0), M, N, float(scale), hw, N if n_keys is None else n_keys, _stream()), "softmax_rows_causal")
     return s
+
+
+def vae_attention16_buffers(n, C, device):
+    """The fp16 operands of vae_attention16 for n tokens of width C: (q [n, C], k [64 nt, C], vt [nt, C, 64]), nt = ceil(n / 64).  Not initialised:
+    x2v_vae_attn_prep_f16 writes every byte the attention kernel reads."""
+    nt = (n + 63) // 64
+    return (torch.empty((n, C), dtype=torch.float16, device=device), torch.empty((64 * nt, C), dtype=torch.float16, device=device),
+            torch.empty((nt, C, 64), dtype=torch.float16, device=device))
+
+
+def vae_attention16(qkv, n, C, hw, scale, out, buffers=None):
+    """Fused fp16 frame-causal attention of one head of width C (x2v_vae_attn_prep_f16 + x2v_vae_attn_f16): qkv fp32 [>= n, 3 C] (the fused q|k|v
+    projection, any row stride), n = frames * hw tokens, out fp32 [>= n, >= C] (any row stride).  buffers: vae_attention16_buffers(n, C, device) to reuse."""
+    _dev_view(qkv, "vae_attention16 qkv", (torch.float32,))
+    _dev_view(out, "vae_attention16 out", (torch.float32,))
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[0] < n or qkv.shape[1] != 3 * C:
+        raise X2VError(f"vae_attention16: qkv must be fp32 [>= {n}, {3 * C}] with unit inner stride, got {tuple(qkv.shape)} strides {qkv.stride()}")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n or out.shape[1] < C:
+        raise X2VError(f"vae_attention16: out must be fp32 [>= {n}, >= {C}] with unit inner stride, got {tuple(out.shape)} strides {out.stride()}")
+    if hw <= 0 or n <= 0 or n % hw:
+        raise X2VError(f"vae_attention16: n={n} tokens are not whole frames of hw={hw}")
+    q16, k16, vt16 = vae_attention16_buffers(n, C, qkv.device) if buffers is None else buffers
+    nt = (n + 63) // 64
+    for t, shape in ((q16, (n, C)), (k16, (64 * nt, C)), (vt16, (nt, C, 64))):
+        if t.dtype != torch.float16 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise X2VError(f"vae_attention16: buffers must be the contiguous CUDA float16 tensors of vae_attention16_buffers({n}, {C}), got {tuple(t.shape)} for {shape}")
+    init()
+    _check(_lib.x2v_vae_attn_prep_f16(_p(qkv), qkv.stride(0), _p(q16), _p(k16), _p(vt16), n, C, _stream()), "vae_attn_prep_f16")
+    _check(_lib.x2v_vae_attn_f16(_p(q16), _p(k16), _p(vt16), _p(out), out.stride(0), n // hw, hw, C, float(scale), _stream()), "vae_attn_f16")
+    return out
 
 
 def blend_axis_(a, b, axis, extent):
