@@ -410,6 +410,30 @@ int x2v_gemm_fp8_blocked(const void* xq, int64_t ldx, int x_kblock, int64_t x_kb
                          const void* bias, void* y, int64_t ldy, int y_nblock, int64_t y_nblock_stride, int64_t M, int N, int K, int epilogue, const void* resid,
                          int64_t ldr, const void* gate, void* stream);
 
+/* ---- fp8 block-128: the reference's W-fp8-block128-sym-A-fp8-channel-group128-sym-dynamic-Deepgemm[-ActSgl] operators (mm_weight.py:418-494):
+ * e4m3fn weights with one fp32 scale per 128 x 128 block (weight load :203-216, per_block_cast_to_fp8 :218-230, restated in torch by the operator
+ * class), e4m3fn activations with one fp32 scale per token and 128 K elements, quantised per call (gemm_b128.hip). */
+
+/* Activation quantiser, act_quant_fp8_perchannelgroup128_sym_deepgemm (mm_weight.py:251-256) bit for bit, every step one correctly rounded fp32
+ * operation (denormals kept), per row m and group g of 128 K elements:
+ *   a = max(amax(|x[m, 128 g .. 128 g + 127]|), 1e-4f),  r = (1.0f / a) * 448.0f,  code = e4m3fn_rne(float(x) * r),  scale = a / 448.0f
+ * r has two roundings on purpose: torch evaluates the reference's `448.0 / tensor` as tensor.reciprocal() * 448.0 on every device, and this is
+ * that expression, not 448.0f / a (they differ in the last bit for about a quarter of all a).
+ * x bf16 [M, K] (ldx % 8 == 0, 16-byte aligned), K % 128 == 0; xq [M, K] bytes (ldq % 8 == 0, 8-byte aligned rows); sx fp32 K-GROUP-MAJOR:
+ * the scale of (m, g) at sx[g * lds + m], lds >= M — the layout x2v_gemm_fp8_block128 reads (and DeepGEMM asks for). */
+int x2v_quant_fp8_group128(const void* x, int64_t ldx, void* xq, int64_t ldq, float* sx, int64_t lds, int64_t M, int K, void* stream);
+
+/* y[m, n] = epi( sum_g (sx[g * lds + m] * sw[(n / 128) * ldsw + g]) * P_g[m, n] + bias[n] ) -> bf16,  P_g = sum over k in [128 g, 128 g + 128) of
+ * xq[m, k] * wq[n, k] — replaces deep_gemm.gemm_fp8_fp8_bf16_nt (mm_weight.py:418-494).  The products of e4m3fn codes are exact; a group's 128 of them
+ * are accumulated in fp32 on the matrix pipe (v_mfma_scale_f32_16x16x128_f8f6f4, unit scales, zero C); s = sx * sw is one fp32 multiplication; the
+ * groups are summed in ascending g, acc = fma(s, P_g, acc) in fp32, starting from 0.  Epilogues X2V_EPI_*: statement order and rounding points of
+ * x2v_gemm_fp8 (the bias and activation step is the same code).  K % 128 == 0, N % 8 == 0, any M >= 0; xq [M, K] and wq [N, K] e4m3fn with
+ * ldx, ldw >= K, multiples of 16 and below 16 MiB, 16-byte aligned; sx as written by x2v_quant_fp8_group128 (lds >= M, (K / 128) * lds * 4 < 2^31);
+ * sw fp32 [ceil(N / 128), K / 128] with row stride ldsw >= K / 128; y, bias, resid, gate as x2v_gemm_fp8.  One kernel body for every M (128 x 256
+ * output tiles, masked tails). */
+int x2v_gemm_fp8_block128(const void* xq, int64_t ldx, const float* sx, int64_t lds, const void* wq, int64_t ldw, const float* sw, int64_t ldsw, const void* bias,
+                          void* y, int64_t ldy, int64_t M, int N, int K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
+
 /* ---- w8a8 int8: the reference's W-int8-channel-sym-A-int8-channel-sym-dynamic-* operators (mm_weight.py:322-354 Vllm, :592-... Sgl-ActVllm;
  * weight load :185-201, activation quantiser :247-249).  Numeric contract, every fp32 operation IEEE and correctly rounded:
  *   activation  amax = max|x[m,:]|, scale[m] = amax / 127.0f, inv = 127.0f / amax, q = clamp(rint(float(x) * inv), -128, 127), round half to

@@ -82,6 +82,9 @@ PROTOTYPES = {
     "x2v_gemm_mxfp4_epi": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
     "x2v_gemm_mxfp4": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p],
     "x2v_gemm_fp8": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "x2v_quant_fp8_group128": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p],
+    "x2v_gemm_fp8_block128": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p,
+                              _c_void_p],
     "x2v_gemm_fp8_variant": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p],
     "x2v_quant_int8_rowwise": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
     "x2v_quant_int8_rowwise_blocked": [_c_void_p, _i64, _i32, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p],
@@ -1129,6 +1132,59 @@ def gemm_int8(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=
     arguments as gemm_fp8.  variant: 1 = the 128x128 kernel (every legal shape), 5 = the continuous 256x256 kernel (X2VError where the shape does not
     allow it), 0 = chosen by shape (gemm_int8_kernel_choice tells which); 2, 3, 4 are refused: there is no int8 ping-pong kernel."""
     return _gemm8(_INT8, xq, sx, wq_nk, sw, bias, epilogue, resid, gate, out, variant, resid_period)
+
+
+def quant_fp8_group128(x):
+    """(e4m3 codes [M, K] row-major, fp32 scales [M, K/128]) of a bf16 x [M, K], K % 128 == 0: one scale per token and 128 K elements, the reference's
+    act_quant_fp8_perchannelgroup128_sym_deepgemm bit for bit (x2v_quant_fp8_group128).  The scales are stored k-group-major: the returned tensor is
+    the transposed view of a contiguous [K/128, M] table, which is what gemm_fp8_block128 reads."""
+    x2 = _row2d(_bf16(x, "x"), "x")
+    M, K = x2.shape
+    if K % 128:
+        raise X2VError(f"quant_fp8_group128: K={K} must be a multiple of 128")
+    xq = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    s = torch.empty((K // 128, M), dtype=torch.float32, device=x.device)
+    init()
+    if M:
+        _check(_lib.x2v_quant_fp8_group128(_p(x2), x2.stride(0), _p(xq), xq.stride(0), _p(s), max(s.stride(0), M), M, K, _stream()), "quant_fp8_group128")
+    return xq, s.t()
+
+
+def gemm_fp8_block128(xq, sx, wq_nk, sw, bias=None, epilogue=EPI_NONE, resid=None, gate=None, out=None):
+    """epi(sum_g (sx[m, g] * sw[n / 128, g]) * (xq . wq^T)_g + bias) -> bf16 [M, N] (x2v_gemm_fp8_block128): xq [M, K], wq_nk [N, K] e4m3 codes, sx fp32
+    [M, K/128] as quant_fp8_group128 returns it (unit stride along M), sw fp32 [ceil(N/128), K/128] with unit inner stride.  epilogue, resid, gate, out
+    as gemm_fp8."""
+    who = "gemm_fp8_block128"
+    if xq.dim() != 2 or wq_nk.dim() != 2 or xq.dtype != torch.float8_e4m3fn or wq_nk.dtype != torch.float8_e4m3fn:
+        raise X2VError(f"{who}: operands must be float8_e4m3fn (OCP; gfx950) matrices")
+    (M, K), N = xq.shape, wq_nk.shape[0]
+    if wq_nk.shape[1] != K or not xq.is_cuda or not wq_nk.is_cuda or xq.stride(1) != 1 or wq_nk.stride(1) != 1:
+        raise X2VError(f"{who}: xq {tuple(xq.shape)} / wq {tuple(wq_nk.shape)} must be device matrices with unit inner stride and equal K")
+    G, NB = K // 128, -(-N // 128)
+    if sx.dtype != torch.float32 or tuple(sx.shape) != (M, G) or (M > 1 and sx.stride(0) != 1) or not sx.is_cuda:
+        raise X2VError(f"{who}: activation scales must be fp32 [{M}, {G}] stored k-group-major (what quant_fp8_group128 returns), got {tuple(sx.shape)} strides {sx.stride()}")
+    if sw.dtype != torch.float32 or tuple(sw.shape) != (NB, G) or (G > 1 and sw.stride(1) != 1) or not sw.is_cuda:
+        raise X2VError(f"{who}: weight scales must be fp32 [{NB}, {G}] with unit inner stride, got {tuple(sw.shape)} strides {sw.stride()}")
+    if epilogue == EPI_RESIDUAL:
+        if resid is None:
+            raise X2VError(f"{who}: residual epilogue needs resid")
+        out2 = _row2d(resid if out is None else out, "out")
+        r2 = _row2d(_bf16(resid, "resid"), "resid")
+        gate = _vec(gate, f"{who} gate", N)
+    else:
+        out2 = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device) if out is None else _row2d(out, "out")
+        r2 = None
+    if tuple(out2.shape) != (M, N) or out2.dtype != torch.bfloat16:
+        raise X2VError(f"{who}: out is {tuple(out2.shape)} {out2.dtype}, expected bf16 {(M, N)}")
+    bias = _vec(bias, f"{who} bias", N)
+    init()
+    if M == 0:
+        return out2
+    lds = max(sx.stride(1), M) if G > 1 else M
+    ldsw = max(sw.stride(0), G) if NB > 1 else G
+    _check(_lib.x2v_gemm_fp8_block128(_p(xq), xq.stride(0), _p(sx), lds, _p(wq_nk), wq_nk.stride(0), _p(sw), ldsw, _p(bias), _p(out2), out2.stride(0), M, N, K, epilogue,
+                                      _p(r2), 0 if r2 is None else r2.stride(0), _p(gate) if epilogue == EPI_RESIDUAL else None, _stream()), who)
+    return out2
 
 
 def gemm_int8_kernel_choice(M, N, K, ldx=None, ldw=None, with_form=False):

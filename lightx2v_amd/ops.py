@@ -5,6 +5,7 @@ Every class honours the reference's duck-typed protocol — ctor signature, `set
 so an unchanged LightX2V config selects them by string:
 
     mm_config.mm_type      = "Hip-bf16" | "W-fp8-channel-sym-A-fp8-channel-sym-dynamic-Hip" | "W-int8-channel-sym-A-int8-channel-sym-dynamic-Hip"
+                             | "W-fp8-block128-sym-A-fp8-channel-group128-sym-dynamic-Hip"
     self_attn_1_type / cross_attn_1_type / attention_type = "hip_flash"
     RMS / LN registries    : key "hip"   (also aliased as "Default"/"sgl-kernel" inside this package, since the
                              reference's weight classes hard-code those keys: transformer_weights.py:127,159,167)
@@ -195,6 +196,73 @@ class MMWeightInt8Hip(MMWeightFp8Hip):
         return lib.layernorm_quant_int8(x, weight, bias, scale, shift, eps)
 
     _gemm, _gemm_blocked = staticmethod(lib.gemm_int8), staticmethod(lib.gemm_int8_blocked)
+
+
+@MM_WEIGHT_REGISTER("W-fp8-block128-sym-A-fp8-channel-group128-sym-dynamic-Hip")
+class MMWeightFp8Block128Hip(_Movable):
+    """reference: mm_weight.py:418-494 (the two Deepgemm classes): e4m3fn weight [N,K] with one fp32 scale per 128 x 128 block,
+    `<name>.weight_scale` [ceil(N/128), ceil(K/128)] (load :203-216), or quantised at load from a 16-bit weight / under `weight_auto_quant`
+    (per_block_cast_to_fp8, :218-230); activations quantised per call with one scale per token and 128 K elements (:251-256); block-scaled GEMM
+    (lib.gemm_fp8_block128).  MMWeightFp8Hip's protocol, without the block-strided and residual-period forms: the fused drivers take their plain
+    paths, and LayerNorm outputs are quantised by `quantize_input`."""
+
+    _tensor_attrs = ("weight", "weight_scale", "bias")
+
+    def __init__(self, weight_name, bias_name, lazy_load=False, lazy_load_file=None):
+        self.weight_name, self.bias_name = weight_name, bias_name
+        self.weight_scale_name = weight_name.removesuffix(".weight") + ".weight_scale"
+        self.lazy_load, self.lazy_load_file = lazy_load, lazy_load_file
+        self.config = {}
+        self.weight = self.weight_scale = self.bias = None
+
+    @staticmethod
+    def per_block_cast_to_fp8(w):
+        """mm_weight.py:218-230 restated: (e4m3 codes [N, K], fp32 scales [ceil(N/128), ceil(K/128)]).  torch evaluates the reference's
+        `448.0 / amax` as amax.reciprocal() * 448.0 — written out here; the scale amax / 448 takes a tensor divisor for MMWeightFp8Hip.load's reason."""
+        n, k = w.shape
+        nb, kb = -(-n // 128), -(-k // 128)
+        padded = torch.zeros((nb * 128, kb * 128), dtype=w.dtype, device=w.device)
+        padded[:n, :k] = w
+        view = padded.view(nb, 128, kb, 128)
+        amax = view.abs().float().amax(dim=(1, 3), keepdim=True).clamp(1e-4)
+        codes = (view * (amax.reciprocal() * 448.0)).to(torch.float8_e4m3fn)
+        return codes.view_as(padded)[:n, :k].contiguous(), (amax / torch.tensor(448.0, dtype=torch.float32, device=w.device)).view(nb, kb)
+
+    def load(self, weight_dict):
+        w = weight_dict[self.weight_name]
+        if self.config.get("weight_auto_quant", False) or w.dtype != torch.float8_e4m3fn:
+            self.weight, self.weight_scale = self.per_block_cast_to_fp8(w)
+        else:
+            self.weight = w.contiguous()
+            self.weight_scale = weight_dict[self.weight_scale_name].float().contiguous()
+        self.bias = weight_dict[self.bias_name] if self.bias_name is not None else None
+
+    def load_from_disk(self):
+        self.weight = self.lazy_load_file.get_tensor(self.weight_name).contiguous()
+        self.weight_scale = self.lazy_load_file.get_tensor(self.weight_scale_name).float().contiguous()
+        self.bias = self.lazy_load_file.get_tensor(self.bias_name).to(torch.bfloat16) if self.bias_name is not None else None
+
+    def quantize_input(self, input_tensor):
+        """Dynamic e4m3 quantisation per token and 128 K elements (mm_weight.py:251-256): (codes [M, K], fp32 scales [M, K/128])."""
+        return lib.quant_fp8_group128(input_tensor)
+
+    def apply(self, input_tensor, epilogue=lib.EPI_NONE, resid=None, gate=None, out=None, row_slice=None, quantized=None):
+        xq, sx = self.quantize_input(input_tensor) if quantized is None else quantized
+        w, sw, b = self.weight, self.weight_scale, self.bias
+        if row_slice is not None:  # whole scale blocks only: the slice starts on a block row of weight_scale
+            start, stop, step = row_slice.indices(w.shape[0])
+            if step != 1 or start % 128:
+                raise lib.X2VError(f"{self.weight_name}: row_slice {row_slice} must start on a multiple of 128 rows (one weight scale per 128 x 128 block)")
+            w, sw, b = w[row_slice], sw[start // 128 : -(-stop // 128)], (None if b is None else b[row_slice])
+        return lib.gemm_fp8_block128(xq, sx, w, sw, b, epilogue=epilogue, resid=resid, gate=gate, out=out)
+
+    def state_dict(self, destination=None):
+        destination = {} if destination is None else destination
+        destination[self.weight_name] = self.weight.cpu().detach().clone()
+        destination[self.weight_scale_name] = self.weight_scale.cpu().detach().clone()
+        if self.bias is not None:
+            destination[self.bias_name] = self.bias.cpu().detach().clone()
+        return destination
 
 
 # ------------------------------------------------------------------------------------------------ norms
